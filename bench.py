@@ -44,11 +44,22 @@ def progress(msg: str):
     print(f"[bench +{time.perf_counter() - _T0:6.1f}s] {msg}", file=sys.stderr, flush=True)
 
 
+def _count(minimum: int):
+    def parse_count(s: str) -> int:
+        v = int(s)
+        if v < minimum:
+            raise argparse.ArgumentTypeError(f"must be >= {minimum}, got {v}")
+        return v
+    return parse_count
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=_count(1), default=3, help="timed denoise steps (past the end of the schedule it starts over)")
+    ap.add_argument("--warmup", type=_count(0), default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what they returned (rank 0's latents) as DIR/latents.npy, float32")
     ap.add_argument("--workload", default="K3", choices=sorted(WORKLOADS))
     ap.add_argument("--num-inference-steps", type=int, default=50)
     ap.add_argument("--guidance-scale", type=float, default=4.0)
@@ -303,6 +314,23 @@ def measure_extras(dit, dev, T, h, w, pe, pm) -> dict:
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, arrays: dict) -> None:
+    """`<name>.npy` per array, float32, so that two builds run with the same arguments can be compared output for output.
+    The largest workload's latents (K3p) are 45 MB: every one is written whole."""
+    import numpy as np
+    host = {name: a.detach().float().cpu().numpy() for name, a in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte budget")
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in host.items():
+        np.save(out_dir / f"{name}.npy", a)
+    progress(f"outputs of the last timed step written to {out_dir}: {', '.join(f'{n}{list(a.shape)}' for n, a in host.items())}")
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` with no torch.distributed environment: start N ranks of this same file under
     torch.distributed.run (one process per GPU over RCCL) as a CHILD process, relay its output — rank 0 prints the one JSON
@@ -377,9 +405,17 @@ def main():
     nm = torch.zeros((1, 512), dtype=torch.int64, device=dev)
     nm[:, :77] = 1
 
-    def run(start, stop, x):
-        return pipe.denoise(x, pe, pm, ne, nm, num_cond_latents=0, num_inference_steps=args.num_inference_steps,
-                            guidance_scale=args.guidance_scale, start_step=start, stop_step=stop)
+    def run(first, count, x):
+        """`count` denoise steps from schedule step `first` on; a step past the end of the schedule starts it over from the
+        current latents, so --warmup and --steps are step counts whatever --num-inference-steps is."""
+        n = args.num_inference_steps
+        while count > 0:
+            start = first % n
+            stop = min(start + count, n)
+            x = pipe.denoise(x, pe, pm, ne, nm, num_cond_latents=0, num_inference_steps=n,
+                             guidance_scale=args.guidance_scale, start_step=start, stop_step=stop)
+            first, count = first + stop - start, count - (stop - start)
+        return x
 
     x = latents
     x = run(0, args.warmup, x)  # W untimed warm-up steps (also builds the fused-weight copies)
@@ -390,7 +426,7 @@ def main():
     progress(f"timed region: {args.steps} CFG denoise step(s)")
     ops.PROFILE = []  # (start_event, end_event, flops, Nq, Nk, kernel name) per attention launch, recorded on the launch stream
     t0 = time.perf_counter()
-    x = run(args.warmup, args.warmup + args.steps, x)
+    x = run(args.warmup, args.steps, x)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -406,6 +442,8 @@ def main():
         dist.all_reduce(ones)                      # the group size as a real RCCL all-reduce sees it
         rccl_ranks = int(ones.item())
     assert torch.isfinite(x).all().item(), "non-finite latents"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), {"latents": x})
 
     sec_per_step = elapsed / args.steps
     progress(f"timed region done: {sec_per_step:.3f} s per step")
