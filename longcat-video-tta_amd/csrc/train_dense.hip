@@ -23,7 +23,7 @@ __global__ __launch_bounds__(256) void transpose_pad_kernel(const bf16_t* __rest
     u16x4 v = {0, 0, 0, 0};
     const int64_t m = m0 + r, n = n0 + c4;
     if (m < M) {
-      if (n + 3 < N && ((ld | n) & 3) == 0) {
+      if (n + 3 < N && ((ld | n) & 3) == 0 && (((uintptr_t)in) & 7) == 0) {   // whole, 8-byte aligned packet
         v = *reinterpret_cast<const u16x4*>(in + m * ld + n);
       } else {
 #pragma unroll
@@ -127,6 +127,7 @@ extern "C" int lcv_transpose_pad(const void* in, void* out, int64_t M, int64_t N
   LCV_CHECK_ARG(in && out, "transpose_pad: null pointer");
   LCV_CHECK_ARG(M > 0 && N > 0 && ld >= N && Mpad >= M && Mpad % 64 == 0, "transpose_pad: M=%ld N=%ld ld=%ld Mpad=%ld (Mpad must be a multiple of 64)",
                 (long)M, (long)N, (long)ld, (long)Mpad);
+  LCV_CHECK_ARG((((uintptr_t)out) & 7) == 0, "transpose_pad: out must be 8-byte aligned (4-element packets are stored)");
   LCV_CHECK_ARG(Mpad / 64 <= 0x7fffffff && (N + 63) / 64 <= 65535, "transpose_pad: grid too large");
   hipLaunchKernelGGL(transpose_pad_kernel, dim3((unsigned)(Mpad / 64), (unsigned)((N + 63) / 64)), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)in, (bf16_t*)out, M, N, ld, Mpad);
@@ -136,6 +137,7 @@ extern "C" int lcv_transpose_pad(const void* in, void* out, int64_t M, int64_t N
 
 extern "C" int lcv_rowsum(const void* in, void* out, int64_t rows, int64_t cols, int out_f32, void* stream) {
   LCV_CHECK_ARG(in && out && rows > 0 && cols > 0 && cols % 8 == 0, "rowsum: bad arguments (cols must be a multiple of 8)");
+  LCV_CHECK_ARG((((uintptr_t)in) & 15) == 0, "rowsum: in must be 16-byte aligned (8-element packets are loaded)");
   hipLaunchKernelGGL(rowsum_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)in, out,
                      rows, cols, out_f32);
   LCV_LAUNCH_CHECK("rowsum");

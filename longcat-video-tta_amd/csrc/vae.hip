@@ -115,6 +115,9 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 extern "C" int lcv_softmax_rows(const float* s, void* p, int64_t rows, int64_t n, int64_t ld_s, int64_t ld_p,
                                 float scale, void* stream) {
   LCV_CHECK_ARG(s && p && n > 0 && ld_s >= n && ld_p >= n, "softmax_rows: bad arguments");
+  // the shift is max(s), not max(scale * s): it only bounds the exponent by 0 when scale > 0 (a negative scale would
+  // overflow __expf once |scale| * (max - min) > 88); the one caller passes head_dim^-0.5
+  LCV_CHECK_ARG(scale > 0.f && scale <= 3.4e38f, "softmax_rows: scale %g must be positive and finite", (double)scale);
   if (rows == 0) return LCV_OK;
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, s, (bf16_t*)p, n,
                      ld_s, ld_p, scale);
