@@ -56,9 +56,134 @@ __device__ __forceinline__ float w64_half_sum(float v) {
 __device__ __forceinline__ float w_exp2(float x) { float y; asm volatile("v_exp_f32 %0, %1" : "=v"(y) : "v"(x)); return y; }
 __device__ __forceinline__ float w_add(float a, float b) { float y; asm volatile("v_add_f32 %0, %1, %2" : "=v"(y) : "v"(a), "v"(b)); return y; }
 __device__ __forceinline__ float w_max3(float a, float b, float c) { float y; asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(y) : "v"(a), "v"(b), "v"(c)); return y; }
-typedef __attribute__((ext_vector_type(2))) float f32x2w;
-__device__ __forceinline__ f32x2w w_pk_add(f32x2w a, f32x2w b) { f32x2w y; asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(y) : "v"(a), "v"(b)); return y; }
 __device__ __forceinline__ unsigned w_pack(float lo, float hi) { unsigned y; asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(y) : "v"(lo), "v"(hi)); return y; }
+
+// ---- the gap table of the steady loop: what follows each MFMA of phase 1 (score MFMA i) and phase 2 (PV MFMA j) ----
+// At one wave per SIMD a v_mfma_f32_32x32x16_bf16 hides about 5 single-issue instructions / 24 issue-cycles with at most one
+// 8-cycle transcendental (MI355X issue-cost constants: v_exp 8, v_cvt_pk 5, the rest 4).  An iteration carries more than the
+// 64 gaps can hide once the row sums are scalar (64 exp, 32 pack, 64 add, 32 max3, 48 fragment reads and their waits, 8 DMA
+// pieces, 8 offset moves: ~1 560 issue-cycles against 64 x 24), so the table spreads the load: 3 exps per 2 gaps in phase 1
+// with the pair on the read-free (even) gaps, phase 2's exps over gaps 0..21, its DMA pieces on the read-free even gaps 0..14,
+// the row-max chain in gaps 8..23 and its exchange / ballot in the otherwise empty tail.  tools/mfma_gaps.py prices the
+// compiler's output gap by gap; tests/test_attn_fwd_gap_budget.py holds it there.
+// Order inside a gap is the order of the entries: packs / adds of earlier exps first, the gap's own exps last, so that no VALU
+// reads a v_exp result right behind it (hipcc pads that with an s_nop) and every pack is far ahead of the PV MFMA that reads it.
+template <int I, int N, class F>
+__device__ __forceinline__ void w64_static_for(F&& f) {
+  if constexpr (I < N) { f(std::integral_constant<int, I>{}); w64_static_for<I + 1, N>(f); }
+}
+enum : unsigned char { W64_NONE, W64_EXP, W64_ADD, W64_PACK, W64_LRUN, W64_VOFF, W64_MAX, W64_HMAX, W64_BALLOT, W64_M0, W64_DMA };
+struct W64Op { unsigned char kind, b, e; };   // b: query block (or DMA piece / offset index), e: element / pair / max step
+constexpr int W64_SLOTS = 6;
+// EXP b e: ex[b][e] = exp2(S(t)[b][e]) | ADD b e: psum[b] += ex[b][e] (e = 1: psum = ex[0] + ex[1]), the two-wave kernel's
+// order | PACK b m: pw[b][m] = bf16(ex[b][2m], ex[b][2m+1]) | LRUN b: l_run[b] += psum[b] | VOFF k: V read offset k to tile
+// t's slot | MAX b s: step s of block b's two max3 chains over S(t+1) | HMAX b: exchange with the partner half | BALLOT b:
+// rescale test | M0 d / DMA d: LDS destination and request of DMA piece d (d < 4: K(t+3), else V(t+2)), one gap apart or more
+// (the number after each row: the gap's issue-cycles at the prices above, its fragment read and wait included)
+constexpr W64Op W64_P1[32][W64_SLOTS] = {
+  {{W64_EXP, 0, 0}, {W64_EXP, 1, 0}},   //  0: 16
+  {{W64_EXP, 0, 1}},   //  1: 16
+  {{W64_PACK, 0, 0}, {W64_ADD, 0, 1}, {W64_EXP, 1, 1}, {W64_EXP, 0, 2}},   //  2: 25
+  {{W64_ADD, 0, 2}, {W64_PACK, 1, 0}, {W64_ADD, 1, 1}, {W64_EXP, 1, 2}},   //  3: 29
+  {{W64_ADD, 1, 2}, {W64_EXP, 0, 3}, {W64_EXP, 1, 3}},   //  4: 20
+  {{W64_PACK, 0, 1}, {W64_ADD, 0, 3}, {W64_PACK, 1, 1}, {W64_ADD, 1, 3}, {W64_EXP, 0, 4}},   //  5: 34
+  {{W64_ADD, 0, 4}, {W64_EXP, 1, 4}, {W64_EXP, 0, 5}},   //  6: 20
+  {{W64_PACK, 0, 2}, {W64_ADD, 0, 5}, {W64_ADD, 1, 4}, {W64_EXP, 1, 5}},   //  7: 29
+  {{W64_PACK, 1, 2}, {W64_ADD, 1, 5}, {W64_EXP, 0, 6}, {W64_EXP, 1, 6}},   //  8: 25
+  {{W64_ADD, 0, 6}, {W64_ADD, 1, 6}, {W64_EXP, 0, 7}},   //  9: 24
+  {{W64_VOFF, 0, 0}, {W64_PACK, 0, 3}, {W64_ADD, 0, 7}, {W64_EXP, 1, 7}, {W64_EXP, 0, 8}},   // 10: 29
+  {{W64_VOFF, 1, 0}, {W64_ADD, 0, 8}, {W64_PACK, 1, 3}, {W64_ADD, 1, 7}, {W64_EXP, 1, 8}},   // 11: 33
+  {{W64_VOFF, 2, 0}, {W64_ADD, 1, 8}, {W64_EXP, 0, 9}, {W64_EXP, 1, 9}},   // 12: 24
+  {{W64_VOFF, 3, 0}, {W64_PACK, 0, 4}, {W64_ADD, 0, 9}, {W64_PACK, 1, 4}, {W64_ADD, 1, 9}, {W64_EXP, 0, 10}},   // 13: 38
+  {{W64_VOFF, 4, 0}, {W64_ADD, 0, 10}, {W64_EXP, 1, 10}, {W64_EXP, 0, 11}},   // 14: 24
+  {{W64_VOFF, 5, 0}, {W64_PACK, 0, 5}, {W64_ADD, 0, 11}, {W64_ADD, 1, 10}, {W64_EXP, 1, 11}},   // 15: 33
+  {{W64_VOFF, 6, 0}, {W64_PACK, 1, 5}, {W64_ADD, 1, 11}, {W64_EXP, 0, 12}, {W64_EXP, 1, 12}},   // 16: 29
+  {{W64_VOFF, 7, 0}, {W64_ADD, 0, 12}, {W64_ADD, 1, 12}, {W64_EXP, 0, 13}},   // 17: 28
+  {{W64_PACK, 0, 6}, {W64_ADD, 0, 13}, {W64_EXP, 1, 13}, {W64_EXP, 0, 14}},   // 18: 25
+  {{W64_ADD, 0, 14}, {W64_PACK, 1, 6}, {W64_ADD, 1, 13}, {W64_EXP, 1, 14}},   // 19: 29
+  {{W64_ADD, 1, 14}, {W64_EXP, 0, 15}, {W64_EXP, 1, 15}},   // 20: 20
+  {{W64_PACK, 0, 7}, {W64_ADD, 0, 15}, {W64_PACK, 1, 7}, {W64_ADD, 1, 15}, {W64_EXP, 0, 16}},   // 21: 34
+  {{W64_ADD, 0, 16}, {W64_EXP, 1, 16}, {W64_EXP, 0, 17}},   // 22: 20
+  {{W64_PACK, 0, 8}, {W64_ADD, 0, 17}, {W64_ADD, 1, 16}, {W64_EXP, 1, 17}},   // 23: 29
+  {{W64_PACK, 1, 8}, {W64_ADD, 1, 17}, {W64_EXP, 0, 18}, {W64_EXP, 1, 18}},   // 24: 25
+  {{W64_ADD, 0, 18}, {W64_ADD, 1, 18}, {W64_EXP, 0, 19}},   // 25: 24
+  {{W64_PACK, 0, 9}, {W64_ADD, 0, 19}, {W64_EXP, 1, 19}, {W64_EXP, 0, 20}},   // 26: 25
+  {{W64_ADD, 0, 20}, {W64_PACK, 1, 9}, {W64_ADD, 1, 19}, {W64_EXP, 1, 20}},   // 27: 33
+  {{W64_ADD, 1, 20}, {W64_EXP, 0, 21}, {W64_EXP, 1, 21}},   // 28: 20
+  {{W64_PACK, 0, 10}, {W64_ADD, 0, 21}, {W64_PACK, 1, 10}, {W64_ADD, 1, 21}, {W64_EXP, 0, 22}},   // 29: 38
+  {{W64_ADD, 0, 22}, {W64_EXP, 1, 22}, {W64_EXP, 0, 23}},   // 30: 20
+  {{W64_PACK, 0, 11}, {W64_ADD, 0, 23}, {W64_ADD, 1, 22}, {W64_EXP, 1, 23}},   // 31: 21
+};
+constexpr W64Op W64_P2[32][W64_SLOTS] = {
+  {{W64_M0, 0, 0}, {W64_PACK, 1, 11}, {W64_ADD, 1, 23}, {W64_EXP, 0, 24}, {W64_DMA, 0, 0}},   //  0: 25
+  {{W64_ADD, 0, 24}, {W64_EXP, 1, 24}},   //  1: 24
+  {{W64_M0, 1, 0}, {W64_ADD, 1, 24}, {W64_EXP, 0, 25}, {W64_DMA, 1, 0}},   //  2: 20
+  {{W64_PACK, 0, 12}, {W64_ADD, 0, 25}},   //  3: 21
+  {{W64_M0, 2, 0}, {W64_EXP, 1, 25}, {W64_DMA, 2, 0}},   //  4: 16
+  {{W64_PACK, 1, 12}, {W64_ADD, 1, 25}, {W64_EXP, 0, 26}},   //  5: 29
+  {{W64_M0, 3, 0}, {W64_ADD, 0, 26}, {W64_DMA, 3, 0}},   //  6: 12
+  {{W64_EXP, 1, 26}},   //  7: 20
+  {{W64_M0, 4, 0}, {W64_ADD, 1, 26}, {W64_MAX, 0, 0}, {W64_EXP, 0, 27}, {W64_DMA, 4, 0}},   //  8: 28
+  {{W64_PACK, 0, 13}, {W64_ADD, 0, 27}, {W64_MAX, 1, 0}},   //  9: 29
+  {{W64_M0, 5, 0}, {W64_MAX, 0, 1}, {W64_EXP, 1, 27}, {W64_DMA, 5, 0}},   // 10: 24
+  {{W64_PACK, 1, 13}, {W64_ADD, 1, 27}, {W64_MAX, 1, 1}, {W64_EXP, 0, 28}},   // 11: 37
+  {{W64_M0, 6, 0}, {W64_ADD, 0, 28}, {W64_MAX, 0, 2}, {W64_EXP, 1, 28}, {W64_DMA, 6, 0}},   // 12: 28
+  {{W64_ADD, 1, 28}, {W64_MAX, 1, 2}},   // 13: 24
+  {{W64_M0, 7, 0}, {W64_MAX, 0, 3}, {W64_EXP, 0, 29}, {W64_DMA, 7, 0}},   // 14: 24
+  {{W64_PACK, 0, 14}, {W64_ADD, 0, 29}, {W64_MAX, 1, 3}, {W64_EXP, 1, 29}},   // 15: 37
+  {{W64_PACK, 1, 14}, {W64_ADD, 1, 29}, {W64_MAX, 0, 4}},   // 16: 17
+  {{W64_MAX, 1, 4}, {W64_EXP, 0, 30}},   // 17: 28
+  {{W64_ADD, 0, 30}, {W64_MAX, 0, 5}, {W64_EXP, 1, 30}},   // 18: 20
+  {{W64_ADD, 1, 30}, {W64_MAX, 1, 5}},   // 19: 24
+  {{W64_MAX, 0, 6}, {W64_EXP, 0, 31}},   // 20: 16
+  {{W64_PACK, 0, 15}, {W64_ADD, 0, 31}, {W64_MAX, 1, 6}, {W64_EXP, 1, 31}},   // 21: 37
+  {{W64_PACK, 1, 15}, {W64_ADD, 1, 31}, {W64_LRUN, 0, 0}, {W64_MAX, 0, 7}},   // 22: 21
+  {{W64_LRUN, 1, 0}, {W64_MAX, 1, 7}},   // 23: 24
+  {{W64_HMAX, 0, 0}},   // 24: 20
+  {{W64_HMAX, 1, 0}},   // 25: 32
+  {{W64_BALLOT, 0, 0}},   // 26: 4
+  {{W64_BALLOT, 1, 0}},   // 27: 12
+  {},   // 28: 0
+  {},   // 29: 8
+  {},   // 30: 0
+  {},   // 31: 0
+};
+// issue-cycle price of a table entry, and of the fragment reads hipcc places at the end of gap i (a read and its wait)
+constexpr int w64_op_cost(W64Op o) {
+  return o.kind == W64_EXP ? 8 : o.kind == W64_PACK ? 5 : o.kind == W64_MAX ? 8 : o.kind == W64_HMAX ? 20 :
+         o.kind == W64_NONE ? 0 : 4;
+}
+constexpr int w64_read_cost(int phase, int i) {
+  return !(i & 1) || i > 29 ? 0 : ((phase == 1 && i >= 27) || (phase == 2 && i <= 25)) ? 12 : 8;
+}
+constexpr bool w64_table_ok(const W64Op (&t)[32][W64_SLOTS], int phase, int max_cyc, int max_exp) {
+  for (int i = 0; i < 32; ++i) {
+    int c = w64_read_cost(phase, i), ex = 0;
+    for (int s = 0; s < W64_SLOTS; ++s) { c += w64_op_cost(t[i][s]); ex += t[i][s].kind == W64_EXP; }
+    if (c > max_cyc || ex > max_exp) return false;
+  }
+  return true;
+}
+constexpr bool w64_table_complete() {   // every exp, add, pack exactly once; each after what it reads
+  int exp_at[2][32] = {}, add_at[2][32] = {}, pack_at[2][16] = {}, n = 0;
+  for (int b = 0; b < 2; ++b) for (int e = 0; e < 32; ++e) { exp_at[b][e] = -1; add_at[b][e] = -1; }
+  for (int b = 0; b < 2; ++b) for (int m = 0; m < 16; ++m) pack_at[b][m] = -1;
+  for (int g = 0; g < 64; ++g)
+    for (int s = 0; s < W64_SLOTS; ++s) {
+      const W64Op o = g < 32 ? W64_P1[g][s] : W64_P2[g - 32][s];
+      const int at = 8 * g + s;
+      if (o.kind == W64_EXP) { if (exp_at[o.b][o.e] >= 0) return false; exp_at[o.b][o.e] = at; ++n; }
+      if (o.kind == W64_ADD) { if (o.e == 0 || exp_at[o.b][o.e] < 0 || (o.e > 1 && add_at[o.b][o.e - 1] < 0)) return false; add_at[o.b][o.e] = at; }
+      if (o.kind == W64_PACK) { if (exp_at[o.b][2 * o.e] < 0 || exp_at[o.b][2 * o.e + 1] < 0) return false; pack_at[o.b][o.e] = at; }
+      if (o.kind == W64_LRUN && add_at[o.b][31] < 0) return false;
+    }
+  for (int b = 0; b < 2; ++b)
+    for (int m = 0; m < 16; ++m)   // pack of k-step m / 4 before PV MFMA 8 (m / 4) + b of phase 2 (MFMA j follows gap j - 1)
+      if (pack_at[b][m] < 0 || pack_at[b][m] >= 8 * (32 + 8 * (m / 4) + b - 1) + W64_SLOTS) return false;
+  return n == 64;
+}
+static_assert(w64_table_complete(), "attn_fwd_w64 gap table: an exp, add or pack is missing, doubled or out of order");
+static_assert(w64_table_ok(W64_P1, 1, 38, 2) && w64_table_ok(W64_P2, 2, 37, 1), "attn_fwd_w64 gap table over its budget");
 
 // GUARD: wait states in front of the MFMA wherever hipcc may have placed a register copy of one of its operands right before the
 // statement (everywhere outside the straight-line steady loop, and the first MFMAs of every phase)
@@ -142,6 +267,19 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
     // restored around every request: two scalar instructions less per request on a wave whose issue slots are the budget)
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
                  :: "v"(off), "s"(base), "s"(lds_wave + (unsigned)dst_tile + 1024u * i) : "memory", "m0");
+  };
+  // the same request in two statements, for the steady loop: the m0 write one or more instructions ahead of the request (the
+  // one wait state an LDS-DMA needs after an m0 write is then already there: no s_nop)
+  auto dma_m0 = [&](int i, int dst_tile) __attribute__((always_inline)) {
+    asm volatile("s_mov_b32 m0, %0" :: "s"(lds_wave + (unsigned)dst_tile + 1024u * i) : "memory", "m0");
+  };
+  auto dma_req = [&](int which, int i, int tile, bool known_full) __attribute__((always_inline)) {
+    const int64_t sn = which ? p.v_sn : p.k_sn;
+    const char* base = which ? vbase_u : kbase_u;
+    unsigned off = which ? voff[i] : koff[i];
+    if (!known_full && tile == nt - 1) off = last_off(i, sn);
+    else base += (int64_t)tile * (128 * sn);
+    asm volatile("global_load_lds_dwordx4 %0, %1" :: "v"(off), "s"(base) : "memory");
   };
   auto dma_tile = [&](int which, int dst_tile, int tile) __attribute__((always_inline)) {
 #pragma unroll
@@ -258,9 +396,6 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
 #ifndef W64_PD
 #define W64_PD 2
 #endif
-#ifndef W64_DMA_STRIDE
-#define W64_DMA_STRIDE 1
-#endif
   constexpr int PD = W64_PD, RING = PD + 1;   // fragments are requested PD fragments (= 2 PD MFMAs) ahead of their first use
   bf16x8 kfr[RING], vfr[RING];
   int v_slot = 2;
@@ -318,13 +453,50 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
     const bool has_v2 = STEADY || t + 2 < nt;
     const int v_delta = next_v_slot();                // v_slot == t % 3 from here on
     const int v_dst = V_REGION + ((v_slot == 0) ? 2 : v_slot - 1) * TILE;   // slot (t + 2) % 3
-    f32x2w psum[2];       // row sums of P(t), even / odd elements apart (v_pk_add_f32: one instruction per pair)
-    f32x2w ex[2][16];     // P(t) in fp32: pair m = elements (2m, 2m + 1)
+    float psum[2];        // row sums of P(t), one chain per query block in element order (attn_fwd_pipe.hip's order)
+    float ex[2][32];      // P(t) in fp32
     unsigned pw[2][16];   // P(t) as packed bf16 pairs: word m = elements (2m, 2m + 1)
+    float mxa[2] = {0.f, 0.f}, mxb[2] = {0.f, 0.f}, mxh[2] = {0.f, 0.f};
+    bool need[2] = {false, false};
+    // one entry of the gap table (every field folds to a constant once the phase loops are unrolled)
+    auto run_op = [&](auto phase_c, auto gap_c, auto slot_c) __attribute__((always_inline)) {
+      constexpr W64Op o = decltype(phase_c)::value == 1 ? W64_P1[decltype(gap_c)::value][decltype(slot_c)::value]
+                                                        : W64_P2[decltype(gap_c)::value][decltype(slot_c)::value];
+      constexpr int b_ = o.b, e = o.e;
+      if constexpr (o.kind == W64_EXP) ex[b_][e] = w_exp2(SCW(c, b_, e));
+      if constexpr (o.kind == W64_ADD) psum[b_] = w_add((e == 1) ? ex[b_][0] : psum[b_], ex[b_][e]);
+      if constexpr (o.kind == W64_PACK) pw[b_][e] = w_pack(ex[b_][2 * e], ex[b_][2 * e + 1]);
+      if constexpr (o.kind == W64_LRUN) l_run[b_] = w_add(l_run[b_], psum[b_]);
+      if constexpr (o.kind == W64_VOFF) asm volatile("v_add_u32 %0, %1, %0" : "+v"(v_off[b_ >> 2][b_ & 3]) : "s"(v_delta));
+      if constexpr (o.kind == W64_MAX) {   // two chains of 8 max3 per query block; step 7 folds chain a into b: the full maximum
+        if constexpr (e == 0) {
+          mxa[b_] = w_max3(n[0][b_][0], n[0][b_][1], n[0][b_][2]);
+          mxb[b_] = w_max3(n[1][b_][0], n[1][b_][1], n[1][b_][2]);
+        } else if constexpr (e < 7) {
+          mxa[b_] = w_max3(mxa[b_], n[0][b_][2 * e + 1], n[0][b_][2 * e + 2]);
+          mxb[b_] = w_max3(mxb[b_], n[1][b_][2 * e + 1], n[1][b_][2 * e + 2]);
+        } else {
+          mxa[b_] = w_max3(mxa[b_], n[0][b_][15], mxb[b_]);
+          mxb[b_] = w_max3(mxa[b_], n[1][b_][15], n[1][b_][14]);
+        }
+      }
+      if constexpr (o.kind == W64_HMAX) mxh[b_] = w64_half_max(mxb[b_]);
+      if constexpr (o.kind == W64_BALLOT) need[b_] = __builtin_amdgcn_ballot_w64(mxh[b_] > W64_RESCALE_THR) != 0ull;
+      // the eight LDS-DMA requests of this iteration: K(t+3) into K(t+1)'s buffer, V(t+2) into V(t-1)'s slot (both free since
+      // the barrier); waited for at the next barrier, a whole iteration away
+      if constexpr (o.kind == W64_M0) {
+        if constexpr (b_ < 4) { if (has_k3) dma_m0(b_, (PAR ^ 1) * TILE); }
+        else { if (has_v2) dma_m0(b_ & 3, v_dst); }
+      }
+      if constexpr (o.kind == W64_DMA) {
+        if constexpr (b_ < 4) { if (has_k3) dma_req(KOP, b_, t + 3, STEADY); }
+        else { if (has_v2) dma_req(VOP, b_ & 3, t + 2, STEADY); }
+      }
+    };
     SCHED_FENCE();
     // ---------------- phase 1: 32 score MFMAs of tile t+1; exp2 / sums / packs of elements 0..23 of both query blocks ----------
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
+    w64_static_for<0, 32>([&](auto i_c) __attribute__((always_inline)) {
+      constexpr int i = decltype(i_c)::value;
       const int f = i >> 1, nb = i & 1;               // fragment f = (k-step f >> 1, key block f & 1) feeds MFMAs 2 f, 2 f + 1
       if (nb == 0) {
         if (f + PD < 16) kfr[(f + PD) % RING] = read_k(kb, f + PD);
@@ -338,30 +510,9 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
         else mfma_s<true>(n[f & 1][nb], kfr[f % RING], qf[nb][f >> 1]);
       }
       SCHED_FENCE();
-      // gaps 10..17: one of the eight V read offsets moves to tile t's slot (no V read is in flight between gap 0 and gap 27)
-      if (i >= 10 && i < 18) asm volatile("v_add_u32 %0, %1, %0" : "+v"(v_off[(i - 10) >> 2][(i - 10) & 3]) : "s"(v_delta));
-      // exps of this gap: indices [e_lo, e_hi) of 48 (index -> query block idx & 1, element idx >> 1); sums / packs trail one gap
-      const int e_lo = (3 * i + 1) / 2, e_hi = (3 * (i + 1) + 1) / 2;
-      const int a_lo = i ? (3 * (i - 1) + 1) / 2 : 0, a_hi = i ? e_lo : 0;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {                   // (at most two per gap; fixed trip count so that the loop unrolls)
-        const int x = e_lo + u;
-        if (x < e_hi) ex[x & 1][x >> 2][(x >> 1) & 1] = w_exp2(SCW(c, x & 1, x >> 1));
-      }
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int x = a_lo + u;
-        if (x < a_hi) {
-          const int b_ = x & 1, j = x >> 1;
-          if (j & 1) {                                  // pair j >> 1 of block b_ is complete
-            pw[b_][j >> 1] = w_pack(ex[b_][j >> 1][0], ex[b_][j >> 1][1]);
-            if (j == 3) psum[b_] = w_pk_add(ex[b_][0], ex[b_][1]);
-            else if (j > 3) psum[b_] = w_pk_add(psum[b_], ex[b_][j >> 1]);
-          }
-        }
-      }
+      w64_static_for<0, W64_SLOTS>([&](auto s_c) { run_op(std::integral_constant<int, 1>{}, i_c, s_c); });
       SCHED_FENCE();
-    }
+    });
     if constexpr (!STEADY) {
       fence_s(n);
       if (t + 1 == nt - 1 && ragged) mask_last(n);   // scalar branch, taken once
@@ -369,11 +520,9 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
     // the one barrier: K(t+2) and V(t+1) are in LDS for every wave; every wave has finished reading K(t+1) and V(t-1)
     dma_wait_and_barrier();
     // ---------------- phase 2: 32 PV MFMAs of tile t; the rest of P(t); row max of S(t+1); next requests and fragments --------
-    float mxa[2] = {0.f, 0.f}, mxb[2] = {0.f, 0.f}, mxh[2] = {0.f, 0.f};
-    bool need[2] = {false, false};
     SCHED_FENCE();
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
+    w64_static_for<0, 32>([&](auto j_c) __attribute__((always_inline)) {
+      constexpr int j = decltype(j_c)::value;
       const int g = j >> 1, nb = j & 1;               // fragment g = (k-step g >> 2, dim block g & 3) feeds MFMAs 2 g, 2 g + 1
       if (nb == 0) {
         if (g + PD < 16) vfr[(g + PD) % RING] = read_v(g + PD);
@@ -384,51 +533,9 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
       if (STEADY && j >= 2) mfma_o<false>(oacc[nb][g & 3], vfr[g % RING], __builtin_bit_cast(bf16x8, pbw));
       else mfma_o<true>(oacc[nb][g & 3], vfr[g % RING], __builtin_bit_cast(bf16x8, pbw));
       SCHED_FENCE();
-      // the eight LDS-DMA requests of this iteration: K(t+3) into K(t+1)'s buffer, V(t+2) into V(t-1)'s slot (both free since the
-      // barrier above); waited for at the next barrier, a whole iteration away
-      if (j % W64_DMA_STRIDE == 0 && j / W64_DMA_STRIDE < 8) {
-        const int dj = j / W64_DMA_STRIDE;
-        if (dj < 4) { if (has_k3) dma_one(KOP, dj & 3, (PAR ^ 1) * TILE, t + 3, STEADY); }
-        else { if (has_v2) dma_one(VOP, dj & 3, v_dst, t + 2, STEADY); }
-      }
-      // row max of S(t+1) first (gaps 0..15: per query block 16 max3 over its 32 values, two chains of 8), then the exchange with
-      // the partner half and the ballot in gaps 16..19: nothing but two scalar branches is left behind the phase
-      if (j < 16) {
-        const int b_ = j & 1, s_ = j >> 1;            // step 0..7 of block b_
-        if (s_ == 0) {
-          mxa[b_] = w_max3(n[0][b_][0], n[0][b_][1], n[0][b_][2]);
-          mxb[b_] = w_max3(n[1][b_][0], n[1][b_][1], n[1][b_][2]);
-        } else if (s_ < 7) {
-          mxa[b_] = w_max3(mxa[b_], n[0][b_][2 * s_ + 1], n[0][b_][2 * s_ + 2]);
-          mxb[b_] = w_max3(mxb[b_], n[1][b_][2 * s_ + 1], n[1][b_][2 * s_ + 2]);
-        } else {
-          mxa[b_] = w_max3(mxa[b_], n[0][b_][15], mxb[b_]);
-          mxb[b_] = w_max3(mxa[b_], n[1][b_][15], n[1][b_][14]);   // (the full maximum: chain a folded in)
-        }
-      }
-      if (j == 16 || j == 17) mxh[j & 1] = w64_half_max(mxb[j & 1]);
-      if (j == 18 || j == 19) need[j & 1] = __builtin_amdgcn_ballot_w64(mxh[j & 1] > W64_RESCALE_THR) != 0ull;
-      // quarter 3 of P(t): index 47 (query block 1, element 23) was exp'ed in the last gap of phase 1; elements 24..31 one exp per
-      // gap in gaps 6..21, the sum / pack two gaps later (the same block's next turn); all packs exist before the k-step 3 MFMAs
-      if (j == 0) {
-        psum[1] = w_pk_add(psum[1], ex[1][11]);
-        pw[1][11] = w_pack(ex[1][11][0], ex[1][11][1]);
-      }
-      if (j >= 6 && j < 22) {
-        const int b_ = j & 1, el = 24 + ((j - 6) >> 1);
-        ex[b_][el >> 1][el & 1] = w_exp2(SCW(c, b_, el));
-      }
-      if (j >= 8 && j < 24) {
-        const int b_ = j & 1, el = 24 + ((j - 8) >> 1);
-        if (el & 1) {
-          psum[b_] = w_pk_add(psum[b_], ex[b_][el >> 1]);
-          pw[b_][el >> 1] = w_pack(ex[b_][el >> 1][0], ex[b_][el >> 1][1]);
-        }
-      }
-      if (j == 24 || j == 25) psum[j & 1][0] = w_add(psum[j & 1][0], psum[j & 1][1]);
-      if (j == 26 || j == 27) l_run[j & 1] = w_add(l_run[j & 1], psum[j & 1][0]);
+      w64_static_for<0, W64_SLOTS>([&](auto s_c) { run_op(std::integral_constant<int, 2>{}, j_c, s_c); });
       SCHED_FENCE();
-    }
+    });
     settle(n, std::integral_constant<int, 0>{}, mxh[0], false, need[0]);
     settle(n, std::integral_constant<int, 1>{}, mxh[1], false, need[1]);
   };
