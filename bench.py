@@ -7,9 +7,15 @@ fused CFG-zero-star + Euler update.  `value` = T_lat / (num_inference_steps * se
 frames per second of the 50-step job, whole-job aggregate over ranks (data-parallel: one independent video per GPU,
 no data-path collective => "weak" scaling).  Inputs are resident in HBM before the timed region.
 
-Extra objects on the JSON line: `roofline` (flash-attention forward, the dominant kernel: algorithmic flops per launch
-/ its average launch duration measured with HIP events on the launch stream inside the timed region) and
-`cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample; rank 0, N=1 only).
+A plain run does only what that figure needs: set-up, the warm-up steps, the timed steps, `--dump-outputs` if asked for,
+and the JSON line.  Its `roofline` object (flash-attention forward, the dominant kernel: algorithmic flops per launch / its
+average launch duration measured with HIP events on the launch stream inside the timed region) costs no run of its own.
+
+`--full` adds everything else the benchmark measures, around the same warm-up and timed steps (about four minutes more on
+one GPU): `cpu_baseline` (the CPU oracle timed on this box's host cores on a bounded sample; rank 0, N=1 only), one CFG
+step at the other workloads (K2, K1, K5, K3p), and the legs of the per-video wall clock (the reference's 480p operating
+point, VAE decode, the LoRA-TTA inner loop with and without early stopping, `--full-tta-leg`).  `--no-cpu-baseline`,
+`--no-extras` and `--no-k3p` each take one of these out of a `--full` run again.
 """
 import argparse
 import json
@@ -39,7 +45,7 @@ _T0 = time.perf_counter()
 
 
 def progress(msg: str):
-    """One line per stage on stderr (stdout carries exactly one JSON line): a default run takes a few minutes and a
+    """One line per stage on stderr (stdout carries exactly one JSON line): a --full run takes a few minutes and a
     silent one looks hung to whoever launched it."""
     print(f"[bench +{time.perf_counter() - _T0:6.1f}s] {msg}", file=sys.stderr, flush=True)
 
@@ -53,7 +59,7 @@ def _count(minimum: int):
     return parse_count
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=_count(1), default=3, help="timed denoise steps (past the end of the schedule it starts over)")
@@ -64,18 +70,39 @@ def parse():
     ap.add_argument("--num-inference-steps", type=int, default=50)
     ap.add_argument("--guidance-scale", type=float, default=4.0)
     ap.add_argument("--depth", type=int, default=48, help="debug only: anything but 48 is not the named model")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baseline, one CFG step at the other workloads, "
+                         "the reference's 480p operating point, VAE decode and the LoRA-TTA legs (about four minutes more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the untimed extras (VAE decode and LoRA-TTA inner-loop step times for the per-video wall clock)")
+                    help="with --full: skip the untimed extras (VAE decode and LoRA-TTA inner-loop step times for the per-video wall clock)")
     ap.add_argument("--full-tta-leg", action="store_true",
-                    help="also time full-model TTA at the 480p operating point (SURVEY §2.1 #9 marks it out of scope: opt-in since round 3)")
-    ap.add_argument("--no-k3p", action="store_true", help="skip the one secondary CFG step at the literal 49x90x160 size (~45 s)")
+                    help="with --full: also time full-model TTA at the 480p operating point (SURVEY §2.1 #9 marks it out of scope: "
+                         "opt-in since round 3)")
+    ap.add_argument("--no-k3p", action="store_true",
+                    help="with --full: skip the one secondary CFG step at the literal 49x90x160 size (~45 s)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="with --gpus N > 1 and no torch.distributed environment: print the launcher command and exit")
     ap.add_argument("--parallelism", default="dp", choices=["dp", "sp"],
                     help="dp: one independent video per GPU (weak scaling, default); sp: ONE video, latent frames sharded "
                          "over the GPUs with an RCCL K/V all-gather per attention layer (strong scaling, config K5)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.full_tta_leg and not args.full:
+        ap.error("--full-tta-leg adds a leg to a --full run: give --full as well")
+    return args
+
+
+def untimed_legs(args, rank: int, world: int) -> dict:
+    """Which measurements beside the warm-up and timed steps this run makes.  All of them sit behind --full, so a plain run
+    makes none, whatever else is on the command line; under --full each has a condition of its own (one GPU, rank 0, the
+    K3 headline, all 48 blocks, its opt-out or opt-in flag)."""
+    one_gpu = args.full and world == 1
+    extras = one_gpu and not args.no_extras
+    return {"cpu_baseline": one_gpu and rank == 0 and not args.no_cpu_baseline,
+            "secondary": extras and args.workload == "K3",
+            "k3p": extras and args.workload == "K3" and not args.no_k3p and args.depth == 48,
+            "extras": extras and args.depth == 48,
+            "full_tta": extras and args.depth == 48 and args.full_tta_leg}
 
 
 def cpu_baseline(num_inference_steps: int) -> dict:
@@ -372,8 +399,9 @@ def main():
         torch.cuda.set_device(0)
     dev = torch.device("cuda", local_rank if world > 1 else 0)
 
+    legs = untimed_legs(args, rank, world)
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if legs["cpu_baseline"]:
         progress("CPU baseline: oracle K1 depth 2, 4 + 4 Euler steps and 2 TTA steps on the host cores ...")
         cpu_base = cpu_baseline(args.num_inference_steps)
         progress(f"CPU baseline done: {cpu_base['k1_step_s_cfg_on_depth2']} s per CFG step at depth 2")
@@ -450,7 +478,7 @@ def main():
 
     # ---- secondary timings (untimed region): one CFG denoise step at BASELINE configs 2, 1 and 5 (K2 49x480p, K1 16x256x256, K5 121x480p) ----
     secondary = {}
-    if world == 1 and not args.no_extras and args.workload == "K3":
+    if legs["secondary"]:
         for name in ("K2", "K1", "K5"):     # BASELINE.json configs 2, 1 and 5 (the 121-frame clip, on one GPU)
             T2, h2, w2, _ = WORKLOADS[name]
             lat2 = torch.randn((1, 16, T2, h2, w2), generator=g, device=dev, dtype=torch.float32)
@@ -463,9 +491,9 @@ def main():
             secondary[f"{name}_cfg_step_s"] = round((time.perf_counter() - t1) / 2, 4)
             progress(f"secondary {name}: {secondary[f'{name}_cfg_step_s']} s per CFG step")
             assert torch.isfinite(x2).all().item()
-        if not args.no_k3p and args.depth == 48:
+        if legs["k3p"]:
             # north_star's literal shape, once and for the record (the headline stays K3): ONE CFG step at 176 400 tokens, no
-            # separate warm-up (kernels and weight copies are warm; a second ~45 s step would push the default run past its budget)
+            # separate warm-up (kernels and weight copies are warm; a second ~45 s step would push the --full run past its budget)
             T2, h2, w2, _ = WORKLOADS["K3p"]
             lat2 = torch.randn((1, 16, T2, h2, w2), generator=g, device=dev, dtype=torch.float32)
             progress("secondary K3p: one CFG step at 176 400 tokens (~45 s) ...")
@@ -482,14 +510,14 @@ def main():
 
     # ---- extras (outside the timed region, rank 0 of a 1-GPU run): the other two legs of "wall-clock per TTA video" ----
     extras = dict(secondary)
-    if world == 1 and not args.no_extras and args.depth == 48:
+    if legs["extras"]:
         import contextlib
         with contextlib.redirect_stdout(sys.stderr):   # stdout carries exactly one JSON line
             progress("extras 1/2: the reference's 480p operating point (generation + LoRA TTA)")
             ref_point = measure_reference_point(dit, dev, pe, pm, ne, nm)
             progress("extras 2/2: VAE decode, then 1 + 20 LoRA-TTA inner steps at the bench resolution, then 20 more with early stopping")
             extras.update(measure_extras(dit, dev, T, h, w, pe, pm))
-            if args.full_tta_leg:
+            if legs["full_tta"]:
                 progress("extras (opt-in): full-model TTA at the 480p operating point")
                 ref_point.update(measure_full_tta_reference_point(dit, dev, pe, pm))
             progress("extras done")
