@@ -3,7 +3,8 @@
 schemas as the reference's `baseline_experiment/scripts/run_baseline.py` (flags :235-262, summary :515-550: the
 "metrics" + "timing.per_video_inference_s" form `export_all_results.py:132-166` recognises as the baseline variant).
 Inputs are those of the TTA runners (`latents/*.pt` or `synthetic:N`); pixel metrics (PSNR / SSIM / LPIPS) are the
-on-device-eval row that comes after the path and are reported as null.  Under `torch.distributed.run`
+on-device evaluation of the decoded frames (LPIPS only when LCV_LPIPS_WEIGHTS names its weights,
+null otherwise).  Under `torch.distributed.run`
 the videos are sharded over ranks (the reference launches it with torchrun too, :76-79 — there for context parallelism)."""
 import argparse
 import csv

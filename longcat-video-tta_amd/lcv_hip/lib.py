@@ -64,6 +64,15 @@ _SIGNATURES = {
     "lcv_frame_ssim": [P, P, I, P, I64, I64, I64, I64, P, I, F32, I, F32, F32, P],
 }
 
+# include/lcv_hip_lpips.h (a header of its own: the on-device LPIPS entry points); same convention, every function returns int
+_SIGNATURES_LPIPS = {
+    "lcv_lpips_pack_weight": [P, P, I64, I64, I64, I64, I64, P],
+    "lcv_lpips_conv_relu": [P, P, I, I, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, P],
+    "lcv_lpips_maxpool": [P, P, I64, I64, I64, I64, P],
+    "lcv_lpips_tap_distance": [P, P, P, P, I, I64, I64, I64, P],
+}
+LCV_LPIPS_TAP_BLOCKS = 64
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -113,7 +122,9 @@ def load():
     lib.lcv_tn_skinny_ws_bytes.argtypes = [I64, I64, I64]
     lib.lcv_attn_bwd_ws_floats.restype = c_int64     # likewise
     lib.lcv_attn_bwd_ws_floats.argtypes = [I64, I64, I64, I64]
-    for name, args in _SIGNATURES.items():
+    lib.lcv_lpips_ws_bytes.restype = c_int64         # likewise
+    lib.lcv_lpips_ws_bytes.argtypes = [I64, I64, I64]
+    for name, args in list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

@@ -622,6 +622,165 @@ def frame_metrics(gen: torch.Tensor, gt: torch.Tensor, data_range: float = 1.0, 
     return mse, out
 
 
+# ------------------------------------------------------------ LPIPS (alex) ---
+# AlexNet `features` as LPIPS taps it (spec/lpips.md §L): (Cin, Cout, kernel, stride, pad, 3/2 max-pool in front)
+LPIPS_ALEX_LAYERS = ((3, 64, 11, 4, 2, False), (64, 192, 5, 1, 2, True), (192, 384, 3, 1, 1, True),
+                     (384, 256, 3, 1, 1, False), (256, 256, 3, 1, 1, False))
+LPIPS_SHIFT = (-0.030, -0.088, -0.188)
+LPIPS_SCALE = (0.458, 0.448, 0.450)
+LPIPS_MIN_SIDE = 31        # below it the second pool has no window
+LPIPS_CHUNK = 8            # frame pairs per pass: bounds the workspace (0.30 GB at 480x832, 0.71 GB at 720x1280)
+_LPIPS_WS = {}
+
+
+class LpipsWeights:
+    """Device-resident weights of LPIPS-alex in the layout the kernels read: `conv[i] = (packed [Cout, Kpad], bias
+    [Cout])`, `lin[i] = [C_i]`, and the scaling layer's six constants (host floats)."""
+
+    def __init__(self, conv, lin, shift=LPIPS_SHIFT, scale=LPIPS_SCALE):
+        import numpy as np
+        self.conv, self.lin = list(conv), list(lin)
+        self.shift_scale = np.asarray(tuple(shift) + tuple(scale), dtype=np.float32)
+        if len(self.conv) != 5 or len(self.lin) != 5 or self.shift_scale.shape != (6,):
+            raise _lib.LcvError("LpipsWeights: five convolutions, five lin vectors, three shifts and three scales expected")
+        for i, ((cin, cout, k, _, _, _), (w, b), l) in enumerate(zip(LPIPS_ALEX_LAYERS, self.conv, self.lin)):
+            kpad = (k * k * cin + 31) // 32 * 32
+            for t, shape, what in ((w, (cout, kpad), "packed weight"), (b, (cout,), "bias"), (l, (cout,), "lin weight")):
+                _req(t, F32, f"LpipsWeights layer {i} {what}")
+                if tuple(t.shape) != shape or not t.is_contiguous():
+                    raise _lib.LcvError(f"LpipsWeights layer {i} {what}: contiguous {shape} expected, got {tuple(t.shape)}")
+
+
+def lpips_pack_weight(w: torch.Tensor) -> torch.Tensor:
+    """fp32 [Cout, Cin, KH, KW] -> fp32 [Cout, Kpad], k = (kh, kw, ci) with ci fastest, zero-padded to a multiple of 32."""
+    _req(w, F32, "lpips_pack_weight.w")
+    if w.dim() != 4:
+        raise _lib.LcvError(f"lpips_pack_weight: [Cout,Cin,KH,KW] expected, got {tuple(w.shape)}")
+    cout, cin, kh, kw = w.shape
+    kpad = (kh * kw * cin + 31) // 32 * 32
+    out = torch.empty((cout, kpad), dtype=F32, device=w.device)
+    call("lcv_lpips_pack_weight", _ptr(w.contiguous()), _ptr(out), cout, cin, kh, kw, kpad, _stream())
+    return out
+
+
+def lpips_conv_relu(x: torch.Tensor, packed: torch.Tensor, bias: torch.Tensor, k: int, stride: int, pad: int,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """relu(conv2d(x) + bias) of a channels-last fp32 [B,h,w,Cin] map with a packed weight -> [B,ho,wo,Cout]."""
+    _req(x, F32, "lpips_conv_relu.x"); _req(packed, F32, "lpips_conv_relu.packed"); _req(bias, F32, "lpips_conv_relu.bias")
+    B, h, w, cin = x.shape
+    cout, kpad = packed.shape
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    if out is None:
+        out = torch.empty((B, max(ho, 0), max(wo, 0), cout), dtype=F32, device=x.device)
+    call("lcv_lpips_conv_relu", _ptr(x.contiguous()), None, 0, 0, None, _ptr(packed), _ptr(bias), _ptr(out), B, h, w, cin, cout,
+         k, k, stride, pad, kpad, _stream())
+    return out
+
+
+def lpips_conv1_relu(gen: torch.Tensor, gt: torch.Tensor, weights: LpipsWeights, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The first layer on the frames themselves: [N,H,W,3] fp32 generated + fp32 / uint8 ground truth -> tap 1
+    [2N,h1,w1,64]; 2x - 1 and the scaling layer happen in the loader."""
+    N, H, W, _ = gen.shape
+    cin, cout, k, stride, pad, _ = LPIPS_ALEX_LAYERS[0]
+    packed, bias = weights.conv[0]
+    h1, w1 = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if out is None:
+        out = torch.empty((2 * N, h1, w1, cout), dtype=F32, device=gen.device)
+    call("lcv_lpips_conv_relu", _ptr(gen), _ptr(gt), 1, 1 if gt.dtype == torch.uint8 else 0, weights.shift_scale.ctypes.data,
+         _ptr(packed), _ptr(bias), _ptr(out), 2 * N, H, W, cin, cout, k, k, stride, pad, packed.shape[1], _stream())
+    return out
+
+
+def lpips_maxpool(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MaxPool2d(3, 2), floor mode, of a channels-last fp32 [B,h,w,C] map."""
+    _req(x, F32, "lpips_maxpool.x")
+    B, h, w, C = x.shape
+    if out is None:
+        out = torch.empty((B, max((h - 3) // 2 + 1, 0), max((w - 3) // 2 + 1, 0), C), dtype=F32, device=x.device)
+    call("lcv_lpips_maxpool", _ptr(x.contiguous()), _ptr(out), B, h, w, C, _stream())
+    return out
+
+
+def lpips_tap_distance(feats: torch.Tensor, lin: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                       partials: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """feats fp32 [2N,h,w,C] (generated half first), lin fp32 [C] -> out[n] (+)= the tap's mean distance of pair n."""
+    _req(feats, F32, "lpips_tap_distance.feats"); _req(lin, F32, "lpips_tap_distance.lin")
+    B, h, w, C = feats.shape
+    if B % 2 or lin.numel() != C:
+        raise _lib.LcvError(f"lpips_tap_distance: 2N images and {C} lin weights expected, got {B} / {lin.numel()}")
+    N = B // 2
+    if out is None:
+        out = torch.zeros(N, dtype=F32, device=feats.device)
+    if partials is None:
+        partials = torch.empty(N * _lib.LCV_LPIPS_TAP_BLOCKS, dtype=F32, device=feats.device)
+    call("lcv_lpips_tap_distance", _ptr(feats.contiguous()), _ptr(lin.contiguous()), _ptr(partials), _ptr(out), 1 if accumulate else 0,
+         N, h * w, C, _stream())
+    return out
+
+
+def _lpips_workspace(n: int, H: int, W: int, device):
+    """The regions `lcv_lpips_ws_bytes` sizes for n pairs, carved from one flat allocation that is kept per frame size
+    (a sweep scores one resolution; a shorter last pass reuses the front of the same buffer)."""
+    key = (H, W, str(device))
+    total = _lib.load().lcv_lpips_ws_bytes(n, H, W)
+    held = _LPIPS_WS.get(key)
+    if held is None or held.numel() * 4 < total:
+        _LPIPS_WS.clear()
+        held = _LPIPS_WS[key] = torch.empty(total // 4, dtype=F32, device=device)
+    shapes, (h, w) = [], (H, W)
+    for cin, cout, k, stride, pad, pool in LPIPS_ALEX_LAYERS:
+        if pool:
+            h, w = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+            shapes.append((2 * n, h, w, cin))
+        h, w = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+        shapes.append((2 * n, h, w, cout))
+    shapes.append((n * _lib.LCV_LPIPS_TAP_BLOCKS,))
+    views, at = [], 0
+    for s in shapes:
+        count = 1
+        for d in s:
+            count *= d
+        views.append(held[at:at + count].view(s))
+        at += (count + 63) // 64 * 64
+    if at * 4 != total:
+        raise _lib.LcvError(f"lpips workspace: carved {at * 4} bytes, the library sizes {total}")
+    return views
+
+
+def lpips_alex(gen: torch.Tensor, gt: torch.Tensor, packed_weights: LpipsWeights) -> torch.Tensor:
+    """LPIPS v0.1 (AlexNet) of each frame pair: gen fp32 [N,H,W,3] in [0,1], gt fp32 or uint8 of the same shape ->
+    fp32 [N] on the device.  Five MFMA convolutions, two pools and five tap distances per pass of up to LPIPS_CHUNK
+    pairs; deterministic (no atomics), and a pair's value does not depend on which other pairs share the call."""
+    _req(gen, F32, "lpips_alex.gen")
+    if gt.dtype not in (torch.uint8, F32) or not gt.is_cuda:
+        raise _lib.LcvError("lpips_alex.gt: fp32 or uint8 GPU tensor expected")
+    if gen.shape != gt.shape or gen.dim() != 4 or gen.shape[-1] != 3:
+        raise _lib.LcvError(f"lpips_alex: [N,H,W,3] frames of equal shape expected, got {tuple(gen.shape)} / {tuple(gt.shape)}")
+    if not isinstance(packed_weights, LpipsWeights):
+        raise _lib.LcvError("lpips_alex: packed_weights must be an ops.LpipsWeights (tta.lpips.LpipsAlex builds one)")
+    N, H, W, _ = gen.shape
+    if H < LPIPS_MIN_SIDE or W < LPIPS_MIN_SIDE:
+        raise _lib.LcvError(f"lpips_alex: a {H}x{W} frame is smaller than {LPIPS_MIN_SIDE}x{LPIPS_MIN_SIDE} "
+                            "(the second max-pool would have no window)")
+    gen, gt = gen.contiguous(), gt.contiguous()
+    out = torch.empty(N, dtype=F32, device=gen.device)
+    for lo in range(0, N, LPIPS_CHUNK):
+        n = min(LPIPS_CHUNK, N - lo)
+        t1, p1, t2, p2, t3, t4, t5, partials = _lpips_workspace(n, H, W, gen.device)
+        o = out[lo:lo + n]
+        conv = packed_weights.conv
+        lpips_conv1_relu(gen[lo:lo + n], gt[lo:lo + n], packed_weights, out=t1)
+        lpips_tap_distance(t1, packed_weights.lin[0], out=o, accumulate=False, partials=partials)
+        x = t1
+        for i, (tap, pooled) in enumerate(((t2, p1), (t3, p2), (t4, None), (t5, None)), start=1):
+            _, _, k, stride, pad, _ = LPIPS_ALEX_LAYERS[i]
+            if pooled is not None:
+                x = lpips_maxpool(x, out=pooled)
+            x = lpips_conv_relu(x, conv[i][0], conv[i][1], k, stride, pad, out=tap)
+            lpips_tap_distance(x, packed_weights.lin[i], out=o, accumulate=True, partials=partials)
+    return out
+
+
 # ------------------------------------------------------- UMT5 text encoder ---
 def gather_rows(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     _req(table, BF16, "gather_rows.table")

@@ -3,11 +3,13 @@
 Host-side mirror of the reference's `evaluate_generation_metrics`, `aggregate_quality_metrics`,
 `OnlineFrechetAccumulator` and `finalize_online_eval` (delta_experiment/scripts/common.py:663-757, 2234-2431, 2453-2530).
 The reference copies every generated clip to the host and loops over frames in numpy / torch-CPU; here the frames stay
-where the VAE decoder wrote them and PSNR / SSIM are two kernels of liblcv_hip.so (`lcv_frame_sqerr`, `lcv_frame_ssim`).
+where the VAE decoder wrote them and PSNR / SSIM are two kernels of liblcv_hip.so (`lcv_frame_sqerr`, `lcv_frame_ssim`);
+LPIPS (AlexNet v0.1) is the library's convolution / tap-distance kernels behind `tta.lpips.LpipsAlex`, given weights.
 
 Kept from the reference: frame slicing `[num_cond : num_cond + num_gen]`, `n_compare = min(gen, gt)`, the `mse < 1e-10 ->
-50 dB` rule, per-frame-then-mean averaging, NaN for a metric whose model is unavailable (LPIPS needs AlexNet weights and
-FVD the I3D TorchScript file: neither exists offline), the result keys and the Frechet accumulator's float64 sums.
+50 dB` rule, per-frame-then-mean averaging, NaN for a metric whose model is unavailable (LPIPS without an `lpips_model`,
+as the reference's ImportError branch; FVD without the I3D TorchScript file), the result keys and the Frechet
+accumulator's float64 sums.
 Not mirrored: decoding the source video with PyAV and the LANCZOS resize of the ground truth (host image IO, outside the
 path): the caller hands ground-truth frames already at the output resolution.
 """
@@ -25,11 +27,13 @@ COV_EPS = 1e-6                   # common.py:2147
 
 
 def evaluate_generation_metrics(gen_output: torch.Tensor, gt_frames: torch.Tensor, num_cond_frames: int,
-                                num_gen_frames: int, flavour: str = "tta") -> Dict[str, float]:
+                                num_gen_frames: int, flavour: str = "tta", lpips_model=None) -> Dict[str, float]:
     """gen_output: fp32 GPU [N,H,W,3] in [0,1], the full pipeline output (conditioning frames first);
     gt_frames: GPU uint8 or fp32 [>=n,H,W,3], the ground truth of the GENERATED frames at the output resolution.
     Returns {"psnr", "ssim", "lpips"}.  flavour "tta": common.py:663-757 (50 dB cap, torchmetrics' Gaussian SSIM);
-    "baseline": run_baseline.py:124-136, 436-441 (60 dB cap, skimage's 7x7 uniform SSIM)."""
+    "baseline": run_baseline.py:124-136, 436-441 (60 dB cap, skimage's 7x7 uniform SSIM).
+    lpips_model: a `tta.lpips.LpipsAlex`; "lpips" is then the mean of its per-frame values over the same frames
+    (common.py:740-757, run_baseline.py:148-165 - one network for both flavours), NaN without one."""
     if flavour not in ("tta", "baseline"):
         raise ValueError(f"unknown metric flavour {flavour!r}")
     gen = gen_output[num_cond_frames:num_cond_frames + num_gen_frames]
@@ -39,7 +43,8 @@ def evaluate_generation_metrics(gen_output: torch.Tensor, gt_frames: torch.Tenso
     mse, ssim = ops.frame_metrics(gen[:n].float(), gt_frames[:n], ssim="gaussian11" if flavour == "tta" else "uniform7")
     cap = 50.0 if flavour == "tta" else 60.0
     psnr = [cap if m < 1e-10 else float(10.0 * math.log10(1.0 / m)) for m in mse.tolist()]
-    return {"psnr": float(np.mean(psnr)), "ssim": float(np.mean(ssim.tolist())), "lpips": float("nan")}
+    lpips = float("nan") if lpips_model is None else float(np.mean(lpips_model(gen[:n].float(), gt_frames[:n]).double().tolist()))
+    return {"psnr": float(np.mean(psnr)), "ssim": float(np.mean(ssim.tolist())), "lpips": lpips}
 
 
 def aggregate_quality_metrics(summary: dict) -> None:

@@ -302,13 +302,16 @@ def ground_truth_frames(blob, entry, shape, device):
 def score_generation(frames: torch.Tensor, blob, entry, args, num_frames=None, flavour: str = "tta") -> Dict:
     """PSNR / SSIM / LPIPS of the generated frames against the ground truth, on the device (common.py:1233-1243)."""
     from tta.eval_metrics import evaluate_generation_metrics
+    from tta.lpips import model_from_env
     num_gen = (num_frames if num_frames is not None else args.num_frames) - args.num_cond_frames
     n_have = max(0, min(num_gen, frames.shape[0] - args.num_cond_frames))
     gt = ground_truth_frames(blob, entry, (n_have,) + tuple(frames.shape[1:]), frames.device)
     if gt is None or n_have == 0:
         return {"psnr": None, "ssim": None, "lpips": None}
-    m = evaluate_generation_metrics(frames, gt, args.num_cond_frames, num_gen, flavour=flavour)
-    return {k: (None if v != v else v) for k, v in m.items()}     # NaN (no LPIPS network offline) -> null in the JSON
+    # the LPIPS network is opt-in: LCV_LPIPS_WEIGHTS names its weights, resolved once per process (tta/lpips.py)
+    m = evaluate_generation_metrics(frames, gt, args.num_cond_frames, num_gen, flavour=flavour,
+                                    lpips_model=model_from_env(frames.device))
+    return {k: (None if v != v else v) for k, v in m.items()}     # NaN (no LPIPS weights given) -> null in the JSON
 
 
 def clip_gate_summary(args) -> Dict:

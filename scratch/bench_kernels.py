@@ -96,6 +96,41 @@ if which in ("eval",):
             print(f"eval {N}x{H}x{W} win {win}: sqerr {m1*1e3:.1f} us {by/m1/1e6:.0f} GB/s | ssim {m2*1e3:.1f} us {by/m2/1e6:.0f} GB/s", flush=True)
         full = lambda: ops.frame_metrics(gen, gt)
         print(f"  frame_metrics end to end (2 launches + partial sums + D2H): {timeit(full, n=10, warm=2)*1e3:.1f} us", flush=True)
+if which in ("lpips",):
+    # on-device LPIPS-alex (csrc/lpips.hip): per-layer time and rate against the 157 TF/s f32-MFMA peak, per tap-distance /
+    # pool launch against HBM, and ops.lpips_alex end to end next to frame_metrics for the same frames
+    from tta.lpips import LpipsAlex
+    model = LpipsAlex.synthetic(0); wts = model.weights
+    for N in (14, 79):
+        H, W = 480, 832
+        gen = torch.rand(N, H, W, 3, device=dev); gt = torch.randint(0, 256, (N, H, W, 3), device=dev, dtype=torch.uint8)
+        n = min(N, ops.LPIPS_CHUNK)            # what one pass of lpips_alex launches
+        g1, t1 = gen[:n].contiguous(), gt[:n].contiguous()
+        x = ops.lpips_conv1_relu(g1, t1, wts)
+        ms = timeit(lambda: ops.lpips_conv1_relu(g1, t1, wts, out=x), n=10, warm=2)
+        fl = 2 * x.numel() * 363
+        print(f"lpips {N} pairs (pass of {n}) conv1 M={x.numel()//64} N=64 K=363: {ms*1e3:.0f} us {fl/ms/1e9:.1f} TF/s ({fl/ms/1e9/157.3:.2f} of f32 MFMA peak)", flush=True)
+        for i in range(1, 5):
+            cin, cout, k, stride, pad, pool = ops.LPIPS_ALEX_LAYERS[i]
+            d = ops.lpips_tap_distance(x, wts.lin[i - 1])
+            ms = timeit(lambda: ops.lpips_tap_distance(x, wts.lin[i - 1], out=d), n=10, warm=2)
+            print(f"   tap {i} distance {tuple(x.shape)}: {ms*1e3:.0f} us {x.numel()*4/ms/1e6:.0f} GB/s", flush=True)
+            if pool:
+                y = ops.lpips_maxpool(x)
+                ms = timeit(lambda: ops.lpips_maxpool(x, out=y), n=10, warm=2)
+                print(f"   maxpool {tuple(x.shape)} -> {tuple(y.shape)}: {ms*1e3:.0f} us {(x.numel()+y.numel())*4/ms/1e6:.0f} GB/s", flush=True)
+                x = y
+            o = ops.lpips_conv_relu(x, wts.conv[i][0], wts.conv[i][1], k, stride, pad)
+            ms = timeit(lambda: ops.lpips_conv_relu(x, wts.conv[i][0], wts.conv[i][1], k, stride, pad, out=o), n=10, warm=2)
+            fl = 2 * o.numel() * k * k * cin
+            print(f"   conv{i+1} M={o.numel()//cout} N={cout} K={k*k*cin}: {ms*1e3:.0f} us {fl/ms/1e9:.1f} TF/s ({fl/ms/1e9/157.3:.2f} of f32 MFMA peak)", flush=True)
+            x = o
+        ms = timeit(lambda: ops.lpips_tap_distance(x, wts.lin[4], out=d), n=10, warm=2)
+        print(f"   tap 5 distance {tuple(x.shape)}: {ms*1e3:.0f} us {x.numel()*4/ms/1e6:.0f} GB/s", flush=True)
+        del x, o, y
+        e2e = timeit(lambda: ops.lpips_alex(gen, gt, wts), n=5, warm=2)
+        fm = timeit(lambda: ops.frame_metrics(gen, gt), n=5, warm=2)
+        print(f"lpips_alex {N}x{H}x{W} end to end: {e2e:.2f} ms ({e2e/N:.3f} ms per pair) | frame_metrics (PSNR + SSIM, with D2H): {fm:.2f} ms", flush=True)
 if which in ("gemm_tail",):
     # the reference's 480p operating shapes (generation: M = 2 x 6 240 rows; TTA: M = 6 240): thin last rounds on 256 CUs,
     # with and without the split-K tail, interleaved in one process
