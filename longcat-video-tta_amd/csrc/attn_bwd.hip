@@ -15,10 +15,7 @@
 // accumulation across workgroups (float atomics run at ~1.3 TB/s chip-wide and would cap a 128-key-block
 // design near 0.4 PFLOP/s — MI355X_MICROARCH.md, Global float atomics).
 // Algorithmic work: 10*Nq*Nk*128 flop per (b, h); bytes (8*N*128*2 + 2*N*4) per (b, h).
-#include "lcv_common.h"
-
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
-#define AS3 __attribute__((address_space(3)))
+#include "attn_common.h"
 
 struct AttnBwdParams {
   const bf16_t* q;
@@ -30,9 +27,7 @@ struct AttnBwdParams {
   bf16_t* dq;
   bf16_t* dk;
   bf16_t* dv;
-  int64_t Nq, Nk;
-  int H;
-  int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+  AttnDims d;
   int64_t dq_sb, dq_sn, dq_sh, dk_sb, dk_sn, dk_sh, dv_sb, dv_sn, dv_sh;
   float scale, scale_log2e;
   int accumulate_kv;
@@ -43,10 +38,6 @@ struct AttnBwdParams {
   int qsplit;
   float* kv_part;
 };
-
-__device__ __forceinline__ int tile_off_b(int row, int ch) {
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
 
 // ---------------------------------------------------------------------------
 // delta[b,h,q] = sum_d dO[b,q,h,d] * O[b,q,h,d]   (16 lanes per (q,h) row)
@@ -115,9 +106,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdParams p
   bf16x8 kf[8], vf[8];
   {
     int64_t krow = key0 + r;
-    if (krow > p.Nk - 1) krow = p.Nk - 1;
-    const bf16_t* kp = p.k + b * p.k_sb + krow * p.k_sn + (int64_t)head * p.k_sh + 8 * h;
-    const bf16_t* vp = p.v + b * p.v_sb + krow * p.v_sn + (int64_t)head * p.v_sh + 8 * h;
+    if (krow > p.d.Nk - 1) krow = p.d.Nk - 1;
+    const bf16_t* kp = p.k + b * p.d.k_sb + krow * p.d.k_sn + (int64_t)head * p.d.k_sh + 8 * h;
+    const bf16_t* vp = p.v + b * p.d.v_sb + krow * p.d.v_sn + (int64_t)head * p.d.v_sh + 8 * h;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
       kf[ks] = *reinterpret_cast<const bf16x8*>(kp + 16 * ks);
@@ -126,16 +117,16 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdParams p
   }
 
   // ---- staging: 512 chunks per tile, 256 threads -> 2 chunks of Q and 2 of dO each ----
-  const bf16_t* qbase = p.q + b * p.q_sb + (int64_t)head * p.q_sh;
-  const bf16_t* dobase = p.d_o + b * p.o_sb + (int64_t)head * p.o_sh;
-  const float* lsebase = p.lse + (b * p.H + head) * p.Nq;
-  const float* delbase = p.delta + (b * p.H + head) * p.Nq;
+  const bf16_t* qbase = p.q + b * p.d.q_sb + (int64_t)head * p.d.q_sh;
+  const bf16_t* dobase = p.d_o + b * p.d.o_sb + (int64_t)head * p.d.o_sh;
+  const float* lsebase = p.lse + (b * p.d.H + head) * p.d.Nq;
+  const float* delbase = p.delta + (b * p.d.H + head) * p.d.Nq;
   int st_off[2], st_row[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int c = tid + i * 256;
     st_row[i] = c >> 4;
-    st_off[i] = tile_off_b(c >> 4, c & 15);
+    st_off[i] = attn_tile_off(c >> 4, c & 15);
   }
   const int st_col = (tid & 15) * 8;
   u32x4 qreg[2], dreg[2];
@@ -144,15 +135,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdParams p
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       int64_t row = q0 + st_row[i];
-      if (row > p.Nq - 1) row = p.Nq - 1;
-      qreg[i] = *reinterpret_cast<const u32x4*>(qbase + row * p.q_sn + st_col);
-      dreg[i] = *reinterpret_cast<const u32x4*>(dobase + row * p.o_sn + st_col);
+      if (row > p.d.Nq - 1) row = p.d.Nq - 1;
+      qreg[i] = *reinterpret_cast<const u32x4*>(qbase + row * p.d.q_sn + st_col);
+      dreg[i] = *reinterpret_cast<const u32x4*>(dobase + row * p.d.o_sn + st_col);
     }
     if (tid < QT) {
       const int64_t row = q0 + tid;
       // rows past Nq get lse = +inf so that their P (and dS) are exactly zero
-      lreg = (row < p.Nq) ? lsebase[row] * 1.4426950408889634f : INFINITY;
-      dlreg = (row < p.Nq) ? delbase[row] : 0.f;
+      lreg = (row < p.d.Nq) ? lsebase[row] * 1.4426950408889634f : INFINITY;
+      dlreg = (row < p.d.Nq) ? delbase[row] : 0.f;
     }
   };
   auto store_tile = [&](int buf) {
@@ -169,7 +160,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdParams p
   };
 
   // ---- LDS read addresses ----
-  const int rf = ((r & 3) << 2) | ((r >> 2) & 3);
+  const int rf = attn_swz(r);
   const int row_off = 256 * r;
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
   int t_base[2], t_low[2];
@@ -185,7 +176,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdParams p
 #pragma unroll
     for (int e = 0; e < 16; ++e) { dkacc[d][e] = 0.f; dvacc[d][e] = 0.f; }
 
-  const int nt_all = (int)((p.Nq + QT - 1) / QT);
+  const int nt_all = (int)((p.d.Nq + QT - 1) / QT);
   const int t_begin = (int)((int64_t)nt_all * split / qsplit), nt = (int)((int64_t)nt_all * (split + 1) / qsplit);   // this split's tiles
   load_tile((int64_t)t_begin * QT);
   store_tile(t_begin & 1);
@@ -256,8 +247,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdParams p
   // ---- epilogue: acc[d][e] = dX^T[dim = 32*d + (e&3) + 8*(e>>2) + 4*h][key = lane & 31] ----
   const int64_t krow = key0 + r;
   if (p.qsplit > 1) {   // partial sums of this query range: plain fp32 stores into this split's slice, added up by the finishing kernel
-    if (krow < p.Nk) {
-      float* part = p.kv_part + ((((int64_t)split * gridDim.z + b) * p.H + head) * p.Nk + krow) * 256;
+    if (krow < p.d.Nk) {
+      float* part = p.kv_part + ((((int64_t)split * gridDim.z + b) * p.d.H + head) * p.d.Nk + krow) * 256;
 #pragma unroll
       for (int d = 0; d < 4; ++d)
 #pragma unroll
@@ -272,7 +263,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdParams p
     }
     return;
   }
-  if (krow < p.Nk) {
+  if (krow < p.d.Nk) {
     bf16_t* dkp = p.dk + b * p.dk_sb + krow * p.dk_sn + (int64_t)head * p.dk_sh;
     bf16_t* dvp = p.dv + b * p.dv_sb + krow * p.dv_sn + (int64_t)head * p.dv_sh;
 #pragma unroll
@@ -302,14 +293,14 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnBwdParams p
 // adding to what is there when accumulate_kv
 __global__ __launch_bounds__(256) void attn_bwd_kv_finish_kernel(const AttnBwdParams p, int64_t B) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;   // one thread per 4 columns of one (b, h, key, k|v) row
-  const int64_t total = B * p.H * p.Nk * 2 * 32;
+  const int64_t total = B * p.d.H * p.d.Nk * 2 * 32;
   if (i >= total) return;
   const int c4 = (int)(i & 31);
   const int which = (int)((i >> 5) & 1);
   const int64_t row = i >> 6;                                   // (b * H + h) * Nk + key
-  const int64_t key = row % p.Nk, bh = row / p.Nk;
-  const int head = (int)(bh % p.H);
-  const int64_t b = bh / p.H;
+  const int64_t key = row % p.d.Nk, bh = row / p.d.Nk;
+  const int head = (int)(bh % p.d.H);
+  const int64_t b = bh / p.d.H;
   f32x4 v = *reinterpret_cast<const f32x4*>(p.kv_part + i * 4);
   for (int sp = 1; sp < p.qsplit; ++sp) {
     const f32x4 w = *reinterpret_cast<const f32x4*>(p.kv_part + ((int64_t)sp * total + i) * 4);
@@ -349,23 +340,23 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_bwd_dq_kernel(const AttnBwdP
   const int head = blockIdx.y;
   const int64_t b = blockIdx.z;
   const int64_t q0 = (int64_t)blockIdx.x * QROWS + wave * 32;
-  const bf16_t* kbase = p.k + b * p.k_sb + (int64_t)head * p.k_sh;
-  const bf16_t* vbase = p.v + b * p.v_sb + (int64_t)head * p.v_sh;
+  const bf16_t* kbase = p.k + b * p.d.k_sb + (int64_t)head * p.d.k_sh;
+  const bf16_t* vbase = p.v + b * p.d.v_sb + (int64_t)head * p.d.v_sh;
 
   bf16x8 qf[8], dof[8];
   float lse_q, delta_q;
   {
     int64_t qrow = q0 + r;
-    if (qrow > p.Nq - 1) qrow = p.Nq - 1;
-    const bf16_t* qp = p.q + b * p.q_sb + qrow * p.q_sn + (int64_t)head * p.q_sh + 8 * h;
-    const bf16_t* dp_ = p.d_o + b * p.o_sb + qrow * p.o_sn + (int64_t)head * p.o_sh + 8 * h;
+    if (qrow > p.d.Nq - 1) qrow = p.d.Nq - 1;
+    const bf16_t* qp = p.q + b * p.d.q_sb + qrow * p.d.q_sn + (int64_t)head * p.d.q_sh + 8 * h;
+    const bf16_t* dp_ = p.d_o + b * p.d.o_sb + qrow * p.d.o_sn + (int64_t)head * p.d.o_sh + 8 * h;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
       qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
       dof[ks] = *reinterpret_cast<const bf16x8*>(dp_ + 16 * ks);
     }
-    lse_q = p.lse[(b * p.H + head) * p.Nq + qrow] * 1.4426950408889634f;
-    delta_q = p.delta[(b * p.H + head) * p.Nq + qrow];
+    lse_q = p.lse[(b * p.d.H + head) * p.d.Nq + qrow] * 1.4426950408889634f;
+    delta_q = p.delta[(b * p.d.H + head) * p.d.Nq + qrow];
   }
 
   int st_off[NCH], st_row[NCH];
@@ -373,7 +364,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_bwd_dq_kernel(const AttnBwdP
   for (int i = 0; i < NCH; ++i) {
     const int c = tid + i * NT;
     st_row[i] = c >> 4;
-    st_off[i] = tile_off_b(c >> 4, c & 15);
+    st_off[i] = attn_tile_off(c >> 4, c & 15);
   }
   const int st_col = (tid & 15) * 8;
   u32x4 kreg[NCH], vreg[NCH];
@@ -381,9 +372,9 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_bwd_dq_kernel(const AttnBwdP
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       int64_t row = kv0 + st_row[i];
-      if (row > p.Nk - 1) row = p.Nk - 1;
-      kreg[i] = *reinterpret_cast<const u32x4*>(kbase + row * p.k_sn + st_col);
-      vreg[i] = *reinterpret_cast<const u32x4*>(vbase + row * p.v_sn + st_col);
+      if (row > p.d.Nk - 1) row = p.d.Nk - 1;
+      kreg[i] = *reinterpret_cast<const u32x4*>(kbase + row * p.d.k_sn + st_col);
+      vreg[i] = *reinterpret_cast<const u32x4*>(vbase + row * p.d.v_sn + st_col);
     }
   };
   auto store_tile = [&](int buf) {
@@ -395,7 +386,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_bwd_dq_kernel(const AttnBwdP
     }
   };
 
-  const int kfz = ((r & 3) << 2) | ((r >> 2) & 3);
+  const int kfz = attn_swz(r);
   const int k_row_off = 256 * r;
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
   int t_base[2], t_low[2];
@@ -411,7 +402,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_bwd_dq_kernel(const AttnBwdP
 #pragma unroll
     for (int e = 0; e < 16; ++e) dqacc[d][e] = 0.f;
 
-  const int nt = (int)((p.Nk + 63) / 64);
+  const int nt = (int)((p.d.Nk + 63) / 64);
   load_tile(0);
   store_tile(0);
   __syncthreads();
@@ -437,8 +428,8 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_bwd_dq_kernel(const AttnBwdP
       d0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c0, dof[ks], d0, 0, 0, 0);
       d1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(c1, dof[ks], d1, 0, 0, 0);
     }
-    if (!has_next && (p.Nk & 63)) {
-      const int valid = (int)(p.Nk - (int64_t)t * 64);
+    if (!has_next && (p.d.Nk & 63)) {
+      const int valid = (int)(p.d.Nk - (int64_t)t * 64);
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int key = (e & 3) + 8 * (e >> 2) + 4 * h;
@@ -477,7 +468,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_bwd_dq_kernel(const AttnBwdP
   }
 
   const int64_t qrow = q0 + r;
-  if (qrow < p.Nq) {
+  if (qrow < p.d.Nq) {
     bf16_t* dqp = p.dq + b * p.dq_sb + qrow * p.dq_sn + (int64_t)head * p.dq_sh;
 #pragma unroll
     for (int d = 0; d < 4; ++d)
@@ -490,19 +481,6 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_bwd_dq_kernel(const AttnBwdP
       }
   }
 }
-
-// pass B, second form (attn_bwd_dq2.hip): q pre-scaled into log2 units
-int attn_bwd_dq2_launch(const void* q, const void* k, const void* v, const void* d_o, const float* lse, const float* delta,
-                        void* dq, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t q_sb, int64_t q_sn, int64_t q_sh,
-                        int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb,
-                        int64_t o_sn, int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh, float scale, hipStream_t s);
-
-// pass A, second form (attn_bwd_dkv2.hip): q pre-scaled into log2 units
-int attn_bwd_dkv2_launch(const void* q, const void* k, const void* v, const void* d_o, const float* lse, const float* delta,
-                         void* dk, void* dv, int accumulate_kv, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t q_sb,
-                         int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn,
-                         int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, int64_t dk_sb, int64_t dk_sn, int64_t dk_sh,
-                         int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale, hipStream_t s);
 
 // few key blocks, many query tiles (the text cross-attention): split the query sweep so that the launch fills the chip
 static int attn_bwd_qsplit(int64_t B, int64_t H, int64_t Nq, int64_t Nk) {
@@ -545,12 +523,17 @@ extern "C" int lcv_attn_bwd(const void* q, const void* k, const void* v, const v
                 "attn_bwd: gradient strides must be multiples of 4 elements");
   if (Nq == 0) return LCV_OK;
   hipStream_t s = (hipStream_t)stream;
+  AttnArgs a = {};
+  a.q = q; a.k = k; a.v = v; a.o = const_cast<void*>(o); a.d_o = d_o; a.lse = const_cast<float*>(lse); a.delta_ws = delta_ws;
+  a.dq = dq; a.dk = dk; a.dv = dv; a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = scale; a.accumulate_kv = accumulate_kv;
+  a.q_sb = q_sb; a.q_sn = q_sn; a.q_sh = q_sh; a.k_sb = k_sb; a.k_sn = k_sn; a.k_sh = k_sh;
+  a.v_sb = v_sb; a.v_sn = v_sn; a.v_sh = v_sh; a.o_sb = o_sb; a.o_sn = o_sn; a.o_sh = o_sh;
+  a.dq_sb = dq_sb; a.dq_sn = dq_sn; a.dq_sh = dq_sh; a.dk_sb = dk_sb; a.dk_sn = dk_sn; a.dk_sh = dk_sh;
+  a.dv_sb = dv_sb; a.dv_sn = dv_sn; a.dv_sh = dv_sh;
   AttnBwdParams p;
   p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.d_o = (const bf16_t*)d_o;
   p.lse = lse; p.delta = delta_ws; p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
-  p.Nq = Nq; p.Nk = Nk; p.H = (int)H;
-  p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
-  p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
+  p.d = attn_dims(a);
   p.dq_sb = dq_sb; p.dq_sn = dq_sn; p.dq_sh = dq_sh; p.dk_sb = dk_sb; p.dk_sn = dk_sn; p.dk_sh = dk_sh;
   p.dv_sb = dv_sb; p.dv_sn = dv_sn; p.dv_sh = dv_sh;
   p.scale = scale; p.scale_log2e = scale * 1.4426950408889634f; p.accumulate_kv = accumulate_kv;
@@ -568,8 +551,7 @@ extern "C" int lcv_attn_bwd(const void* q, const void* k, const void* v, const v
   // (a third form of pass A - one wave per SIMD, software-pipelined, bit-identical, 2 % slower - was built in round 3 and is kept
   // under scratch/tried/attn_bwd_dkv3_r3_one_wave_per_simd.hip.txt with its numbers in profiles/r03_attn_bwd_lab.md)
   if (unit && (bvar & 2)) {
-    const int rc = attn_bwd_dkv2_launch(q, k, v, d_o, lse, delta_ws + B * H * Nq /* the padded -lse2 / -delta rows */, dk, dv, accumulate_kv, B, H, Nq, Nk, q_sb, q_sn, q_sh, k_sb, k_sn,
-                                        k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh, dk_sb, dk_sn, dk_sh, dv_sb, dv_sn, dv_sh, scale, s);
+    const int rc = attn_bwd_dkv2_launch(a, s);
     if (rc != LCV_OK) return rc;
   } else {
     const size_t lds = 2 * (2 * 32 * 256 + 2 * 32 * 4);
@@ -588,18 +570,12 @@ extern "C" int lcv_attn_bwd(const void* q, const void* k, const void* v, const v
     }
   }
   if (unit && (bvar & 1))
-    return attn_bwd_dq2_launch(q, k, v, d_o, lse, delta_ws, dq, B, H, Nq, Nk, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh,
-                               o_sb, o_sn, o_sh, dq_sb, dq_sn, dq_sh, scale, s);
+    return attn_bwd_dq2_launch(a, s);
   {
     constexpr int NW = 8;
     const size_t lds = 2 * 2 * 64 * 256;
     auto kern = attn_bwd_dq_kernel<NW>;
-    // (function-local static: initialised once, thread-safe)
-    static const bool attr_ok = !(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-    if (!attr_ok) {
-        lcv_set_error("attn_bwd: cannot raise dynamic LDS");
-        return LCV_EDEVICE;
-    }
+    ATTN_RAISE_LDS_ONCE("attn_bwd", attn_raise_lds((const void*)kern, lds));
     hipLaunchKernelGGL(kern, dim3((unsigned)((Nq + NW * 32 - 1) / (NW * 32)), (unsigned)H, (unsigned)B),
                        dim3(NW * 64), lds, s, p);
     LCV_LAUNCH_CHECK("attn_bwd_dq");

@@ -10,13 +10,8 @@
 //   * row constants as the initial accumulator: S starts at -lse (log2 units) and dP at -delta, read from LDS straight into the
 //     accumulators, so P = exp2(S) and dS' = P * dP are 2 vector instructions per score; the softmax scale is applied to dK once
 //     in the epilogue.
-#include "lcv_common.h"
+#include "attn_common.h"
 #include <stdlib.h>
-
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
-typedef __attribute__((address_space(1))) void gbl_void_k;
-typedef __attribute__((address_space(3))) void lds_void_k;
-#define AS3 __attribute__((address_space(3)))
 
 struct AttnBwdDkv2Params {
   const bf16_t* q;
@@ -27,17 +22,13 @@ struct AttnBwdDkv2Params {
   const float* consts;   // per (b, h): nlse2[Nqp] | ndelta[Nqp] (attn_bwd_delta_kernel), Nqp = roundup(Nq, 32)
   bf16_t* dk;
   bf16_t* dv;
-  int64_t Nq, Nk;
-  int H;
-  int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+  AttnDims d;
   int64_t dk_sb, dk_sn, dk_sh, dv_sb, dv_sn, dv_sh;
   float scale;
   int accumulate_kv;
-  int gx, xcd_remap;   // blocks per (batch, head); head-per-XCD block order (speed only: see attn_fwd.hip)
+  int gx, xcd_remap;   // blocks per (batch, head); head-per-XCD block order (ATTN_BLOCK_DECODE)
   int stagger;         // s_sleep argument (x 64 cycles) for every second resident workgroup; 0 = off
 };
-
-__device__ __forceinline__ int swz_k2(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 
 // PIPE: the fragment reads of k-step ks+1 (and of transposed-read step j+1) are issued BEFORE the MFMAs of step ks (j), pinned
 // with scheduling fences.  hipcc's own order is {3 reads; wait; 2 MFMAs} x 8 - every MFMA pair behind a full LDS latency,
@@ -60,29 +51,18 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  // Block order (speed only): with the remap each XCD walks the key blocks of ITS OWN (batch, head) pairs, so that head's
-  // Q / dO rows (re-streamed by every key block) stay in one 4 MiB L2 instead of being fetched into all eight
   int kb, head;
   int64_t b;
-  if (p.xcd_remap) {
-    const int id = blockIdx.x;
-    const int xcd = id & 7, j = id >> 3;
-    const int pair = (j / p.gx) * 8 + xcd;
-    kb = j - (j / p.gx) * p.gx;
-    head = pair % p.H;
-    b = pair / p.H;
-  } else {
-    kb = blockIdx.x; head = blockIdx.y; b = blockIdx.z;
-  }
+  ATTN_BLOCK_DECODE(p, kb, head, b);
   const int64_t key0 = (int64_t)kb * (NW * 32);
-  const bf16_t* kbase = p.k + b * p.k_sb + (int64_t)head * p.k_sh;
+  const bf16_t* kbase = p.k + b * p.d.k_sb + (int64_t)head * p.d.k_sh;
 
   // ---- V rows of this lane's key as B operands (registers); K rows of the whole block -> LDS by DMA ----
   bf16x8 vf[8];
   {
     int64_t krow = key0 + wave * 32 + r;
-    if (krow > p.Nk - 1) krow = p.Nk - 1;
-    const bf16_t* vp = p.v + b * p.v_sb + krow * p.v_sn + (int64_t)head * p.v_sh + 8 * h;
+    if (krow > p.d.Nk - 1) krow = p.d.Nk - 1;
+    const bf16_t* vp = p.v + b * p.d.v_sb + krow * p.d.v_sn + (int64_t)head * p.d.v_sh + 8 * h;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) vf[ks] = *reinterpret_cast<const bf16x8*>(vp + 16 * ks);
   }
@@ -90,25 +70,25 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   for (int i = 0; i < 8; ++i) {  // 32 one-KiB pieces (4 rows each), 8 per wave
     const int row = 4 * (8 * wave + i) + (lane >> 4);
     int64_t g = key0 + row;
-    if (g > p.Nk - 1) g = p.Nk - 1;
-    const int col = 8 * ((lane & 15) ^ swz_k2(row));
-    __builtin_amdgcn_global_load_lds((gbl_void_k*)(kbase + g * p.k_sn + col), (lds_void_k*)(lds_k + (8 * wave + i) * 1024), 16, 0, 0);
+    if (g > p.d.Nk - 1) g = p.d.Nk - 1;
+    const int col = 8 * ((lane & 15) ^ attn_swz(row));
+    __builtin_amdgcn_global_load_lds((gbl_void_t*)(kbase + g * p.d.k_sn + col), (lds_void_t*)(lds_k + (8 * wave + i) * 1024), 16, 0, 0);
   }
 
   // ---- Q / dO tile staging by DMA (2 + 2 pieces per wave), -lse / -delta through two registers of the first 32 threads ----
-  const bf16_t* qbase = p.q + b * p.q_sb + (int64_t)head * p.q_sh;
-  const bf16_t* dobase = p.d_o + b * p.o_sb + (int64_t)head * p.o_sh;
-  const int64_t Nqp = (p.Nq + 31) / 32 * 32;
-  const char* cbase_u = lcv_uniform_ptr(p.consts + (b * p.H + head) * 2 * Nqp);
+  const bf16_t* qbase = p.q + b * p.d.q_sb + (int64_t)head * p.d.q_sh;
+  const bf16_t* dobase = p.d_o + b * p.d.o_sb + (int64_t)head * p.d.o_sh;
+  const int64_t Nqp = (p.d.Nq + 31) / 32 * 32;
+  const char* cbase_u = lcv_uniform_ptr(p.consts + (b * p.d.H + head) * 2 * Nqp);
   const unsigned coff = (unsigned)((lane < 32 ? lane : Nqp + lane - 32) * 4);   // one dword piece: 32 x nlse2 | 32 x ndelta
   int dma_row[NP];
   unsigned qoff[NP], dooff[NP];
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     dma_row[i] = 4 * (NP * wave + i) + (lane >> 4);
-    const int col = 8 * ((lane & 15) ^ swz_k2(dma_row[i]));
-    qoff[i] = (unsigned)((dma_row[i] * p.q_sn + col) * 2);
-    dooff[i] = (unsigned)((dma_row[i] * p.o_sn + col) * 2);
+    const int col = 8 * ((lane & 15) ^ attn_swz(dma_row[i]));
+    qoff[i] = (unsigned)((dma_row[i] * p.d.q_sn + col) * 2);
+    dooff[i] = (unsigned)((dma_row[i] * p.d.o_sn + col) * 2);
   }
   const char* qbase_u = lcv_uniform_ptr(qbase);
   const char* dobase_u = lcv_uniform_ptr(dobase);
@@ -117,9 +97,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     // asm-issued (lcv_common.h: a builtin DMA would be waited for before the next fragment read); waited for before the barrier.
     // Source = scalar tile base + a per-lane 32-bit offset that never changes; the ragged last tile clamps rows per lane.
     const unsigned sb = stage_addr0 + (unsigned)(buf * STAGE) + (unsigned)wave * (unsigned)(NP * 1024);
-    const char* qt = qbase_u + q0 * (2 * p.q_sn);
-    const char* dt = dobase_u + q0 * (2 * p.o_sn);
-    if (q0 + QT <= p.Nq) {
+    const char* qt = qbase_u + q0 * (2 * p.d.q_sn);
+    const char* dt = dobase_u + q0 * (2 * p.d.o_sn);
+    if (q0 + QT <= p.d.Nq) {
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
         lcv_lds_dma16_sv(qoff[i], qt, sb + 1024u * i);
@@ -128,10 +108,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     } else {
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
-        int64_t back = q0 + dma_row[i] - (p.Nq - 1);
+        int64_t back = q0 + dma_row[i] - (p.d.Nq - 1);
         if (back < 0) back = 0;
-        lcv_lds_dma16(qt + qoff[i] - back * p.q_sn * 2, sb + 1024u * i);
-        lcv_lds_dma16(dt + dooff[i] - back * p.o_sn * 2, sb + (unsigned)TILE_BYTES + 1024u * i);
+        lcv_lds_dma16(qt + qoff[i] - back * p.d.q_sn * 2, sb + 1024u * i);
+        lcv_lds_dma16(dt + dooff[i] - back * p.d.o_sn * 2, sb + (unsigned)TILE_BYTES + 1024u * i);
       }
     }
     // the tile's row constants, already in accumulator form, by one dword piece (no register round trip, no compiler-visible
@@ -140,7 +120,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   };
 
   // ---- LDS read addresses ----
-  const int rf = swz_k2(r);
+  const int rf = attn_swz(r);
   const int row_off = 256 * r;
   const int krow_off = 256 * (32 * wave + r);
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
@@ -157,7 +137,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
     for (int e = 0; e < 16; ++e) { dkacc[d][e] = 0.f; dvacc[d][e] = 0.f; }
 
-  const int nt = (int)((p.Nq + QT - 1) / QT);
+  const int nt = (int)((p.d.Nq + QT - 1) / QT);
   if (p.stagger) {   // A/B knob: the second workgroup of a CU (dispatch order: id + 256) starts half a tile late
     const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
     if ((lin >> 8) & 1)
@@ -277,7 +257,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
   // ---- epilogue: acc[d][e] = dX^T[dim = 32 d + (e & 3) + 8 (e >> 2) + 4 h][key = lane & 31] ----
   const int64_t krow = key0 + wave * 32 + r;
-  if (krow < p.Nk) {
+  if (krow < p.d.Nk) {
     bf16_t* dkp = p.dk + b * p.dk_sb + krow * p.dk_sn + (int64_t)head * p.dk_sh;
     bf16_t* dvp = p.dv + b * p.dv_sb + krow * p.dv_sn + (int64_t)head * p.dv_sh;
 #pragma unroll
@@ -304,43 +284,33 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 // called by lcv_attn_bwd (attn_bwd.hip) when scale * log2(e) == 1 and LCV_ATTN_BWD_VAR allows it
-int attn_bwd_dkv2_launch(const void* q, const void* k, const void* v, const void* d_o, const float* lse, const float* delta,
-                         void* dk, void* dv, int accumulate_kv, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t q_sb,
-                         int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn,
-                         int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, int64_t dk_sb, int64_t dk_sn, int64_t dk_sh,
-                         int64_t dv_sb, int64_t dv_sn, int64_t dv_sh, float scale, hipStream_t s) {
-  AttnBwdDkv2Params p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.d_o = (const bf16_t*)d_o;
-  p.lse = lse; p.consts = delta; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv; p.Nq = Nq; p.Nk = Nk; p.H = (int)H;
-  p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
-  p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
-  p.dk_sb = dk_sb; p.dk_sn = dk_sn; p.dk_sh = dk_sh; p.dv_sb = dv_sb; p.dv_sn = dv_sn; p.dv_sh = dv_sh;
-  p.scale = scale; p.accumulate_kv = accumulate_kv;
+int attn_bwd_dkv2_launch(const AttnArgs& a, hipStream_t s) {
   const char* we = lcv_knob("LCV_ATTN_BWD_DKV_WAVES");   // A/B knob: 4 = two 4-wave workgroups per CU (128 keys each), 8 = one 8-wave (256 keys)
   const int nw = (we && we[0] == '8') ? 8 : 4;
-  const size_t lds = (size_t)nw * 32 * 256 + 2 * (2 * 32 * 256 + 2 * 32 * 4);
-    const int l4 = 4 * 32 * 256 + 2 * (2 * 32 * 256 + 2 * 32 * 4), l8 = 8 * 32 * 256 + 2 * (2 * 32 * 256 + 2 * 32 * 4);
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, l4) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, l4) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_bwd_dkv2_kernel<true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, l8) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("attn_bwd: cannot raise dynamic LDS");
-      return LCV_EDEVICE;
-  }
-  { const char* se = lcv_knob("LCV_ATTN_BWD_STAGGER"); p.stagger = se ? atoi(se) : 0; if (p.stagger < 0 || p.stagger > 127) p.stagger = 0; }
+  constexpr size_t STAGES = 2 * (2 * 32 * 256 + 2 * 32 * 4);   // [2] x (Q | dO | -lse | -delta)
+  constexpr size_t L4 = 4 * 32 * 256 + STAGES, L8 = 8 * 32 * 256 + STAGES;   // the block's K rows in front
+  const size_t lds = nw == 8 ? L8 : L4;
+  ATTN_RAISE_LDS_ONCE("attn_bwd", attn_raise_lds((const void*)attn_bwd_dkv2_kernel<true, 4>, L4) &&
+                                      attn_raise_lds((const void*)attn_bwd_dkv2_kernel<false, 4>, L4) &&
+                                      attn_raise_lds((const void*)attn_bwd_dkv2_kernel<true, 8>, L8));
   const char* pe = lcv_knob("LCV_ATTN_BWD_PIPE");   // A/B knob: 0 = hipcc's own read / MFMA order
   const bool pipe = !(pe && pe[0] == '0');
-  const unsigned gx = (unsigned)((Nk + nw * 32 - 1) / (nw * 32));
   // A/B knob LCV_ATTN_BWD_XCD=1 enables the head-per-XCD block order.  OFF by default: at the K3-TTA shapes (25 200 keys x 32
   // heads) it measured 27.06 vs 26.51 ms per layer in one process - unlike the forward, these passes are not helped by it
   const char* xe = lcv_knob("LCV_ATTN_BWD_XCD");
-  p.gx = (int)gx;
-  p.xcd_remap = ((B * H) % 8 == 0 && gx >= 8 && xe && xe[0] == '1') ? 1 : 0;
-  const dim3 grid = p.xcd_remap ? dim3(gx * (unsigned)(H * B)) : dim3(gx, (unsigned)H, (unsigned)B);
-  if (nw == 8) hipLaunchKernelGGL((attn_bwd_dkv2_kernel<true, 8>), grid, dim3(512), lds, s, p);
-  else if (pipe) hipLaunchKernelGGL((attn_bwd_dkv2_kernel<true, 4>), grid, dim3(256), lds, s, p);
-  else hipLaunchKernelGGL((attn_bwd_dkv2_kernel<false, 4>), grid, dim3(256), lds, s, p);
+  const AttnGrid g = attn_grid(a.B, a.H, (a.Nk + nw * 32 - 1) / (nw * 32), xe && xe[0] == '1');
+  AttnBwdDkv2Params p;
+  p.q = (const bf16_t*)a.q; p.k = (const bf16_t*)a.k; p.v = (const bf16_t*)a.v; p.d_o = (const bf16_t*)a.d_o;
+  p.lse = a.lse; p.consts = a.delta_ws + a.B * a.H * a.Nq;   // behind the deltas: the padded -lse2 / -delta rows
+  p.dk = (bf16_t*)a.dk; p.dv = (bf16_t*)a.dv;
+  p.d = attn_dims(a);
+  p.dk_sb = a.dk_sb; p.dk_sn = a.dk_sn; p.dk_sh = a.dk_sh; p.dv_sb = a.dv_sb; p.dv_sn = a.dv_sn; p.dv_sh = a.dv_sh;
+  p.scale = a.scale; p.accumulate_kv = a.accumulate_kv;
+  p.gx = g.gx; p.xcd_remap = g.xcd_remap;
+  { const char* se = lcv_knob("LCV_ATTN_BWD_STAGGER"); p.stagger = se ? atoi(se) : 0; if (p.stagger < 0 || p.stagger > 127) p.stagger = 0; }
+  if (nw == 8) hipLaunchKernelGGL((attn_bwd_dkv2_kernel<true, 8>), g.grid, dim3(512), lds, s, p);
+  else if (pipe) hipLaunchKernelGGL((attn_bwd_dkv2_kernel<true, 4>), g.grid, dim3(256), lds, s, p);
+  else hipLaunchKernelGGL((attn_bwd_dkv2_kernel<false, 4>), g.grid, dim3(256), lds, s, p);
   LCV_LAUNCH_CHECK("attn_bwd_dkv2");
   return LCV_OK;
 }

@@ -12,14 +12,9 @@
 //     (SQ_WAIT_ANY 0.41 of the wave cycles -> 0.15 now).  Bit-identical (same products, same order per accumulator); +3 % only:
 //     with the waits gone the chip lowers its clock (1.74 -> 1.65 GHz at MFMA busy 0.64 -> 0.70): profiles/r04_attn_bwd_passB.md.
 // This loop, like the forward, is vector-issue bound: the file is built without SLP vectorisation (lcv_hip/build.py).
-#include "lcv_common.h"
+#include "attn_common.h"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
-typedef __attribute__((address_space(1))) void gbl_void_q;
-typedef __attribute__((address_space(3))) void lds_void_q;
-#define AS3 __attribute__((address_space(3)))
 
 struct AttnBwdDq2Params {
   const bf16_t* q;
@@ -29,11 +24,10 @@ struct AttnBwdDq2Params {
   const float* lse;
   const float* delta;
   bf16_t* dq;
-  int64_t Nq, Nk;
-  int H;
-  int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh, dq_sb, dq_sn, dq_sh;
+  AttnDims d;
+  int64_t dq_sb, dq_sn, dq_sh;
   float scale;
-  int gx, xcd_remap;   // blocks per (batch, head); head-per-XCD block order (speed only: see attn_fwd.hip)
+  int gx, xcd_remap;   // blocks per (batch, head); head-per-XCD block order (ATTN_BLOCK_DECODE)
 };
 
 // <NW, NS>: waves per workgroup (32 query rows each) and K / V stages.  <8, 4>: one workgroup per CU, DMA three tiles ahead.
@@ -54,39 +48,28 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  // Block order (speed only): ids are dealt round-robin over the 8 XCDs, so with the remap each XCD walks the query blocks of
-  // ITS OWN (batch, head) pairs and that head's K / V stream through one 4 MiB L2 instead of eight
   int qb, head;
   int64_t b;
-  if (p.xcd_remap) {
-    const int id = blockIdx.x;
-    const int xcd = id & 7, j = id >> 3;
-    const int pair = (j / p.gx) * 8 + xcd;
-    qb = j - (j / p.gx) * p.gx;
-    head = pair % p.H;
-    b = pair / p.H;
-  } else {
-    qb = blockIdx.x; head = blockIdx.y; b = blockIdx.z;
-  }
+  ATTN_BLOCK_DECODE(p, qb, head, b);
   const int64_t q0 = (int64_t)qb * QROWS + wave * 32;
-  const bf16_t* kbase = p.k + b * p.k_sb + (int64_t)head * p.k_sh;
-  const bf16_t* vbase = p.v + b * p.v_sb + (int64_t)head * p.v_sh;
+  const bf16_t* kbase = p.k + b * p.d.k_sb + (int64_t)head * p.d.k_sh;
+  const bf16_t* vbase = p.v + b * p.d.v_sb + (int64_t)head * p.d.v_sh;
 
   bf16x8 qf[8], dof[8];
   float sinit;   // -lse (log2 units) of this lane's query: every element of the score accumulators starts there
   float delta_q;
   {
     int64_t qrow = q0 + r;
-    if (qrow > p.Nq - 1) qrow = p.Nq - 1;
-    const bf16_t* qp = p.q + b * p.q_sb + qrow * p.q_sn + (int64_t)head * p.q_sh + 8 * h;
-    const bf16_t* dp_ = p.d_o + b * p.o_sb + qrow * p.o_sn + (int64_t)head * p.o_sh + 8 * h;
+    if (qrow > p.d.Nq - 1) qrow = p.d.Nq - 1;
+    const bf16_t* qp = p.q + b * p.d.q_sb + qrow * p.d.q_sn + (int64_t)head * p.d.q_sh + 8 * h;
+    const bf16_t* dp_ = p.d_o + b * p.d.o_sb + qrow * p.d.o_sn + (int64_t)head * p.d.o_sh + 8 * h;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
       qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
       dof[ks] = *reinterpret_cast<const bf16x8*>(dp_ + 16 * ks);
     }
-    sinit = -p.lse[(b * p.H + head) * p.Nq + qrow] * 1.4426950408889634f;
-    delta_q = p.delta[(b * p.H + head) * p.Nq + qrow];
+    sinit = -p.lse[(b * p.d.H + head) * p.d.Nq + qrow] * 1.4426950408889634f;
+    delta_q = p.delta[(b * p.d.H + head) * p.d.Nq + qrow];
   }
 
   // LDS-DMA roles (as attn_fwd.hip): wave w fills rows 8 w .. 8 w + 7 of both tiles, 2 + 2 one-KiB instructions.  Source = a
@@ -98,8 +81,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // the scalar base of the piece and the second is one more register.
   constexpr bool ONE_OFF = NW == 4;
   unsigned koff[NP], voff[ONE_OFF ? 1 : NP];
-  const int64_t kv_delta = (p.v_sn - p.k_sn) * 2;
-  auto lane16 = []() -> int { return (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >> 4); };
+  const int64_t kv_delta = (p.d.v_sn - p.d.k_sn) * 2;
+  auto lane16 = []() -> int { return (int)((unsigned)lane_now() >> 4); };
   auto dma_row_of = [&](int i) { return 4 * NP * wave + 4 * i + lane16(); };
   // recomputed from the hardware lane id at every use: a register held across the loop for it tipped three offsets into scratch
   // (wraps for a negative delta; the SUM with koff is a true offset >= 0)
@@ -107,9 +90,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const int row = 4 * NP * wave + 4 * i + (lane >> 4);
-    const int col = 8 * ((lane & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-    koff[i] = (unsigned)((row * p.k_sn + col) * 2);
-    if constexpr (!ONE_OFF) voff[i] = (unsigned)((row * p.v_sn + col) * 2);
+    const int col = 8 * ((lane & 15) ^ attn_swz(row));
+    koff[i] = (unsigned)((row * p.d.k_sn + col) * 2);
+    if constexpr (!ONE_OFF) voff[i] = (unsigned)((row * p.d.v_sn + col) * 2);
   }
   const char* kbase_u = lcv_uniform_ptr(kbase);
   const char* vbase_u = lcv_uniform_ptr(vbase);
@@ -117,9 +100,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   auto dma_tile = [&](int t, int buf, auto full_c) {
     constexpr bool FULL = decltype(full_c)::value;
     const unsigned dst = lds_addr0 + (unsigned)(buf * 2 * TILE_BYTES) + (unsigned)wave * (unsigned)(NP * 1024);
-    const char* kt = kbase_u + (int64_t)t * (128 * p.k_sn);   // scalar: 64 rows x stride x 2 bytes per tile
-    const char* vt = vbase_u + (int64_t)t * (128 * p.v_sn);
-    if (FULL || (int64_t)t * 64 + 64 <= p.Nk) {
+    const char* kt = kbase_u + (int64_t)t * (128 * p.d.k_sn);   // scalar: 64 rows x stride x 2 bytes per tile
+    const char* vt = vbase_u + (int64_t)t * (128 * p.d.v_sn);
+    if (FULL || (int64_t)t * 64 + 64 <= p.d.Nk) {
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
         lcv_lds_dma16_sv(koff[i], kt, dst + 1024u * i);
@@ -129,16 +112,16 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     } else {  // ragged last tile (once per workgroup): rows past Nk re-read the last key (masked below)
 #pragma unroll
       for (int i = 0; i < NP; ++i) {
-        int64_t back = (int64_t)t * 64 + dma_row_of(i) - (p.Nk - 1);
+        int64_t back = (int64_t)t * 64 + dma_row_of(i) - (p.d.Nk - 1);
         if (back < 0) back = 0;
-        lcv_lds_dma16(kt + koff[i] - back * p.k_sn * 2, dst + 1024u * i);
+        lcv_lds_dma16(kt + koff[i] - back * p.d.k_sn * 2, dst + 1024u * i);
         const int64_t vo = ONE_OFF ? (int64_t)koff[i] + (int64_t)dma_row_of(i) * kv_delta : (int64_t)voff[ONE_OFF ? 0 : i];
-        lcv_lds_dma16(vt + vo - back * p.v_sn * 2, dst + (unsigned)TILE_BYTES + 1024u * i);
+        lcv_lds_dma16(vt + vo - back * p.d.v_sn * 2, dst + (unsigned)TILE_BYTES + 1024u * i);
       }
     }
   };
 
-  const int kfz = ((r & 3) << 2) | ((r >> 2) & 3);
+  const int kfz = attn_swz(r);
   const int k_row_off = 256 * r;
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
   int t_base[2], t_low[2];
@@ -158,7 +141,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // ahead.  With two stages a tile had one tile's worth of MFMAs (~1.6 us) to land and the waves still waited 45 % of their
   // cycles; counted waits: at the end of tile t only tile t+1 has to be in, t+2 and t+3 stay in flight (4 pieces each).
   static_assert((NW == 8 && NS == 4) || (NW == 4 && NS == 2), "the counted waits below are written for these two forms");
-  const int nt = (int)((p.Nk + 63) / 64);
+  const int nt = (int)((p.d.Nk + 63) / 64);
 #pragma unroll
   for (int i = 0; i < NS - 1; ++i)
     if (i < nt) dma_tile(i, i, std::false_type{});
@@ -200,8 +183,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks % (ROW_AHEAD + 1)], qf[ks], s, 0, 0, 0);
         d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cf[ks % (ROW_AHEAD + 1)], dof[ks], d, 0, 0, 0);
       }
-      if (!has_next && (p.Nk & 63)) {  // last tile only
-        const int valid = (int)(p.Nk - (int64_t)t * 64) - 32 * half;
+      if (!has_next && (p.d.Nk & 63)) {  // last tile only
+        const int valid = (int)(p.d.Nk - (int64_t)t * 64) - 32 * half;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int key = (e & 3) + 8 * (e >> 2) + 4 * h;
@@ -249,7 +232,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   tile_body(nt - 1, std::true_type{}, std::false_type{});   // the (possibly ragged) last tile: the only body with mask code
 
   const int64_t qrow = q0 + r;
-  if (qrow < p.Nq) {
+  if (qrow < p.d.Nq) {
     bf16_t* dqp = p.dq + b * p.dq_sb + qrow * p.dq_sn + (int64_t)head * p.dq_sh;
 #pragma unroll
     for (int d = 0; d < 4; ++d)
@@ -264,35 +247,25 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 // called by lcv_attn_bwd (attn_bwd.hip) when scale * log2(e) == 1 and LCV_ATTN_BWD_VAR != 0
-int attn_bwd_dq2_launch(const void* q, const void* k, const void* v, const void* d_o, const float* lse, const float* delta,
-                        void* dq, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t q_sb, int64_t q_sn, int64_t q_sh,
-                        int64_t k_sb, int64_t k_sn, int64_t k_sh, int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb,
-                        int64_t o_sn, int64_t o_sh, int64_t dq_sb, int64_t dq_sn, int64_t dq_sh, float scale, hipStream_t s) {
-  AttnBwdDq2Params p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.d_o = (const bf16_t*)d_o;
-  p.lse = lse; p.delta = delta; p.dq = (bf16_t*)dq; p.Nq = Nq; p.Nk = Nk; p.H = (int)H;
-  p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
-  p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
-  p.dq_sb = dq_sb; p.dq_sn = dq_sn; p.dq_sh = dq_sh; p.scale = scale;
+int attn_bwd_dq2_launch(const AttnArgs& a, hipStream_t s) {
   const char* we = lcv_knob("LCV_ATTN_BWD_DQ_WAVES");   // A/B knob: 8 = one 8-wave workgroup per CU (4 stages), 4 = two 4-wave ones
   const int nw = (we && we[0] == '8') ? 8 : 4;
-  const size_t lds = (nw == 8 ? 4 : 2) * 2 * 64 * 256;   // NS stages of (K tile | V tile)
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)attn_bwd_dq2_kernel<8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 64 * 256) != hipSuccess ||
-        hipFuncSetAttribute((const void*)attn_bwd_dq2_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 64 * 256) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("attn_bwd: cannot raise dynamic LDS");
-      return LCV_EDEVICE;
-  }
-  const unsigned gx = (unsigned)((Nq + nw * 32 - 1) / (nw * 32));
+  constexpr size_t STAGE = 2 * 64 * 256;   // K tile | V tile
+  const size_t lds = (nw == 8 ? 4 : 2) * STAGE;
+  ATTN_RAISE_LDS_ONCE("attn_bwd", attn_raise_lds((const void*)attn_bwd_dq2_kernel<8, 4>, 4 * STAGE) &&
+                                      attn_raise_lds((const void*)attn_bwd_dq2_kernel<4, 2>, 2 * STAGE));
   // A/B knob LCV_ATTN_BWD_XCD=1 enables the head-per-XCD block order.  OFF by default: at the K3-TTA shapes (25 200 keys x 32
   // heads) it measured 27.06 vs 26.51 ms per layer in one process - unlike the forward, these passes are not helped by it
   const char* xe = lcv_knob("LCV_ATTN_BWD_XCD");
-  p.gx = (int)gx;
-  p.xcd_remap = ((B * H) % 8 == 0 && gx >= 8 && xe && xe[0] == '1') ? 1 : 0;
-  const dim3 grid = p.xcd_remap ? dim3(gx * (unsigned)(H * B)) : dim3(gx, (unsigned)H, (unsigned)B);
-  if (nw == 8) hipLaunchKernelGGL((attn_bwd_dq2_kernel<8, 4>), grid, dim3(512), lds, s, p);
-  else hipLaunchKernelGGL((attn_bwd_dq2_kernel<4, 2>), grid, dim3(256), lds, s, p);
+  const AttnGrid g = attn_grid(a.B, a.H, (a.Nq + nw * 32 - 1) / (nw * 32), xe && xe[0] == '1');
+  AttnBwdDq2Params p;
+  p.q = (const bf16_t*)a.q; p.k = (const bf16_t*)a.k; p.v = (const bf16_t*)a.v; p.d_o = (const bf16_t*)a.d_o;
+  p.lse = a.lse; p.delta = a.delta_ws; p.dq = (bf16_t*)a.dq;
+  p.d = attn_dims(a);
+  p.dq_sb = a.dq_sb; p.dq_sn = a.dq_sn; p.dq_sh = a.dq_sh; p.scale = a.scale;
+  p.gx = g.gx; p.xcd_remap = g.xcd_remap;
+  if (nw == 8) hipLaunchKernelGGL((attn_bwd_dq2_kernel<8, 4>), g.grid, dim3(512), lds, s, p);
+  else hipLaunchKernelGGL((attn_bwd_dq2_kernel<4, 2>), g.grid, dim3(256), lds, s, p);
   LCV_LAUNCH_CHECK("attn_bwd_dq2");
   return LCV_OK;
 }

@@ -15,53 +15,13 @@
 //   * V^T fragments come from the row-major V tile with ds_read_b64_tr_b16; K and V share
 //     one XOR-swizzled 256-byte-row image that is conflict-free for both read kinds.
 //   * algorithmic work per launch: 4*Nq*Nk*128 flop and (Nq*2 + Nk*2)*128*2 bytes per (b, h).
-#include "lcv_common.h"
+#include "attn_common.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) unsigned char lds_u8;
-
-struct AttnFwdParams {
-  const bf16_t* q;
-  const bf16_t* k;
-  const bf16_t* v;
-  bf16_t* o;
-  float* lse;
-  int64_t Nq, Nk;
-  int H;
-  int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+struct AttnFwdParams : AttnFwdLead {
   float scale, scale_log2e;
   int gx, xcd_remap;  // q-blocks per (b,h); head-per-XCD block order when (B*H) % 8 == 0
 };
-
-#define RESCALE_THR 6.0f  // log2 units: the running max may lag by up to 2^6 before O and l are rescaled
-
-// exchange with the partner lane (l ^ 32) by ONE v_permlane32_swap: r[0] = low-half values, r[1] = high-half values in
-// every lane.  The two operands must be distinct registers (the instruction swaps halves BETWEEN them; the compiler
-// folds identical operands into one register and the swap degenerates), hence the opaque copy.
-__device__ __forceinline__ void half_pair(float v, float& lo, float& hi) {
-  // inline asm on purpose: hipcc 7.2 folds the two results of __builtin_amdgcn_permlane32_swap into one value when
-  // both operands derive from the same variable (observed: `lo + hi` became `lo + lo`).  The leading s_nop 1 covers
-  // the "VALU write -> v_permlane read" hazard (2 wait states) that the compiler does not pad inside an asm string.
-  float a = v, b = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
-  lo = a;  // [low-half value | low-half value]
-  hi = b;  // [high-half value | high-half value]
-}
-__device__ __forceinline__ float half_max(float v) {
-  float lo, hi;
-  half_pair(v, lo, hi);
-  return fmaxf(lo, hi);
-}
-__device__ __forceinline__ float half_sum(float v) {
-  float lo, hi;
-  half_pair(v, lo, hi);
-  return lo + hi;
-}
-
-// byte offset of 16-byte chunk `ch` (0..15) of row `row` in a [rows][128] bf16 tile
-__device__ __forceinline__ int tile_off(int row, int ch) {
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
 
 // XATTN only names the instantiation used for the short-KV text cross-attention (Nk <= 512) so that profiles list it
 // separately from the self-attention launches (the dominant kernel); the code path is the same.
@@ -73,9 +33,6 @@ __device__ __forceinline__ int tile_off(int row, int ch) {
 //            a three-stage {QK^T | softmax | PV} ping-pong with waves 4-7 one stage behind, raw barriers and counted
 //            vmcnt: -1 %; the 16x16x32 MFMA shape: -10 % (this loop is vector-issue bound and that shape doubles the
 //            MFMA issue slots).  Sources of the dropped variants: scratch/tried/.)
-typedef __attribute__((address_space(1))) void gbl_void_t;
-typedef __attribute__((address_space(3))) void lds_void_t;
-
 template <int NWAVES, int PRIO, bool XATTN, int VAR>
 __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdParams p) {
   constexpr bool DMA = (VAR & 1) != 0;
@@ -97,32 +54,20 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  // Block order (speed only, never correctness): workgroup ids are dealt round-robin over the 8 XCDs, so with the
-  // remap every XCD walks the q-blocks of ITS OWN (batch, head) pairs and that head's K/V (24 MB at K3) streams
-  // through one 4 MiB L2 instead of eight.
   int qb, head;
   int64_t b;
-  if (p.xcd_remap) {
-    const int id = blockIdx.x;
-    const int xcd = id & 7, j = id >> 3;
-    const int pair = (j / p.gx) * 8 + xcd;
-    qb = j - (j / p.gx) * p.gx;
-    head = pair % p.H;
-    b = pair / p.H;
-  } else {
-    qb = blockIdx.x; head = blockIdx.y; b = blockIdx.z;
-  }
+  ATTN_BLOCK_DECODE(p, qb, head, b);
   const int64_t q0 = (int64_t)qb * QROWS + wave * 32;
 
-  const bf16_t* kbase = p.k + b * p.k_sb + (int64_t)head * p.k_sh;
-  const bf16_t* vbase = p.v + b * p.v_sb + (int64_t)head * p.v_sh;
+  const bf16_t* kbase = p.k + b * p.d.k_sb + (int64_t)head * p.d.k_sh;
+  const bf16_t* vbase = p.v + b * p.d.v_sb + (int64_t)head * p.d.v_sh;
 
   // ---- Q fragments (B operand): lane holds Q[q0 + r][16*ks + 8*h .. +8] ----
   bf16x8 qf[8];
   {
     int64_t qrow = q0 + r;
-    if (qrow > p.Nq - 1) qrow = p.Nq - 1;
-    const bf16_t* qp = p.q + b * p.q_sb + qrow * p.q_sn + (int64_t)head * p.q_sh + 8 * h;
+    if (qrow > p.d.Nq - 1) qrow = p.d.Nq - 1;
+    const bf16_t* qp = p.q + b * p.d.q_sb + qrow * p.d.q_sn + (int64_t)head * p.d.q_sh + 8 * h;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
   }
@@ -134,7 +79,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
   for (int i = 0; i < NCH; ++i) {
     const int c = tid + i * NT;
     st_row[i] = c >> 4;
-    st_off[i] = tile_off(c >> 4, c & 15);
+    st_off[i] = attn_tile_off(c >> 4, c & 15);
   }
   const int st_col = (tid & 15) * 8;
   u32x4 kreg[NCH], vreg[NCH];
@@ -146,9 +91,9 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     dma_row[i] = 8 * wave + 4 * i + (lane >> 4);
-    dma_col[i] = 8 * ((lane & 15) ^ (((dma_row[i] & 3) << 2) | ((dma_row[i] >> 2) & 3)));
-    kdma[i] = kbase + dma_row[i] * p.k_sn + dma_col[i];
-    vdma[i] = vbase + dma_row[i] * p.v_sn + dma_col[i];
+    dma_col[i] = 8 * ((lane & 15) ^ attn_swz(dma_row[i]));
+    kdma[i] = kbase + dma_row[i] * p.d.k_sn + dma_col[i];
+    vdma[i] = vbase + dma_row[i] * p.d.v_sn + dma_col[i];
   }
   // issue the K (which = 0) or V (which = 1) rows of tile t into buffer buf; kdma / vdma point at this lane's rows of tile t
   // FULL: the caller knows tile t is a full 64-key tile (every tile but the last) - no ragged-row branch in its stream
@@ -157,8 +102,8 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
     constexpr bool FULL = decltype(full_c)::value;
     lds_u8* dst = lds + buf * 2 * TILE_BYTES + which * TILE_BYTES + wave * 2048;
     const bf16_t** src = which ? vdma : kdma;
-    const int64_t sn = which ? p.v_sn : p.k_sn;
-    if (FULL || (int64_t)t * 64 + 64 <= p.Nk) {
+    const int64_t sn = which ? p.d.v_sn : p.d.k_sn;
+    if (FULL || (int64_t)t * 64 + 64 <= p.d.Nk) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         __builtin_amdgcn_global_load_lds((gbl_void_t*)src[i], (lds_void_t*)(dst + 1024 * i), 16, 0, 0);
@@ -167,7 +112,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
     } else {  // ragged last tile: rows past Nk re-read the last key (masked below)
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        int64_t back = (int64_t)t * 64 + dma_row[i] - (p.Nk - 1);
+        int64_t back = (int64_t)t * 64 + dma_row[i] - (p.d.Nk - 1);
         if (back < 0) back = 0;
         __builtin_amdgcn_global_load_lds((gbl_void_t*)(src[i] - back * sn), (lds_void_t*)(dst + 1024 * i), 16, 0, 0);
       }
@@ -183,9 +128,9 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
       int64_t row = kv0 + st_row[i];
-      if (row > p.Nk - 1) row = p.Nk - 1;  // tail keys re-read the last row; they are masked below
-      kreg[i] = *reinterpret_cast<const u32x4*>(kbase + row * p.k_sn + st_col);
-      vreg[i] = *reinterpret_cast<const u32x4*>(vbase + row * p.v_sn + st_col);
+      if (row > p.d.Nk - 1) row = p.d.Nk - 1;  // tail keys re-read the last row; they are masked below
+      kreg[i] = *reinterpret_cast<const u32x4*>(kbase + row * p.d.k_sn + st_col);
+      vreg[i] = *reinterpret_cast<const u32x4*>(vbase + row * p.d.v_sn + st_col);
     }
   };
   auto store_tile = [&](int buf) {
@@ -198,7 +143,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
   };
 
   // ---- per-lane LDS read addresses ----
-  const int kf = ((r & 3) << 2) | ((r >> 2) & 3);  // swizzle term of rows r and 32 + r
+  const int kf = attn_swz(r);  // swizzle term of rows r and 32 + r
   const int k_row_off = 256 * r;
   // transposed V reads: lane = 16*g + 4*q4 + p4 ; supplies row q4, columns 4*p4..4*p4+3 of its block
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, g1 = (lane >> 4) & 1;
@@ -221,7 +166,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
   float l_run = 0.f;        // this lane's partial row sum (its 32 of every 64 keys)
 
   if (PRIO == 1 && wave >= NWAVES / 2) __builtin_amdgcn_s_setprio(1);  // static priority for the younger half
-  const int nt = (int)((p.Nk + 63) / 64);
+  const int nt = (int)((p.d.Nk + 63) / 64);
   {
     if (DMA) {
       dma_tile(0, 0, std::false_type{});
@@ -260,8 +205,8 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
     }
 
     // ---- mask keys past Nk (last tile only; wave-uniform branch) ----
-    if (!has_next && (p.Nk & 63)) {
-      const int valid = (int)(p.Nk - (int64_t)t * 64);
+    if (!has_next && (p.d.Nk & 63)) {
+      const int valid = (int)(p.d.Nk - (int64_t)t * 64);
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int key = (e & 3) + 8 * (e >> 2) + 4 * h;
@@ -281,14 +226,14 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
     }
     float mx = fmaxf(mxa, mxb);
     mx = half_max(mx);
-    // defer-max: rescale O / l only when some query's running max grows by more than 2^RESCALE_THR; otherwise keep the
-    // old max (P <= 2^RESCALE_THR, harmless in fp32 sums and bf16 P).  The decision is wave-uniform and taken before
+    // defer-max: rescale O / l only when some query's running max grows by more than 2^ATTN_RESCALE_THR; otherwise keep the
+    // old max (P <= 2^ATTN_RESCALE_THR, harmless in fp32 sums and bf16 P).  The decision is wave-uniform and taken before
     // this tile's P exists and after the previous tile's PV finished, so nothing is ever scaled twice or not at all.
     float psum = 0.f;
     if constexpr (UNIT) {
       // the scores are already relative to the running max: mx > 0 is growth.  Tile 0 always takes the branch and sets
       // the first real maximum (m_run starts at 0 with O = l = 0, so its alpha multiplies zeros).
-      if (__builtin_amdgcn_ballot_w64(mx > RESCALE_THR) != 0ull || t == 0) {
+      if (__builtin_amdgcn_ballot_w64(mx > ATTN_RESCALE_THR) != 0ull || t == 0) {
         const float d = (t == 0) ? mx : fmaxf(mx, 0.f);
         const float alpha = __builtin_amdgcn_exp2f(-d);
         m_run += d;
@@ -311,7 +256,7 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
         psum += s0[e] + s1[e];
       }
     } else {
-      if (__builtin_amdgcn_ballot_w64((mx - m_run) * p.scale_log2e > RESCALE_THR) != 0ull) {
+      if (__builtin_amdgcn_ballot_w64((mx - m_run) * p.scale_log2e > ATTN_RESCALE_THR) != 0ull) {
         const float m_new = fmaxf(m_run, mx);
         const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale_log2e);  // first tile: exp2(-inf) = 0
         m_run = m_new;
@@ -388,8 +333,8 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
   const float l_tot = half_sum(l_run);
   const float inv = 1.0f / l_tot;
   const int64_t qrow = q0 + r;
-  if (qrow < p.Nq) {
-    bf16_t* op = p.o + b * p.o_sb + qrow * p.o_sn + (int64_t)head * p.o_sh;
+  if (qrow < p.d.Nq) {
+    bf16_t* op = p.o + b * p.d.o_sb + qrow * p.d.o_sn + (int64_t)head * p.d.o_sh;
 #pragma unroll
     for (int d = 0; d < 4; ++d)
 #pragma unroll
@@ -399,18 +344,9 @@ __global__ __launch_bounds__(NWAVES * 64) void attn_fwd_kernel(const AttnFwdPara
         for (int e = 0; e < 4; ++e) pk[e] = f2bf(oacc[d][4 * i + e] * inv);
         *reinterpret_cast<u16x4*>(op + 32 * d + 8 * i + 4 * h) = pk;
       }
-    if (p.lse && h == 0) p.lse[(b * p.H + head) * p.Nq + qrow] = m_run * p.scale + __logf(l_tot);
+    if (p.lse && h == 0) p.lse[(b * p.d.H + head) * p.d.Nq + qrow] = m_run * p.scale + __logf(l_tot);
   }
 }
-
-int attn_fwd_w64_launch(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Nq,
-                        int64_t Nk, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh,
-                        int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale,
-                        int xcd_ok, hipStream_t s);
-int attn_fwd_pipe_launch(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Nq,
-                         int64_t Nk, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh,
-                         int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale,
-                         int xcd_ok, hipStream_t s);   // attn_fwd_pipe.hip
 
 static thread_local const char* g_last_attn_kernel = "none";
 extern "C" const char* lcv_attn_fwd_last_kernel(void) { return g_last_attn_kernel; }
@@ -430,25 +366,22 @@ extern "C" int lcv_attn_fwd(const void* q, const void* k, const void* v, void* o
   LCV_CHECK_ARG(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)o % 8 == 0),
                 "attn_fwd: pointers must be 16-byte aligned");
   if (Nq == 0) return LCV_OK;
-  AttnFwdParams p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = lse;
-  p.Nq = Nq; p.Nk = Nk; p.H = (int)H;
-  p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
-  p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
-  p.scale = scale; p.scale_log2e = scale * 1.4426950408889634f;
+  AttnArgs a = {};
+  a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.scale = scale;
+  a.q_sb = q_sb; a.q_sn = q_sn; a.q_sh = q_sh; a.k_sb = k_sb; a.k_sn = k_sn; a.k_sh = k_sh;
+  a.v_sb = v_sb; a.v_sn = v_sn; a.v_sh = v_sh; a.o_sb = o_sb; a.o_sn = o_sn; a.o_sh = o_sh;
   constexpr int NW = 8;
   const size_t lds = 2 * 2 * 64 * 256;
-  const unsigned gx = (unsigned)((Nq + NW * 32 - 1) / (NW * 32));
   const char* xe = lcv_knob("LCV_ATTN_XCD");  // A/B knob: 0 disables the head-per-XCD block order
-  p.gx = (int)gx;
-  p.xcd_remap = ((B * H) % 8 == 0 && gx >= 8 && !(xe && xe[0] == '0')) ? 1 : 0;
-  const dim3 grid = p.xcd_remap ? dim3(gx * (unsigned)(H * B)) : dim3(gx, (unsigned)H, (unsigned)B);
+  const bool xcd_ok = !(xe && xe[0] == '0');
+  const AttnGrid g = attn_grid(B, H, (Nq + NW * 32 - 1) / (NW * 32), xcd_ok);
+  const AttnFwdParams p = {attn_fwd_lead(a), scale, scale * 1.4426950408889634f, g.gx, g.xcd_remap};
   auto launch = [&](auto kern) -> int {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    if (!attn_raise_lds((const void*)kern, lds)) {
       lcv_set_error("attn_fwd: cannot raise dynamic LDS");
       return LCV_EDEVICE;
     }
-    hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(kern, g.grid, dim3(NW * 64), lds, (hipStream_t)stream, p);
     return LCV_OK;
   };
   // Q pre-scaled into log2 units (scale = ln 2): the multiply-free softmax body
@@ -462,13 +395,11 @@ extern "C" int lcv_attn_fwd(const void* q, const void* k, const void* v, void* o
   const char* we = lcv_knob("LCV_ATTN_FWD_W64");
   if (unit && Nk > 512 && span32 && !(we && we[0] == '0')) {
     g_last_attn_kernel = "attn_fwd_w64_kernel";
-    return attn_fwd_w64_launch(q, k, v, o, lse, B, H, Nq, Nk, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn,
-                               o_sh, scale, !(xe && xe[0] == '0'), (hipStream_t)stream);
+    return attn_fwd_w64_launch(a, xcd_ok, (hipStream_t)stream);
   }
   if (unit && Nk > 512 && span32) {   // LCV_ATTN_FWD_W64=0: the two-waves-per-SIMD kernel of round 2, kept as the bit-level cross-check of the default
     g_last_attn_kernel = "attn_fwd_pipe_kernel";
-    return attn_fwd_pipe_launch(q, k, v, o, lse, B, H, Nq, Nk, q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn,
-                                o_sh, scale, !(xe && xe[0] == '0'), (hipStream_t)stream);
+    return attn_fwd_pipe_launch(a, xcd_ok, (hipStream_t)stream);
   }
   if (Nk <= 512) { g_last_attn_kernel = "attn_fwd_kernel<8, 0, true, 0>"; rc = launch(attn_fwd_kernel<NW, 0, true, 0>); }
   else if (unit) { g_last_attn_kernel = "attn_fwd_kernel<8, 0, false, 3>"; rc = launch(attn_fwd_kernel<NW, 0, false, 3>); }

@@ -28,57 +28,23 @@
 // [row max + exchange + vmcnt + barrier + first LDS reads of the next iteration] with the matrix pipe idle; now the fragments of
 // the next phase are requested before the barrier / before the iteration ends and the reductions sit in MFMA gaps.
 // Each gap's instructions are pinned (asm volatile + sched_barrier(0)): the order in this file IS the order in the binary.
-#include "lcv_common.h"
+#include "attn_common.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) unsigned char lds_u8p;
-typedef __attribute__((address_space(1))) void gbl_void_p;
-typedef __attribute__((address_space(3))) void lds_void_p;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-#define AS3P __attribute__((address_space(3)))
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 
-struct AttnFwdPipeParams {
-  const bf16_t* q;
-  const bf16_t* k;
-  const bf16_t* v;
-  bf16_t* o;
-  float* lse;
-  int64_t Nq, Nk;
-  int H;
-  int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+struct AttnFwdPipeParams : AttnFwdLead {
   float scale;
   int gx, xcd_remap;
   int prio_mode;   // how the two waves of a SIMD take turns in the issue arbitration (0 = none; the lab variants measured no gain)
 };
 
-#define PIPE_RESCALE_THR 6.0f
-
-__device__ __forceinline__ float pipe_half_max(float v) {
-  float a = v, b = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
-  return fmaxf(a, b);
-}
-__device__ __forceinline__ float pipe_half_sum(float v) {
-  float a = v, b = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
-  return a + b;
-}
 __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
   bf16x2_t t;
   t[0] = (__bf16)lo;
   t[1] = (__bf16)hi;
   return __builtin_bit_cast(unsigned, t);
 }
-
-// The vector instructions of the gaps are asm volatile ON PURPOSE: hipcc's instruction selection is free to hoist a pure
-// builtin (it gathered all 24 exponentials of phase 1 behind the second MFMA), while volatile statements keep their program order
-// among themselves and against sched_barrier(0).  Every result is consumed at least one gap later, so no statement needs a wait
-// state inside it (a transcendental's result is not read by the next instruction, an MFMA operand not written just before it).
-__device__ __forceinline__ float g_exp2(float x) { float y; asm volatile("v_exp_f32 %0, %1" : "=v"(y) : "v"(x)); return y; }
-__device__ __forceinline__ float g_add(float a, float b) { float y; asm volatile("v_add_f32 %0, %1, %2" : "=v"(y) : "v"(a), "v"(b)); return y; }
-__device__ __forceinline__ float g_max3(float a, float b, float c) { float y; asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(y) : "v"(a), "v"(b), "v"(c)); return y; }
-__device__ __forceinline__ unsigned g_pack(float lo, float hi) { unsigned y; asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(y) : "v"(lo), "v"(hi)); return y; }
 
 // element j (0..31) of the 64 scores a lane holds for one tile: j < 16 -> s0[j], else s1[j - 16]; quarter q = j >> 3 is the
 // B operand of PV k-step q
@@ -87,7 +53,7 @@ __device__ __forceinline__ unsigned g_pack(float lo, float hi) { unsigned y; asm
 __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipeParams p) {
   constexpr int TILE = 64 * 256;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  lds_u8p* lds = (lds_u8p*)smem;  // K buffers 0, 1 | V buffers 0, 1, 2
+  lds_u8* lds = (lds_u8*)smem;  // K buffers 0, 1 | V buffers 0, 1, 2
   constexpr int V_REGION = 2 * TILE;
 
   const int tid = threadIdx.x;
@@ -96,16 +62,7 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   const int r = lane & 31, h = lane >> 5;
   int qb, head;
   int64_t b;
-  if (p.xcd_remap) {   // head-per-XCD block order (speed only): see attn_fwd.hip
-    const int id = blockIdx.x;
-    const int xcd = id & 7, j = id >> 3;
-    const int pair = (j / p.gx) * 8 + xcd;
-    qb = j - (j / p.gx) * p.gx;
-    head = pair % p.H;
-    b = pair / p.H;
-  } else {
-    qb = blockIdx.x; head = blockIdx.y; b = blockIdx.z;
-  }
+  ATTN_BLOCK_DECODE(p, qb, head, b);   // head-per-XCD block order (speed only)
   const int64_t q0 = (int64_t)qb * 256 + wave * 32;
   // Issue arbitration between the two waves of a SIMD is "priority, then age": left alone, waves 0-3 (older) win every phase,
   // reach the barrier early and idle there while waves 4-7 finish.  prio_mode 1 / 2: the halves swap priority every phase, so
@@ -118,9 +75,9 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
     }
   };
   if (p.prio_mode == 3 && hi_half) __builtin_amdgcn_s_setprio(1);
-  const int nt_ = (int)((p.Nk + 63) / 64);
-  const bf16_t* kbase = p.k + b * p.k_sb + (int64_t)head * p.k_sh;
-  const bf16_t* vbase = p.v + b * p.v_sb + (int64_t)head * p.v_sh;
+  const int nt_ = (int)((p.d.Nk + 63) / 64);
+  const bf16_t* kbase = p.k + b * p.d.k_sb + (int64_t)head * p.d.k_sh;
+  const bf16_t* vbase = p.v + b * p.d.v_sb + (int64_t)head * p.d.v_sh;
 
   // ---- LDS-DMA roles: wave w fills rows 8 w .. 8 w + 7 of a tile with two 1-KiB instructions ----
   // Source address = scalar base of the tile (SGPR pair, advanced one tile per issue by scalar adds) + a per-lane 32-bit byte
@@ -130,29 +87,22 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   // The lane id is re-derived from the hardware (v_mbcnt) wherever a rare branch, the last tile or the epilogue needs it:
   // no register holds it across the loop, and what is computed from it cannot be hoisted in front of the loop (where output
   // pointers and edge-case offsets once sat in ~50 registers for the whole sweep and pushed loop values into scratch)
-  auto lane_now = []() -> int { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); };
   auto dma_row_of = [&](int ln, int i) { return 8 * wave + 4 * i + (ln >> 4); };
   auto dma_colb_of = [&](int ln, int i) {
     const int row = dma_row_of(ln, i);
-    return 16 * ((ln & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+    return 16 * ((ln & 15) ^ attn_swz(row));
   };
   auto full_off = [&](int i, int64_t sn) { return (unsigned)(dma_row_of(lane, i) * sn * 2 + dma_colb_of(lane, i)); };
   auto last_off = [&](int i, int64_t sn) {
     const int ln = lane_now();
     int64_t row = (int64_t)(nt_ - 1) * 64 + dma_row_of(ln, i);
-    if (row > p.Nk - 1) row = p.Nk - 1;
+    if (row > p.d.Nk - 1) row = p.d.Nk - 1;
     return (unsigned)(row * sn * 2 + dma_colb_of(ln, i));
   };
-  koff0 = full_off(0, p.k_sn); koff1 = full_off(1, p.k_sn); voff0 = full_off(0, p.v_sn); voff1 = full_off(1, p.v_sn);
-  // scalar (SGPR) bases of this (batch, head)'s K and V rows: readfirstlane makes the uniformity provable, so the asm below
-  // gets its "s" operands (a pointer hipcc cannot prove uniform would be handed over in VGPRs)
-  auto uniform_ptr = [](const bf16_t* ptr) -> const char* {
-    const unsigned long long v = (unsigned long long)ptr;
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (const char*)(((unsigned long long)hi << 32) | lo);
-  };
-  const char* kbase_u = uniform_ptr(kbase);
-  const char* vbase_u = uniform_ptr(vbase);
+  koff0 = full_off(0, p.d.k_sn); koff1 = full_off(1, p.d.k_sn); voff0 = full_off(0, p.d.v_sn); voff1 = full_off(1, p.d.v_sn);
+  // scalar (SGPR) bases of this (batch, head)'s K and V rows
+  const char* kbase_u = lcv_uniform_ptr(kbase);
+  const char* vbase_u = lcv_uniform_ptr(vbase);
   const unsigned lds_wave = (unsigned)(uintptr_t)lds + (unsigned)wave * 2048u;   // this wave's 2 KiB slice of every tile
   // The LDS-DMA is issued from inline asm ON PURPOSE: hipcc treats a builtin LDS-DMA as a pending LDS write and parks an
   // s_waitcnt vmcnt(0) in front of the next ds_read, which here would stall every iteration on the tiles it has just requested.
@@ -162,7 +112,7 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   auto dma_one = [&](auto which_c, auto i_c, int dst_tile, int tile) {
     constexpr int which = decltype(which_c)::value;
     constexpr int i = decltype(i_c)::value;
-    const int64_t sn = which ? p.v_sn : p.k_sn;
+    const int64_t sn = which ? p.d.v_sn : p.d.k_sn;
     const char* base = which ? vbase_u : kbase_u;
     unsigned off = which ? (i ? voff1 : voff0) : (i ? koff1 : koff0);
     if (tile == nt_ - 1) {   // scalar branch, taken four times per workgroup: the last tile's rows past Nk re-read the last key
@@ -187,13 +137,13 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   using KOP = std::integral_constant<int, 0>;
   using VOP = std::integral_constant<int, 1>;
 
-  // ---- per-lane LDS read offsets (the image of attn_fwd.hip::tile_off); set again from lane_now() after the loop so
+  // ---- per-lane LDS read offsets (attn_tile_off); set again from lane_now() after the loop so
   // that the loop's copies do not stay live through the register-hungry tail (which made hipcc spill them EVERYWHERE) ----
   int k_off[8];
   int v_off[2][4];
   auto set_read_offsets = [&](int ln, int slot) {
     const int rr = ln & 31, hh = ln >> 5;
-    const int kfz = ((rr & 3) << 2) | ((rr >> 2) & 3);
+    const int kfz = attn_swz(rr);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) k_off[ks] = 256 * rr + 16 * ((2 * ks + hh) ^ kfz);
     const int q4 = (ln >> 2) & 3, p4 = ln & 3, g1 = (ln >> 4) & 1;
@@ -205,22 +155,22 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   };
   set_read_offsets(lane, 2);   // (V slot 2: iteration 0 rotates the offsets to slot 0)
 
-  auto read_k = [&](const lds_u8p* kb, int i) -> bf16x8 {   // fragment of score MFMA i: k-step i >> 1, key block i & 1
-    return *reinterpret_cast<const AS3P bf16x8*>(kb + (i & 1) * 32 * 256 + k_off[i >> 1]);
+  auto read_k = [&](const lds_u8* kb, int i) -> bf16x8 {   // fragment of score MFMA i: k-step i >> 1, key block i & 1
+    return *reinterpret_cast<const AS3 bf16x8*>(kb + (i & 1) * 32 * 256 + k_off[i >> 1]);
   };
   // Q fragments (B operand of the score MFMAs): lane holds Q[q0 + r][16 ks + 8 h .. + 8], resident for the whole sweep
   bf16x8 qf[8];
   {
     int64_t qrow = q0 + r;
-    if (qrow > p.Nq - 1) qrow = p.Nq - 1;
-    const bf16_t* qp = p.q + b * p.q_sb + qrow * p.q_sn + (int64_t)head * p.q_sh + 8 * h;
+    if (qrow > p.d.Nq - 1) qrow = p.d.Nq - 1;
+    const bf16_t* qp = p.q + b * p.d.q_sb + qrow * p.d.q_sn + (int64_t)head * p.d.q_sh + 8 * h;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
   }
   // fragment of PV MFMA j (k-step j >> 2, dim block j & 3) of the V tile the offsets currently point at (v_slot)
   auto read_v = [&](int j) -> bf16x8 {
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3P s16x4*)(lds + 4096 * (j >> 2) + v_off[0][j & 3]));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3P s16x4*)(lds + 4096 * (j >> 2) + v_off[1][j & 3]));
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3 s16x4*)(lds + 4096 * (j >> 2) + v_off[0][j & 3]));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3 s16x4*)(lds + 4096 * (j >> 2) + v_off[1][j & 3]));
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
   };
 
@@ -235,12 +185,12 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   for (int e = 0; e < 16; ++e) minit[e] = 0.f;
   f32x16 sa0, sa1, sb0, sb1;   // score sets A and B
 
-  const int nt = (int)((p.Nk + 63) / 64);
-  const bool ragged = (p.Nk & 63) != 0;
+  const int nt = (int)((p.d.Nk + 63) / 64);
+  const bool ragged = (p.d.Nk & 63) != 0;
 
   // scores of the (possibly ragged) last tile past Nk -> -inf (before their row max)
   auto mask_last = [&](f32x16& s0, f32x16& s1) {
-    const int valid = (int)(p.Nk - (int64_t)(nt - 1) * 64);
+    const int valid = (int)(p.d.Nk - (int64_t)(nt - 1) * 64);
     const int hh_ = lane_now() >> 5;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -251,7 +201,7 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   };
   // row max of a score tile relative to the running max, and the (rare) rescale it may trigger
   auto settle = [&](f32x16& s0, f32x16& s1, float mx, bool first) {   // mx: row max over both lane halves
-    if (__builtin_amdgcn_ballot_w64(mx > PIPE_RESCALE_THR) != 0ull || first) {
+    if (__builtin_amdgcn_ballot_w64(mx > ATTN_RESCALE_THR) != 0ull || first) {
       const float d = first ? mx : fmaxf(mx, 0.f);
       const float alpha = __builtin_amdgcn_exp2f(-d);
       m_run += d;
@@ -288,7 +238,7 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   dma(VOP{}, V_REGION + TILE, 1);
   dma_wait_and_barrier();
   {
-    const lds_u8p* kb = lds;
+    const lds_u8* kb = lds;
 #pragma unroll
     for (int e = 0; e < 16; ++e) { sa0[e] = 0.f; sa1[e] = 0.f; }
 #pragma unroll
@@ -301,7 +251,7 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
     float mxa = sa0[0], mxb = sa1[0];
 #pragma unroll
     for (int e = 1; e < 16; ++e) { mxa = fmaxf(mxa, sa0[e]); mxb = fmaxf(mxb, sa1[e]); }
-    settle(sa0, sa1, pipe_half_max(fmaxf(mxa, mxb)), true);
+    settle(sa0, sa1, half_max(fmaxf(mxa, mxb)), true);
   }
   __syncthreads();                        // every wave has read K(0)
   dma(KOP{}, 0, 2);                       // K(2) -> K buffer 0; waited for at the barrier of iteration 0
@@ -313,8 +263,8 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   // (c0, c1) hold S(t), settled; (n0, n1) receive S(t+1).  STEADY: tiles up to t+3 exist and are full (no run-time checks).
   auto iteration = [&](const int t, auto par_c, f32x16& c0, f32x16& c1, f32x16& n0, f32x16& n1) {
     constexpr int PAR = decltype(par_c)::value;
-    const lds_u8p* kb = lds + (PAR ^ 1) * TILE;      // K(t+1)
-    const lds_u8p* kb_next = lds + PAR * TILE;        // K(t+2)
+    const lds_u8* kb = lds + (PAR ^ 1) * TILE;      // K(t+1)
+    const lds_u8* kb_next = lds + PAR * TILE;        // K(t+2)
     // edge handling by scalar conditions (a few SALU instructions per iteration; no second, register-hungry loop body)
     const bool has_k3 = t + 3 < nt;
     const bool has_v2 = t + 2 < nt;
@@ -347,12 +297,12 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
       const int a_lo = i ? (3 * (i - 1) + 1) / 2 : 0, a_hi = i ? e_lo : 0;
 #pragma unroll
       for (int j = 0; j < 24; ++j)
-        if (j >= e_lo && j < e_hi) ex[j] = g_exp2(SC(c0, c1, j));
+        if (j >= e_lo && j < e_hi) ex[j] = gap_exp2(SC(c0, c1, j));
 #pragma unroll
       for (int j = 0; j < 24; ++j)
         if (j >= a_lo && j < a_hi) {
-          psum = (j == 0) ? ex[0] : g_add(psum, ex[j]);
-          if (j & 1) pw[j >> 1] = g_pack(ex[j - 1], ex[j]);
+          psum = (j == 0) ? ex[0] : gap_add(psum, ex[j]);
+          if (j & 1) pw[j >> 1] = gap_pack(ex[j - 1], ex[j]);
         }
       SCHED_FENCE();
     }
@@ -379,26 +329,26 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
       if (j == 2 && has_v2) dma_one(VOP{}, I0{}, v_dst, t + 2);
       if (j == 3 && has_v2) dma_one(VOP{}, I1{}, v_dst, t + 2);
       if (j == 0) {   // element 23 (exp'ed in the last gap of phase 1)
-        psum = g_add(psum, ex[23]);
-        pw[11] = g_pack(ex[22], ex[23]);
+        psum = gap_add(psum, ex[23]);
+        pw[11] = gap_pack(ex[22], ex[23]);
       }
       if (j < 8) {    // quarter 3: one exp per gap, sum / pack one gap later
-        ex[24 + j] = g_exp2(SC(c0, c1, 24 + j));
+        ex[24 + j] = gap_exp2(SC(c0, c1, 24 + j));
         if (j > 0) {
-          psum = g_add(psum, ex[24 + j - 1]);
-          if ((j - 1) & 1) pw[12 + ((j - 1) >> 1)] = g_pack(ex[24 + j - 2], ex[24 + j - 1]);
+          psum = gap_add(psum, ex[24 + j - 1]);
+          if ((j - 1) & 1) pw[12 + ((j - 1) >> 1)] = gap_pack(ex[24 + j - 2], ex[24 + j - 1]);
         }
       } else if (j == 8) {
-        psum = g_add(psum, ex[31]);
-        pw[15] = g_pack(ex[30], ex[31]);
-        l_run = g_add(l_run, psum);
+        psum = gap_add(psum, ex[31]);
+        pw[15] = gap_pack(ex[30], ex[31]);
+        l_run = gap_add(l_run, psum);
       }
       // row max of S(t+1): chain a over n0[0..15] and n1[0] in gaps 2..9, chain b over n1[1..15] in gaps 3..9
-      if (j == 2) mxa = g_max3(n0[0], n0[1], n1[0]);
-      if (j > 2 && j < 10) mxa = g_max3(mxa, n0[2 * (j - 2)], n0[2 * (j - 2) + 1]);
-      if (j == 3) mxb = g_max3(n1[1], n1[2], n1[3]);
-      if (j > 3 && j < 10) mxb = g_max3(mxb, n1[2 * (j - 2)], n1[2 * (j - 2) + 1]);
-      if (j == 10) mx = pipe_half_max(g_max3(mxa, mxb, mxb));   // + the partner half's keys (one v_permlane32_swap)
+      if (j == 2) mxa = gap_max3(n0[0], n0[1], n1[0]);
+      if (j > 2 && j < 10) mxa = gap_max3(mxa, n0[2 * (j - 2)], n0[2 * (j - 2) + 1]);
+      if (j == 3) mxb = gap_max3(n1[1], n1[2], n1[3]);
+      if (j > 3 && j < 10) mxb = gap_max3(mxb, n1[2 * (j - 2)], n1[2 * (j - 2) + 1]);
+      if (j == 10) mx = half_max(gap_max3(mxa, mxb, mxb));   // + the partner half's keys (one v_permlane32_swap)
       SCHED_FENCE();
     }
     settle(n0, n1, mx, false);
@@ -441,13 +391,13 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
   }
 
   // ---- epilogue ----
-  const float l_tot = pipe_half_sum(l_run);
+  const float l_tot = half_sum(l_run);
   const float inv = 1.0f / l_tot;
   const int lane_l = lane_now();
   const int r_l = lane_l & 31, h_l = lane_l >> 5;
   const int64_t qrow = q0 + r_l;
-  if (qrow < p.Nq) {
-    bf16_t* op = p.o + b * p.o_sb + qrow * p.o_sn + (int64_t)head * p.o_sh;
+  if (qrow < p.d.Nq) {
+    bf16_t* op = p.o + b * p.d.o_sb + qrow * p.d.o_sn + (int64_t)head * p.d.o_sh;
 #pragma unroll
     for (int d = 0; d < 4; ++d)
 #pragma unroll
@@ -457,34 +407,17 @@ __global__ __launch_bounds__(512) void attn_fwd_pipe_kernel(const AttnFwdPipePar
         for (int e = 0; e < 4; ++e) pk[e] = f2bf(oacc[d][4 * i + e] * inv);
         *reinterpret_cast<u16x4*>(op + 32 * d + 8 * i + 4 * h_l) = pk;
       }
-    if (p.lse && h_l == 0) p.lse[(b * p.H + head) * p.Nq + qrow] = m_run * p.scale + __logf(l_tot);
+    if (p.lse && h_l == 0) p.lse[(b * p.d.H + head) * p.d.Nq + qrow] = m_run * p.scale + __logf(l_tot);
   }
 }
 
 // called by lcv_attn_fwd (attn_fwd.hip) for unit-scale self-attention with Nk >= 256
-int attn_fwd_pipe_launch(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Nq,
-                         int64_t Nk, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh,
-                         int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale,
-                         int xcd_ok, hipStream_t s) {
-  AttnFwdPipeParams p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = lse;
-  p.Nq = Nq; p.Nk = Nk; p.H = (int)H;
-  p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
-  p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
-  p.scale = scale;
-  const unsigned gx = (unsigned)((Nq + 255) / 256);
-  p.gx = (int)gx;
-  p.xcd_remap = (xcd_ok && (B * H) % 8 == 0 && gx >= 8) ? 1 : 0;
-  p.prio_mode = 0;
+int attn_fwd_pipe_launch(const AttnArgs& a, bool xcd_ok, hipStream_t s) {
+  const AttnGrid g = attn_grid(a.B, a.H, (a.Nq + 255) / 256, xcd_ok);
+  const AttnFwdPipeParams p = {attn_fwd_lead(a), a.scale, g.gx, g.xcd_remap, 0};
   const size_t lds = 5 * 64 * 256;   // K x2, V x3
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)attn_fwd_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("attn_fwd: cannot raise dynamic LDS");
-      return LCV_EDEVICE;
-  }
-  const dim3 grid = p.xcd_remap ? dim3(gx * (unsigned)(H * B)) : dim3(gx, (unsigned)H, (unsigned)B);
-  hipLaunchKernelGGL(attn_fwd_pipe_kernel, grid, dim3(512), lds, s, p);
+  ATTN_RAISE_LDS_ONCE("attn_fwd", attn_raise_lds((const void*)attn_fwd_pipe_kernel, lds));
+  hipLaunchKernelGGL(attn_fwd_pipe_kernel, g.grid, dim3(512), lds, s, p);
   LCV_LAUNCH_CHECK("attn_fwd_pipe");
   return LCV_OK;
 }

@@ -19,44 +19,13 @@
 // MFMAs are issued from asm with the register class pinned (score sets in arch VGPRs, O in AGPRs, Q fragments as AGPR B
 // operands): left alone hipcc puts every MFMA result of a > 256-register kernel into AGPRs (round 3, scratch/tried/attn_bwd_dkv3_r3_one_wave_per_simd.hip.txt).  asm is opaque
 // to the hazard recogniser: see GUARD below and profiles/r03_attn_bwd_lab.md for the four ways that went wrong before.
-#include "lcv_common.h"
+#include "attn_common.h"
 #include <type_traits>
 
-typedef __attribute__((address_space(3))) unsigned char lds_u8w;
-#define AS3W __attribute__((address_space(3)))
-#define SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-
-struct AttnFwdW64Params {
-  const bf16_t* q;
-  const bf16_t* k;
-  const bf16_t* v;
-  bf16_t* o;
-  float* lse;
-  int64_t Nq, Nk;
-  int H;
-  int64_t q_sb, q_sn, q_sh, k_sb, k_sn, k_sh, v_sb, v_sn, v_sh, o_sb, o_sn, o_sh;
+struct AttnFwdW64Params : AttnFwdLead {
   float scale;
   int gx, xcd_remap;
 };
-
-#define W64_RESCALE_THR 6.0f
-
-
-__device__ __forceinline__ float w64_half_max(float v) {
-  float a = v, b = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
-  return fmaxf(a, b);
-}
-__device__ __forceinline__ float w64_half_sum(float v) {
-  float a = v, b = v;
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
-  return a + b;
-}
-// gap instructions: asm volatile keeps their program order (attn_fwd_pipe.hip)
-__device__ __forceinline__ float w_exp2(float x) { float y; asm volatile("v_exp_f32 %0, %1" : "=v"(y) : "v"(x)); return y; }
-__device__ __forceinline__ float w_add(float a, float b) { float y; asm volatile("v_add_f32 %0, %1, %2" : "=v"(y) : "v"(a), "v"(b)); return y; }
-__device__ __forceinline__ float w_max3(float a, float b, float c) { float y; asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(y) : "v"(a), "v"(b), "v"(c)); return y; }
-__device__ __forceinline__ unsigned w_pack(float lo, float hi) { unsigned y; asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(y) : "v"(lo), "v"(hi)); return y; }
 
 // ---- the gap table of the steady loop: what follows each MFMA of phase 1 (score MFMA i) and phase 2 (PV MFMA j) ----
 // At one wave per SIMD a v_mfma_f32_32x32x16_bf16 hides about 5 single-issue instructions / 24 issue-cycles with at most one
@@ -209,7 +178,7 @@ __device__ __forceinline__ void mfma_o(f32x16& c, const bf16x8& a, const bf16x8&
 __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Params p) {
   constexpr int TILE = 64 * 256;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  lds_u8w* lds = (lds_u8w*)smem;  // K buffers 0, 1 | V buffers 0, 1, 2
+  lds_u8* lds = (lds_u8*)smem;  // K buffers 0, 1 | V buffers 0, 1, 2
   constexpr int V_REGION = 2 * TILE;
 
   const int tid = threadIdx.x;
@@ -218,47 +187,37 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
   const int r = lane & 31, h = lane >> 5;
   int qb, head;
   int64_t b;
-  if (p.xcd_remap) {   // head-per-XCD block order (speed only): see attn_fwd.hip
-    const int id = blockIdx.x;
-    const int xcd = id & 7, j = id >> 3;
-    const int pair = (j / p.gx) * 8 + xcd;
-    qb = j - (j / p.gx) * p.gx;
-    head = pair % p.H;
-    b = pair / p.H;
-  } else {
-    qb = blockIdx.x; head = blockIdx.y; b = blockIdx.z;
-  }
+  ATTN_BLOCK_DECODE(p, qb, head, b);   // head-per-XCD block order (speed only)
   const int64_t q0 = (int64_t)qb * 256 + wave * 64;
-  auto lane_now = []() -> int { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); };
-  const int nt = (int)((p.Nk + 63) / 64);
-  const bool ragged = (p.Nk & 63) != 0;
-  const char* kbase_u = lcv_uniform_ptr(p.k + b * p.k_sb + (int64_t)head * p.k_sh);
-  const char* vbase_u = lcv_uniform_ptr(p.v + b * p.v_sb + (int64_t)head * p.v_sh);
+  const int nt = (int)((p.d.Nk + 63) / 64);
+  const bool ragged = (p.d.Nk & 63) != 0;
+  const char* kbase_u = lcv_uniform_ptr(p.k + b * p.d.k_sb + (int64_t)head * p.d.k_sh);
+  const char* vbase_u = lcv_uniform_ptr(p.v + b * p.d.v_sb + (int64_t)head * p.d.v_sh);
 
   // ---- LDS-DMA roles: wave w fills rows 16 w .. 16 w + 15 of a tile with four 1-KiB requests (scalar tile base + a constant
   // per-lane 32-bit byte offset: row 16 w + 4 i + (lane >> 4), swizzled 16-byte column) ----
   auto dma_row_of = [&](int ln, int i) { return 16 * wave + 4 * i + (ln >> 4); };
   auto dma_colb_of = [&](int ln, int i) {
     const int row = dma_row_of(ln, i);
-    return 16 * ((ln & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+    return 16 * ((ln & 15) ^ attn_swz(row));
   };
   unsigned koff[4], voff[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    koff[i] = (unsigned)(dma_row_of(lane, i) * p.k_sn * 2 + dma_colb_of(lane, i));
-    voff[i] = (unsigned)(dma_row_of(lane, i) * p.v_sn * 2 + dma_colb_of(lane, i));
+    koff[i] = (unsigned)(dma_row_of(lane, i) * p.d.k_sn * 2 + dma_colb_of(lane, i));
+    voff[i] = (unsigned)(dma_row_of(lane, i) * p.d.v_sn * 2 + dma_colb_of(lane, i));
   }
   auto last_off = [&](int i, int64_t sn) {   // the last tile's rows past Nk re-read the last key (their scores are masked)
     const int ln = lane_now();
     int64_t row = (int64_t)(nt - 1) * 64 + dma_row_of(ln, i);
-    if (row > p.Nk - 1) row = p.Nk - 1;
+    if (row > p.d.Nk - 1) row = p.d.Nk - 1;
     return (unsigned)(row * sn * 2 + dma_colb_of(ln, i));
   };
   const unsigned lds_wave = (unsigned)(uintptr_t)lds + (unsigned)wave * 4096u;   // this wave's 4 KiB slice of every tile
   // piece i (0..3) of tile `tile` of K (which = 0) or V (which = 1) to the buffer at LDS byte offset `dst_tile`
   // (which / i are plain ints that fold once the calling loop is unrolled: ONE copy of this body per gap, or the unroller gives up)
   auto dma_one = [&](int which, int i, int dst_tile, int tile, bool known_full) __attribute__((always_inline)) {
-    const int64_t sn = which ? p.v_sn : p.k_sn;
+    const int64_t sn = which ? p.d.v_sn : p.d.k_sn;
     const char* base = which ? vbase_u : kbase_u;
     unsigned off = which ? voff[i] : koff[i];
     if (!known_full && tile == nt - 1) off = last_off(i, sn);
@@ -274,7 +233,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
     asm volatile("s_mov_b32 m0, %0" :: "s"(lds_wave + (unsigned)dst_tile + 1024u * i) : "memory", "m0");
   };
   auto dma_req = [&](int which, int i, int tile, bool known_full) __attribute__((always_inline)) {
-    const int64_t sn = which ? p.v_sn : p.k_sn;
+    const int64_t sn = which ? p.d.v_sn : p.d.k_sn;
     const char* base = which ? vbase_u : kbase_u;
     unsigned off = which ? voff[i] : koff[i];
     if (!known_full && tile == nt - 1) off = last_off(i, sn);
@@ -293,7 +252,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
   int v_off[2][4];
   auto set_read_offsets = [&](int ln, int slot) {
     const int rr = ln & 31, hh = ln >> 5;
-    const int kfz = ((rr & 3) << 2) | ((rr >> 2) & 3);
+    const int kfz = ((rr & 3) << 2) | ((rr >> 2) & 3);   // = attn_swz(rr), written out: through the function this kernel allocates its registers differently
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) k_off[ks] = 256 * rr + 16 * ((2 * ks + hh) ^ kfz);
     const int q4 = (ln >> 2) & 3, p4 = ln & 3, g1 = (ln >> 4) & 1;
@@ -305,12 +264,12 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
                          16 * ((2 * g1 + (p4 >> 1)) ^ (hh + 2 * half));   // ABSOLUTE LDS byte address: no base add per read
   };
   set_read_offsets(lane, 2);   // (V slot 2: iteration 0 rotates the offsets to slot 0)
-  auto read_k = [&](const lds_u8w* kb, int f) __attribute__((always_inline)) -> bf16x8 {   // K fragment f: k-step f >> 1, key block f & 1
-    return *reinterpret_cast<const AS3W bf16x8*>(kb + (f & 1) * 32 * 256 + k_off[f >> 1]);
+  auto read_k = [&](const lds_u8* kb, int f) __attribute__((always_inline)) -> bf16x8 {   // K fragment f: k-step f >> 1, key block f & 1
+    return *reinterpret_cast<const AS3 bf16x8*>(kb + (f & 1) * 32 * 256 + k_off[f >> 1]);
   };
   auto read_v = [&](int g) __attribute__((always_inline)) -> bf16x8 {   // V^T fragment g: k-step g >> 2, dim block g & 3, of the slot the offsets point at
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3W s16x4*)(uintptr_t)(unsigned)(v_off[0][g & 3] + 4096 * (g >> 2)));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3W s16x4*)(uintptr_t)(unsigned)(v_off[1][g & 3] + 4096 * (g >> 2)));
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3 s16x4*)(uintptr_t)(unsigned)(v_off[0][g & 3] + 4096 * (g >> 2)));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((AS3 s16x4*)(uintptr_t)(unsigned)(v_off[1][g & 3] + 4096 * (g >> 2)));
     return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
   };
 
@@ -319,8 +278,8 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb) {
     int64_t qrow = q0 + 32 * nb + r;
-    if (qrow > p.Nq - 1) qrow = p.Nq - 1;
-    const bf16_t* qp = p.q + b * p.q_sb + qrow * p.q_sn + (int64_t)head * p.q_sh + 8 * h;
+    if (qrow > p.d.Nq - 1) qrow = p.d.Nq - 1;
+    const bf16_t* qp = p.q + b * p.d.q_sb + qrow * p.d.q_sn + (int64_t)head * p.d.q_sh + 8 * h;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) qf[nb][ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
   }
@@ -347,7 +306,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
   f32x16 sa[2][2], sb[2][2];   // score sets A and B: [key block][query block]
 
   auto mask_last = [&](f32x16 (&s)[2][2]) __attribute__((always_inline)) {   // scores of the ragged last tile past Nk -> -inf
-    const int valid = (int)(p.Nk - (int64_t)(nt - 1) * 64);
+    const int valid = (int)(p.d.Nk - (int64_t)(nt - 1) * 64);
     const int hh_ = lane_now() >> 5;
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb)
@@ -431,7 +390,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
       for (int e = 1; e < 16; ++e) mx = fmaxf(mx, sa[0][nb][e]);
 #pragma unroll
       for (int e = 0; e < 16; ++e) mx = fmaxf(mx, sa[1][nb][e]);
-      settle(sa, nb_c, w64_half_max(mx), true, true);
+      settle(sa, nb_c, half_max(mx), true, true);
     };
     first_settle(std::integral_constant<int, 0>{});
     first_settle(std::integral_constant<int, 1>{});
@@ -447,8 +406,8 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
   auto iteration = [&](const int t, auto par_c, auto steady_c, f32x16 (&c)[2][2], f32x16 (&n)[2][2]) __attribute__((always_inline)) {
     constexpr int PAR = decltype(par_c)::value;
     constexpr bool STEADY = decltype(steady_c)::value;
-    const lds_u8w* kb = lds + (PAR ^ 1) * TILE;      // K(t+1)
-    const lds_u8w* kb_next = lds + PAR * TILE;        // K(t+2)
+    const lds_u8* kb = lds + (PAR ^ 1) * TILE;      // K(t+1)
+    const lds_u8* kb_next = lds + PAR * TILE;        // K(t+2)
     const bool has_k3 = STEADY || t + 3 < nt;
     const bool has_v2 = STEADY || t + 2 < nt;
     const int v_delta = next_v_slot();                // v_slot == t % 3 from here on
@@ -463,25 +422,25 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
       constexpr W64Op o = decltype(phase_c)::value == 1 ? W64_P1[decltype(gap_c)::value][decltype(slot_c)::value]
                                                         : W64_P2[decltype(gap_c)::value][decltype(slot_c)::value];
       constexpr int b_ = o.b, e = o.e;
-      if constexpr (o.kind == W64_EXP) ex[b_][e] = w_exp2(SCW(c, b_, e));
-      if constexpr (o.kind == W64_ADD) psum[b_] = w_add((e == 1) ? ex[b_][0] : psum[b_], ex[b_][e]);
-      if constexpr (o.kind == W64_PACK) pw[b_][e] = w_pack(ex[b_][2 * e], ex[b_][2 * e + 1]);
-      if constexpr (o.kind == W64_LRUN) l_run[b_] = w_add(l_run[b_], psum[b_]);
+      if constexpr (o.kind == W64_EXP) ex[b_][e] = gap_exp2(SCW(c, b_, e));
+      if constexpr (o.kind == W64_ADD) psum[b_] = gap_add((e == 1) ? ex[b_][0] : psum[b_], ex[b_][e]);
+      if constexpr (o.kind == W64_PACK) pw[b_][e] = gap_pack(ex[b_][2 * e], ex[b_][2 * e + 1]);
+      if constexpr (o.kind == W64_LRUN) l_run[b_] = gap_add(l_run[b_], psum[b_]);
       if constexpr (o.kind == W64_VOFF) asm volatile("v_add_u32 %0, %1, %0" : "+v"(v_off[b_ >> 2][b_ & 3]) : "s"(v_delta));
       if constexpr (o.kind == W64_MAX) {   // two chains of 8 max3 per query block; step 7 folds chain a into b: the full maximum
         if constexpr (e == 0) {
-          mxa[b_] = w_max3(n[0][b_][0], n[0][b_][1], n[0][b_][2]);
-          mxb[b_] = w_max3(n[1][b_][0], n[1][b_][1], n[1][b_][2]);
+          mxa[b_] = gap_max3(n[0][b_][0], n[0][b_][1], n[0][b_][2]);
+          mxb[b_] = gap_max3(n[1][b_][0], n[1][b_][1], n[1][b_][2]);
         } else if constexpr (e < 7) {
-          mxa[b_] = w_max3(mxa[b_], n[0][b_][2 * e + 1], n[0][b_][2 * e + 2]);
-          mxb[b_] = w_max3(mxb[b_], n[1][b_][2 * e + 1], n[1][b_][2 * e + 2]);
+          mxa[b_] = gap_max3(mxa[b_], n[0][b_][2 * e + 1], n[0][b_][2 * e + 2]);
+          mxb[b_] = gap_max3(mxb[b_], n[1][b_][2 * e + 1], n[1][b_][2 * e + 2]);
         } else {
-          mxa[b_] = w_max3(mxa[b_], n[0][b_][15], mxb[b_]);
-          mxb[b_] = w_max3(mxa[b_], n[1][b_][15], n[1][b_][14]);
+          mxa[b_] = gap_max3(mxa[b_], n[0][b_][15], mxb[b_]);
+          mxb[b_] = gap_max3(mxa[b_], n[1][b_][15], n[1][b_][14]);
         }
       }
-      if constexpr (o.kind == W64_HMAX) mxh[b_] = w64_half_max(mxb[b_]);
-      if constexpr (o.kind == W64_BALLOT) need[b_] = __builtin_amdgcn_ballot_w64(mxh[b_] > W64_RESCALE_THR) != 0ull;
+      if constexpr (o.kind == W64_HMAX) mxh[b_] = half_max(mxb[b_]);
+      if constexpr (o.kind == W64_BALLOT) need[b_] = __builtin_amdgcn_ballot_w64(mxh[b_] > ATTN_RESCALE_THR) != 0ull;
       // the eight LDS-DMA requests of this iteration: K(t+3) into K(t+1)'s buffer, V(t+2) into V(t-1)'s slot (both free since
       // the barrier); waited for at the next barrier, a whole iteration away
       if constexpr (o.kind == W64_M0) {
@@ -557,7 +516,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
       }
       l_run[nb] += psum;
 #pragma unroll
-      for (int m = 0; m < 16; ++m) pw[nb][m] = w_pack(ex[2 * m], ex[2 * m + 1]);
+      for (int m = 0; m < 16; ++m) pw[nb][m] = gap_pack(ex[2 * m], ex[2 * m + 1]);
     }
 #pragma unroll
     for (int g = 0; g < 16; ++g) {
@@ -597,11 +556,11 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
   const int r_l = lane_l & 31, h_l = lane_l >> 5;
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb) {
-    const float l_tot = w64_half_sum(l_run[nb]);
+    const float l_tot = half_sum(l_run[nb]);
     const float inv = 1.0f / l_tot;
     const int64_t qrow = q0 + 32 * nb + r_l;
-    if (qrow < p.Nq) {
-      bf16_t* op = p.o + b * p.o_sb + qrow * p.o_sn + (int64_t)head * p.o_sh;
+    if (qrow < p.d.Nq) {
+      bf16_t* op = p.o + b * p.d.o_sb + qrow * p.d.o_sn + (int64_t)head * p.d.o_sh;
 #pragma unroll
       for (int d = 0; d < 4; ++d)
 #pragma unroll
@@ -611,35 +570,19 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
           for (int e = 0; e < 4; ++e) pk[e] = f2bf(oacc[nb][d][4 * i + e] * inv);
           *reinterpret_cast<u16x4*>(op + 32 * d + 8 * i + 4 * h_l) = pk;
         }
-      if (p.lse && h_l == 0) p.lse[(b * p.H + head) * p.Nq + qrow] = m_run[nb] * p.scale + __logf(l_tot);
+      if (p.lse && h_l == 0) p.lse[(b * p.d.H + head) * p.d.Nq + qrow] = m_run[nb] * p.scale + __logf(l_tot);
     }
   }
 }
 
 // called by lcv_attn_fwd (attn_fwd.hip) for unit-scale self-attention with Nk > 512: the default since round 3 (LCV_ATTN_FWD_W64=0
 // selects attn_fwd_pipe.hip instead)
-int attn_fwd_w64_launch(const void* q, const void* k, const void* v, void* o, float* lse, int64_t B, int64_t H, int64_t Nq,
-                        int64_t Nk, int64_t q_sb, int64_t q_sn, int64_t q_sh, int64_t k_sb, int64_t k_sn, int64_t k_sh,
-                        int64_t v_sb, int64_t v_sn, int64_t v_sh, int64_t o_sb, int64_t o_sn, int64_t o_sh, float scale,
-                        int xcd_ok, hipStream_t s) {
-  AttnFwdW64Params p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (bf16_t*)o; p.lse = lse;
-  p.Nq = Nq; p.Nk = Nk; p.H = (int)H;
-  p.q_sb = q_sb; p.q_sn = q_sn; p.q_sh = q_sh; p.k_sb = k_sb; p.k_sn = k_sn; p.k_sh = k_sh;
-  p.v_sb = v_sb; p.v_sn = v_sn; p.v_sh = v_sh; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sh = o_sh;
-  p.scale = scale;
-  const unsigned gx = (unsigned)((Nq + 255) / 256);
-  p.gx = (int)gx;
-  p.xcd_remap = (xcd_ok && (B * H) % 8 == 0 && gx >= 8) ? 1 : 0;
+int attn_fwd_w64_launch(const AttnArgs& a, bool xcd_ok, hipStream_t s) {
+  const AttnGrid g = attn_grid(a.B, a.H, (a.Nq + 255) / 256, xcd_ok);
+  const AttnFwdW64Params p = {attn_fwd_lead(a), a.scale, g.gx, g.xcd_remap};
   const size_t lds = 5 * 64 * 256;   // K x2, V x3
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)attn_fwd_w64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("attn_fwd_w64: cannot raise dynamic LDS");
-      return LCV_EDEVICE;
-  }
-  const dim3 grid = p.xcd_remap ? dim3(gx * (unsigned)(H * B)) : dim3(gx, (unsigned)H, (unsigned)B);
-  hipLaunchKernelGGL(attn_fwd_w64_kernel, grid, dim3(256), lds, s, p);
+  ATTN_RAISE_LDS_ONCE("attn_fwd_w64", attn_raise_lds((const void*)attn_fwd_w64_kernel, lds));
+  hipLaunchKernelGGL(attn_fwd_w64_kernel, g.grid, dim3(256), lds, s, p);
   LCV_LAUNCH_CHECK("attn_fwd_w64");
   return LCV_OK;
 }

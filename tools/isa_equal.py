@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Are the kernels of a HIP source the same machine code as at an earlier revision?  (the check behind a pure refactor)
+
+Exports csrc/ and include/ of <rev> with `git archive`, compiles each named source from both trees to device assembly with the
+library's own recipe (lcv_hip/build.py: HIPCC, FLAGS, EXTRA, plus --cuda-device-only -S), normalises both listings and compares
+them kernel by kernel: instructions, labels, the .amdhsa_* descriptor (register counts, LDS, kernarg size) and the code-object
+metadata.  Normalising means: comments, blank lines, `.file` / `.ident` go; a mangled symbol becomes its function name plus
+template arguments (the parameter types - a renamed struct - drop out); basic-block labels lose their function index.
+
+Usage: python tools/isa_equal.py <rev> [file.hip ...]     (default: csrc/attn_*.hip; exit code 1 on any difference)
+"""
+import re
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+from typing import Dict, List
+
+ROOT = Path(__file__).resolve().parents[1]
+PKG = "longcat-video-tta_amd"
+_MANGLED = re.compile(r"_Z(\d+)(\w+)")
+_TEMPLATE = re.compile(r"I(?:L[a-z]\w*?E)+E")       # literal template arguments only: <8, 0, true, 0> = ILi8ELi0ELb1ELi0EE
+_LABEL = re.compile(r"\.L(BB|func_end|func_begin)\d+")
+
+
+def _plain(m: "re.Match") -> str:
+    n, rest = int(m.group(1)), m.group(2)
+    if n > len(rest):
+        return m.group(0)
+    name, tail = rest[:n], rest[n:]
+    t = _TEMPLATE.match(tail)
+    return name + (t.group(0) if t else "")
+
+
+def normalise(text: str) -> Dict[str, List[str]]:
+    """hipcc -S text -> {kernel: its lines from the entry label to .end_amdhsa_kernel}, plus "(metadata)"."""
+    out: Dict[str, List[str]] = {}
+    cur, functions = None, set()
+    for raw in text.splitlines():
+        line = raw.split(";", 1)[0].rstrip()
+        line = _LABEL.sub(r".L\1", _MANGLED.sub(_plain, line))
+        s = line.strip()
+        if not s or s.startswith((".file", ".ident")):
+            continue
+        m = re.fullmatch(r"\.type\s+(\S+),@function", s)
+        if m:
+            functions.add(m.group(1) + ":")
+        if s == ".amdgpu_metadata":
+            cur = out.setdefault("(metadata)", [])
+        elif s in functions:
+            cur = out.setdefault(s[:-1], [])
+        if cur is not None:
+            cur.append(s)
+            if s in (".end_amdhsa_kernel", ".end_amdgpu_metadata") or s.startswith(".Lfunc_end"):
+                cur = None
+    return out
+
+
+def compare(old: str, new: str, show: int = 4) -> List[str]:
+    """-> one report line per kernel: `identical`, or where the two listings part."""
+    a, b = normalise(old), normalise(new)
+    report = []
+    for k in sorted(set(a) | set(b)):
+        if k not in a or k not in b:
+            report.append(f"{k}: only in the {'new' if k in b else 'old'} listing")
+        elif a[k] == b[k]:
+            report.append(f"{k}: identical ({len(a[k])} lines)")
+        else:
+            i = next((i for i, (x, y) in enumerate(zip(a[k], b[k])) if x != y), min(len(a[k]), len(b[k])))
+            report.append(f"{k}: DIFFERS at line {i} of {len(a[k])} / {len(b[k])}\n" +
+                          "\n".join(f"    - {x}" for x in a[k][i:i + show]) + "\n" + "\n".join(f"    + {y}" for y in b[k][i:i + show]))
+    return report
+
+
+def device_asm(csrc: Path, include: Path, name: str, dst: Path) -> str:
+    sys.path.insert(0, str(ROOT / PKG))
+    from lcv_hip import build as B
+    flags = [str(include) if f == str(B.INCLUDE) else f for f in B.FLAGS]
+    cmd = [B.HIPCC, *flags, *B.EXTRA.get(name, []), "--cuda-device-only", "-S", str(csrc / name), "-o", str(dst)]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"hipcc failed for {csrc / name}:\n{r.stderr[-2000:]}")
+    return dst.read_text()
+
+
+def main(argv: List[str]) -> int:
+    if not argv:
+        print(__doc__)
+        return 2
+    rev = argv[0]
+    names = argv[1:] or sorted(p.name for p in (ROOT / PKG / "csrc").glob("attn_*.hip"))
+    bad = 0
+    with tempfile.TemporaryDirectory() as tmp:
+        tmp = Path(tmp)
+        tar = subprocess.run(["git", "-C", str(ROOT), "archive", rev, f"{PKG}/csrc", "include"], capture_output=True, check=True)
+        subprocess.run(["tar", "-x", "-C", str(tmp)], input=tar.stdout, check=True)
+
+        def one(name):
+            old = device_asm(tmp / PKG / "csrc", tmp / "include", Path(name).name, tmp / (Path(name).stem + ".old.s"))
+            new = device_asm(ROOT / PKG / "csrc", ROOT / "include", Path(name).name, tmp / (Path(name).stem + ".new.s"))
+            return name, compare(old, new)
+        with ThreadPoolExecutor(max_workers=6) as ex:
+            for name, report in ex.map(one, names):
+                print(f"== {name}")
+                print("\n".join("  " + line for line in report))
+                bad += sum("identical" not in line.split("\n")[0] for line in report)
+    print(f"{'DIFFERENT' if bad else 'all identical'} against {rev}")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
