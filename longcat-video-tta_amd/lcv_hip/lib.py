@@ -73,6 +73,18 @@ _SIGNATURES_LPIPS = {
 }
 LCV_LPIPS_TAP_BLOCKS = 64
 
+# include/lcv_hip_det.h (a header of its own: the fixed-order forms of the atomic reductions); each takes its counterpart's
+# arguments plus `void* ws, int64_t ws_bytes` in front of the stream (qknorm: without dw_slots); every function returns int
+_SIGNATURES_DET = {
+    "lcv_det_adaln_modulate_bwd": [P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, F32, P, P, I64, P],
+    "lcv_det_layernorm_affine_bwd": [P, P, P, P, P, P, I64, I64, F32, P, P, I64, P],
+    "lcv_det_gate_residual_bwd": [P, P, P, P, P, I64, I64, I64, I64, I64, I64, P, I64, P],
+    "lcv_det_qknorm_rope_bwd": [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, F32, F32, P, P, P, I64, P],
+    "lcv_det_linear_f32_smallm_bwd": [P, P, P, P, I64, I64, I64, I, P, I64, P],
+    "lcv_det_grad_norm_clip": [P, I64, I64, I, F32, P, P, P, I64, P],
+}
+LCV_DET_ADALN, LCV_DET_LAYERNORM, LCV_DET_GATE, LCV_DET_QKNORM, LCV_DET_SMALLM, LCV_DET_GRAD_NORM = range(6)
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -124,7 +136,9 @@ def load():
     lib.lcv_attn_bwd_ws_floats.argtypes = [I64, I64, I64, I64]
     lib.lcv_lpips_ws_bytes.restype = c_int64         # likewise
     lib.lcv_lpips_ws_bytes.argtypes = [I64, I64, I64]
-    for name, args in list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()):
+    lib.lcv_det_ws_bytes.restype = c_int64           # likewise
+    lib.lcv_det_ws_bytes.argtypes = [I, I64, I64, I64]
+    for name, args in list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

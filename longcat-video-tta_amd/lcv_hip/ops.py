@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the stream; every op below
 hands raw pointers + sizes to liblcv_hip.so.  Nothing in this module computes
 with torch operators.
 """
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -16,6 +17,31 @@ BF16 = torch.bfloat16
 F32 = torch.float32
 PROFILE = None  # set to a list by bench.py to collect (start, end, flops, Nq, Nk) per attention launch
 PROFILE_BWD = None  # likewise for attention_bwd: (start, end, algorithmic flops = 10 B H Nq Nk D, Nq, Nk) per call
+
+
+# Deterministic mode: the six wrappers whose default kernels finish a sum with fp32 atomics (the AdaLN / LayerNorm / gate /
+# q-k-norm parameter gradients, the small-M linear's input gradient, the gradient-norm clip) call the fixed-order entry points
+# of include/lcv_hip_det.h instead.  Same data gradients bit for bit; the reduced outputs become a pure function of the
+# inputs, so one process gives the same bits for the same seed.  Off unless LCV_DETERMINISTIC=1 (read once, here) or
+# set_deterministic(True).  It covers one process: the order inside RCCL's collectives (sequence parallelism) is not ours.
+_DETERMINISTIC = os.environ.get("LCV_DETERMINISTIC", "") == "1"
+
+
+def set_deterministic(flag: bool) -> None:
+    global _DETERMINISTIC
+    _DETERMINISTIC = bool(flag)
+
+
+def is_deterministic() -> bool:
+    return _DETERMINISTIC
+
+
+def _det_ws(kind: int, device, d0: int, d1: int = 0, d2: int = 0):
+    """(workspace, bytes) for a fixed-order entry point, from the caching allocator (as tn_skinny's)."""
+    n = int(_lib.load().lcv_det_ws_bytes(kind, d0, d1, d2))
+    if n < 0:
+        raise _lib.LcvError(f"lcv_det_ws_bytes: unknown kind {kind}")
+    return torch.empty((max(n, 16) // 4,), dtype=F32, device=device), n
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -346,6 +372,11 @@ def adaln_modulate_bwd(x, mod, dy, shift_idx, scale_idx, T, eps=1e-6, need_dmod=
     dx = torch.empty_like(x)
     dmod = torch.zeros_like(mod) if need_dmod else None
     dres = _res_grad(dres, x, "adaln_modulate_bwd.dres")
+    if _DETERMINISTIC and need_dmod:
+        ws, nb = _det_ws(_lib.LCV_DET_ADALN, x.device, B * T, N // T, C)
+        call("lcv_det_adaln_modulate_bwd", _ptr(x), _ptr(mod), _ptr(dy), _ptr(dx), _ptr(dmod), B, T, N // T, C,
+             mod.shape[-1], shift_idx * C, scale_idx * C, eps, _ptr(dres), _ptr(ws), nb, _stream())
+        return dx, dmod
     call("lcv_adaln_modulate_bwd", _ptr(x), _ptr(mod), _ptr(dy), _ptr(dx), _ptr(dmod), B, T, N // T, C,
          mod.shape[-1], shift_idx * C, scale_idx * C, eps, _ptr(dres), _stream())
     return dx, dmod
@@ -360,6 +391,11 @@ def layernorm_affine_bwd(x, w, dy, eps=1e-6, need_dw=False, dres=None):
     dx = torch.empty_like(x)
     dw = torch.zeros(C, dtype=F32, device=x.device) if need_dw else None
     db = torch.zeros(C, dtype=F32, device=x.device) if need_dw else None
+    if _DETERMINISTIC and need_dw:
+        ws, nb = _det_ws(_lib.LCV_DET_LAYERNORM, x.device, x.numel() // C, C)
+        call("lcv_det_layernorm_affine_bwd", _ptr(x), _ptr(wf), _ptr(dy), _ptr(dx), _ptr(dw), _ptr(db), x.numel() // C, C,
+             eps, _ptr(dres), _ptr(ws), nb, _stream())
+        return dx, dw, db
     call("lcv_layernorm_affine_bwd", _ptr(x), _ptr(wf), _ptr(dy), _ptr(dx), _ptr(dw), _ptr(db), x.numel() // C, C,
          eps, _ptr(dres), _stream())
     return dx, dw, db
@@ -370,6 +406,11 @@ def gate_residual_bwd(y, mod, dout, gate_idx, T, need_dmod=False):
     B, N, C = y.shape
     dy = torch.empty_like(y)
     dmod = torch.zeros_like(mod) if need_dmod else None
+    if _DETERMINISTIC and need_dmod:
+        ws, nb = _det_ws(_lib.LCV_DET_GATE, y.device, B * T, N // T, C)
+        call("lcv_det_gate_residual_bwd", _ptr(y), _ptr(mod), _ptr(dout), _ptr(dy), _ptr(dmod), B, T, N // T, C,
+             mod.shape[-1], gate_idx * C, _ptr(ws), nb, _stream())
+        return dy, dmod
     call("lcv_gate_residual_bwd", _ptr(y), _ptr(mod), _ptr(dout), _ptr(dy), _ptr(dmod), B, T, N // T, C,
          mod.shape[-1], gate_idx * C, _stream())
     return dy, dmod
@@ -389,6 +430,19 @@ def qknorm_rope_bwd(q_in, k_in, dq_out, dk_out, dq_in, dk_in, wq, wk, cs, pos_of
     for t in (q_in, k_in, dq_out, dk_out, dq_in, dk_in):
         if t is not None and (t.stride(3) != 1 or t.stride(2) != D):
             raise _lib.LcvError("qknorm_rope_bwd: (H, D) must be contiguous")
+    if _DETERMINISTIC and (dwq is not None or dwk is not None):
+        # fixed-order form: per-token partials + two ordered sums, added straight into the [128] accumulators
+        for t, nme in ((dwq, "dwq"), (dwk, "dwk")):
+            if t is not None:
+                _req(t, F32, "qknorm_rope_bwd." + nme)
+                if t.numel() != D or not t.is_contiguous():
+                    raise _lib.LcvError(f"qknorm_rope_bwd.{nme}: contiguous fp32 [{D}] expected")
+        ws, nb = _det_ws(_lib.LCV_DET_QKNORM, ref.device, B, N)
+        call("lcv_det_qknorm_rope_bwd", _ptr(q_in), _ptr(k_in), _ptr(dq_out), _ptr(dk_out), _ptr(dq_in), _ptr(dk_in),
+             _ptr(wq), _ptr(wk), _ptr(cs), B, N, H, ref.stride(0), ref.stride(1), go.stride(0), go.stride(1),
+             gk.stride(0), gk.stride(1), gi.stride(0), gi.stride(1), pos_off, eps, q_scale, _ptr(dwq), _ptr(dwk),
+             _ptr(ws), nb, _stream())
+        return
     # the norm-weight gradients are accumulated into DW_SLOTS rows (token % DW_SLOTS) and added up afterwards: one 128-float
     # target for every token of the call would serialise the kernel on those addresses
     slots = DW_SLOTS if (dwq is not None or dwk is not None) else 1
@@ -458,6 +512,11 @@ def linear_f32_smallm_bwd(dy, w, a, act_in=0):
     M, K = a.shape
     N = w.shape[0]
     da = torch.empty((M, K), dtype=F32, device=a.device)
+    if _DETERMINISTIC:
+        ws, nb = _det_ws(_lib.LCV_DET_SMALLM, a.device, M, N, K)
+        call("lcv_det_linear_f32_smallm_bwd", _ptr(dy.contiguous()), _ptr(w.contiguous()), _ptr(a.contiguous()), _ptr(da),
+             M, N, K, act_in, _ptr(ws), nb, _stream())
+        return da
     call("lcv_linear_f32_smallm_bwd", _ptr(dy.contiguous()), _ptr(w.contiguous()), _ptr(a.contiguous()), _ptr(da),
          M, N, K, act_in, _stream())
     return da
@@ -532,13 +591,21 @@ class FusedAdamWClip:
             self._total_chunks = chunk
             self._n_active = len(sel)
             self._desc_key = key
+            # one fp32 partial per chunk for the fixed-order clip (deterministic mode), sized with the table
+            self._det_ws = torch.empty((chunk,), dtype=F32, device=self.params[0].device) if _DETERMINISTIC else None
         self._grads = grads  # keep alive until the launch
         return self._desc
 
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
         d = self._descriptors()
-        call("lcv_grad_norm_clip", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
-             float(max_norm), _ptr(self._ws), _ptr(self._norm_coef), _stream())
+        if _DETERMINISTIC:
+            if getattr(self, "_det_ws", None) is None:      # the mode was switched on after the table was built
+                self._det_ws = torch.empty((self._total_chunks,), dtype=F32, device=self.params[0].device)
+            call("lcv_det_grad_norm_clip", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
+                 float(max_norm), _ptr(self._ws), _ptr(self._norm_coef), _ptr(self._det_ws), self._total_chunks * 4, _stream())
+        else:
+            call("lcv_grad_norm_clip", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
+                 float(max_norm), _ptr(self._ws), _ptr(self._norm_coef), _stream())
         self._have_coef = True
         return self._norm_coef[0]
 

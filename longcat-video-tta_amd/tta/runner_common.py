@@ -65,6 +65,9 @@ def load_components(args, device):
     from longcat_video.modules.longcat_video_dit import LongCatVideoTransformer3DModel
     from longcat_video.modules.scheduling_flow_match_euler_discrete import FlowMatchEulerDiscreteScheduler
     from longcat_video.pipeline_longcat_video import LongCatVideoPipeline
+    from lcv_hip import ops
+    if ops.is_deterministic():   # every runner comes through here once
+        print("  deterministic mode (LCV_DETERMINISTIC=1): fixed-order reductions, same seed -> same bits within one process")
     ck = args.checkpoint_dir
     if ck.startswith("synthetic"):
         kw = {}
