@@ -2,9 +2,7 @@
 // q/k RMSNorm + RoPE, SwiGLU, unpatchify, the fp32 small-M linear, and the skinny token contraction
 // that yields the LoRA dA / dB.  bf16 roundings of the forward are treated as identity (straight-through),
 // as autograd does for the reference's bf16 modules.
-#include "lcv_common.h"
-
-#define ROWNORM_MAXCH 8
+#include "bwd_rows.h"
 
 // ---------------------------------------------------------------------------
 // LayerNorm backward, one wave per row.
@@ -34,88 +32,88 @@ __global__ __launch_bounds__(256) void rownorm_bwd_kernel(
   for (int it = 0; it < rows_per_block; it += 4) {
     const int64_t row = row0 + it + (threadIdx.x >> 6);
     if (row >= rows) continue;
-  const bf16_t* xr = x + row * C;
-  const bf16_t* gr = dy + row * C;
-  const int64_t frame = (MODE == 0) ? row / S : 0;
-  const float* pm = p_mul + frame * mod_stride;
-  float v[ROWNORM_MAXCH][8], g[ROWNORM_MAXCH][8];
-  float sum = 0.f;
+    const bf16_t* xr = x + row * C;
+    const bf16_t* gr = dy + row * C;
+    const int64_t frame = (MODE == 0) ? row / S : 0;
+    const float* pm = p_mul + frame * mod_stride;
+    float v[ROWNORM_MAXCH][8], g[ROWNORM_MAXCH][8];
+    float sum = 0.f;
 #pragma unroll
-  for (int ch = 0; ch < ROWNORM_MAXCH; ++ch) {
-    const int c = (ch * 64 + lane) * 8;
-    if (c < C) {
-      unpack8(*reinterpret_cast<const u16x8*>(xr + c), v[ch]);
-      unpack8(*reinterpret_cast<const u16x8*>(gr + c), g[ch]);
+    for (int ch = 0; ch < ROWNORM_MAXCH; ++ch) {
+      const int c = (ch * 64 + lane) * 8;
+      if (c < C) {
+        unpack8(*reinterpret_cast<const u16x8*>(xr + c), v[ch]);
+        unpack8(*reinterpret_cast<const u16x8*>(gr + c), g[ch]);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) sum += v[ch][i];
-    } else {
+        for (int i = 0; i < 8; ++i) sum += v[ch][i];
+      } else {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) { v[ch][i] = 0.f; g[ch][i] = 0.f; }
-    }
-  }
-  const float mean = wave_sum(sum) / (float)C;
-  float sq = 0.f;
-#pragma unroll
-  for (int ch = 0; ch < ROWNORM_MAXCH; ++ch) {
-    const int c = (ch * 64 + lane) * 8;
-    if (c < C) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float d = v[ch][i] - mean;
-        sq += d * d;
+        for (int i = 0; i < 8; ++i) { v[ch][i] = 0.f; g[ch][i] = 0.f; }
       }
     }
-  }
-  const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
-  float sg = 0.f, sgx = 0.f;
-  const bool in_lds = frame == frame0;      // a workgroup that straddles two frames sends the second one's rows directly
+    const float mean = wave_sum(sum) / (float)C;
+    float sq = 0.f;
 #pragma unroll
-  for (int ch = 0; ch < ROWNORM_MAXCH; ++ch) {
-    const int c = (ch * 64 + lane) * 8;
-    if (c < C) {
-      const f32x4 m0 = *reinterpret_cast<const f32x4*>(pm + c);
-      const f32x4 m1 = *reinterpret_cast<const f32x4*>(pm + c + 4);
+    for (int ch = 0; ch < ROWNORM_MAXCH; ++ch) {
+      const int c = (ch * 64 + lane) * 8;
+      if (c < C) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float xh = (v[ch][i] - mean) * rstd;
-        const float dyv = g[ch][i];
-        if (want_d) {  // parameter / modulation gradients
-          if (in_lds) {
-            atomicAdd(&s_add[c + i], dyv);
-            atomicAdd(&s_mul[c + i], dyv * xh);
-          } else {
-            atomicAdd(d_add + frame * mod_stride + c + i, dyv);
-            atomicAdd(d_mul + frame * mod_stride + c + i, dyv * xh);
-          }
+        for (int i = 0; i < 8; ++i) {
+          const float d = v[ch][i] - mean;
+          sq += d * d;
         }
-        const float mul = ((i < 4) ? m0[i] : m1[i - 4]) + ((MODE == 0) ? 1.0f : 0.0f);
-        const float gg = dyv * mul;
-        v[ch][i] = xh;
-        g[ch][i] = gg;
-        sg += gg;
-        sgx += gg * xh;
       }
     }
-  }
-  const float mg = wave_sum(sg) / (float)C;
-  const float mgx = wave_sum(sgx) / (float)C;
-  bf16_t* dr = dx + row * C;
+    const float rstd = rsqrtf(wave_sum(sq) / (float)C + eps);
+    float sg = 0.f, sgx = 0.f;
+    const bool in_lds = frame == frame0;      // a workgroup that straddles two frames sends the second one's rows directly
 #pragma unroll
-  for (int ch = 0; ch < ROWNORM_MAXCH; ++ch) {
-    const int c = (ch * 64 + lane) * 8;
-    if (c < C) {
-      float o[8];
+    for (int ch = 0; ch < ROWNORM_MAXCH; ++ch) {
+      const int c = (ch * 64 + lane) * 8;
+      if (c < C) {
+        const f32x4 m0 = *reinterpret_cast<const f32x4*>(pm + c);
+        const f32x4 m1 = *reinterpret_cast<const f32x4*>(pm + c + 4);
 #pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = rstd * (g[ch][i] - mg - v[ch][i] * mgx);
-      if (dres) {   // the gradient that reaches x through the residual path of the same block, summed here in fp32
-        float rr[8];
-        unpack8(*reinterpret_cast<const u16x8*>(dres + row * C + c), rr);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] += rr[i];
+        for (int i = 0; i < 8; ++i) {
+          const float xh = (v[ch][i] - mean) * rstd;
+          const float dyv = g[ch][i];
+          if (want_d) {  // parameter / modulation gradients
+            if (in_lds) {
+              atomicAdd(&s_add[c + i], dyv);
+              atomicAdd(&s_mul[c + i], dyv * xh);
+            } else {
+              atomicAdd(d_add + frame * mod_stride + c + i, dyv);
+              atomicAdd(d_mul + frame * mod_stride + c + i, dyv * xh);
+            }
+          }
+          const float mul = ((i < 4) ? m0[i] : m1[i - 4]) + ((MODE == 0) ? 1.0f : 0.0f);
+          const float gg = dyv * mul;
+          v[ch][i] = xh;
+          g[ch][i] = gg;
+          sg += gg;
+          sgx += gg * xh;
+        }
       }
-      *reinterpret_cast<u16x8*>(dr + c) = pack8(o);
     }
-  }
+    const float mg = wave_sum(sg) / (float)C;
+    const float mgx = wave_sum(sgx) / (float)C;
+    bf16_t* dr = dx + row * C;
+#pragma unroll
+    for (int ch = 0; ch < ROWNORM_MAXCH; ++ch) {
+      const int c = (ch * 64 + lane) * 8;
+      if (c < C) {
+        float o[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = rstd * (g[ch][i] - mg - v[ch][i] * mgx);
+        if (dres) {   // the gradient that reaches x through the residual path of the same block, summed here in fp32
+          float rr[8];
+          unpack8(*reinterpret_cast<const u16x8*>(dres + row * C + c), rr);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) o[i] += rr[i];
+        }
+        *reinterpret_cast<u16x8*>(dr + c) = pack8(o);
+      }
+    }
   }
   if (want_d) {
     __syncthreads();
@@ -190,7 +188,6 @@ __global__ __launch_bounds__(256) void gate_residual_bwd_kernel(const bf16_t* __
 // every row, so the per-channel products accumulate in registers and reach memory as one atomic per channel per
 // GATE_RPB rows (flushed early when the rows cross into the next frame).
 #define GATE_RPB 32
-#define GATE_MAXPK 2   // C <= 4096: 512 packets per row over 256 threads
 __global__ __launch_bounds__(256) void gate_residual_bwd_dgate_kernel(const bf16_t* __restrict__ y, const float* __restrict__ gate,
                                                                       const bf16_t* __restrict__ dout, bf16_t* __restrict__ dy,
                                                                       float* __restrict__ dgate, int64_t rows, int cpk, int64_t S,
@@ -220,25 +217,7 @@ __global__ __launch_bounds__(256) void gate_residual_bwd_dgate_kernel(const bf16
     if (row >= rows) break;
     const int64_t frame = row / S;
     if (frame != cur_frame) { flush(cur_frame); cur_frame = frame; }
-#pragma unroll
-    for (int u = 0; u < GATE_MAXPK; ++u) {
-      const int pkc = threadIdx.x + u * 256;
-      if (pkc < cpk) {
-        const int64_t pk = row * cpk + pkc;
-        const int64_t goff = frame * mod_stride + pkc * 8;
-        float d[8], o[8], yf[8];
-        unpack8(*reinterpret_cast<const u16x8*>(dout + pk * 8), d);
-        unpack8(*reinterpret_cast<const u16x8*>(y + pk * 8), yf);
-        const f32x4 g0 = *reinterpret_cast<const f32x4*>(gate + goff);
-        const f32x4 g1 = *reinterpret_cast<const f32x4*>(gate + goff + 4);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          o[i] = d[i] * ((i < 4) ? g0[i] : g1[i - 4]);
-          acc[u][i] = fmaf(d[i], yf[i], acc[u][i]);
-        }
-        *reinterpret_cast<u16x8*>(dy + pk * 8) = pack8(o);
-      }
-    }
+    gate_bwd_row(y, gate, dout, dy, row, frame, cpk, mod_stride, acc);
   }
   flush(cur_frame);
 }
@@ -270,57 +249,6 @@ extern "C" int lcv_gate_residual_bwd(const void* y, const float* mod, const void
 // ---------------------------------------------------------------------------
 // q/k RMSNorm + RoPE backward (weights frozen):  dx = r * (dn - n * mean(dn * n)),  dn = w * rope^T(dout)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void norm_rope_bwd_vec(const bf16_t* xin, const bf16_t* dout, bf16_t* dxin,
-                                                  const float (&w)[8], const float (&cs)[8], bool do_rope,
-                                                  float eps, float out_scale, float (&dwacc)[8], bool want_dw) {
-  float x[8], d[8];
-  unpack8(*reinterpret_cast<const u16x8*>(xin), x);
-  unpack8(*reinterpret_cast<const u16x8*>(dout), d);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) d[i] *= out_scale;  // the forward multiplied its output by out_scale
-  float ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
-  ss += __shfl_xor(ss, 8, 64);
-  ss += __shfl_xor(ss, 4, 64);
-  ss += __shfl_xor(ss, 2, 64);
-  ss += __shfl_xor(ss, 1, 64);
-  const float r = rsqrtf(ss * (1.0f / 128.0f) + eps);
-  float dn[8], n[8];
-  float dot = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float d0 = d[2 * i], d1 = d[2 * i + 1];
-    if (do_rope) {
-      const float c = cs[2 * i], s = cs[2 * i + 1];
-      const float t0 = d0 * c + d1 * s;
-      const float t1 = d1 * c - d0 * s;
-      d0 = t0;
-      d1 = t1;
-    }
-    dn[2 * i] = d0 * w[2 * i];
-    dn[2 * i + 1] = d1 * w[2 * i + 1];
-    if (want_dw) {  // y = rope(n * w): dw += rope^T(dout) * n (norm-weight tuning, run_norm_tune_tta.py:87-98)
-      dwacc[2 * i] += d0 * (x[2 * i] * r);
-      dwacc[2 * i + 1] += d1 * (x[2 * i + 1] * r);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    n[i] = x[i] * r;
-    dot += dn[i] * n[i];
-  }
-  dot += __shfl_xor(dot, 8, 64);
-  dot += __shfl_xor(dot, 4, 64);
-  dot += __shfl_xor(dot, 2, 64);
-  dot += __shfl_xor(dot, 1, 64);
-  dot *= (1.0f / 128.0f);
-  float o[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = r * (dn[i] - n[i] * dot);
-  *reinterpret_cast<u16x8*>(dxin) = pack8(o);
-}
-
 __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(
     const bf16_t* __restrict__ q_in, const bf16_t* __restrict__ k_in, const bf16_t* __restrict__ dq_out,
     const bf16_t* __restrict__ dk_out, bf16_t* __restrict__ dq_in, bf16_t* __restrict__ dk_in,
@@ -330,48 +258,14 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_kernel(
     int dw_slots) {
   __shared__ float s_dw[2][4][128];
   const int64_t n = blockIdx.x, b = blockIdx.y;
-  const int sub = threadIdx.x & 15;
-  const int hl = threadIdx.x >> 4;
-  float cs[8] = {1, 0, 1, 0, 1, 0, 1, 0};
-  const bool do_rope = cs_tab != nullptr;
-  if (do_rope) {
-    const float* p = cs_tab + ((pos_off + n) * 64 + sub * 4) * 2;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p);
-    const f32x4 c = *reinterpret_cast<const f32x4*>(p + 4);
-    cs[0] = a[0]; cs[1] = a[1]; cs[2] = a[2]; cs[3] = a[3];
-    cs[4] = c[0]; cs[5] = c[1]; cs[6] = c[2]; cs[7] = c[3];
-  }
-  float wqf[8], wkf[8];
-  unpack8(*reinterpret_cast<const u16x8*>(wq + sub * 8), wqf);
-  unpack8(*reinterpret_cast<const u16x8*>(wk + sub * 8), wkf);
   float dwq_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dwk_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int h0 = 0; h0 < H; h0 += 16) {
-    const int h = h0 + hl;
-    if (h >= H) continue;
-    const int64_t off = (int64_t)h * 128 + sub * 8;
-    if (q_in)
-      norm_rope_bwd_vec(q_in + b * in_sb + n * in_sn + off, dq_out + b * q_sb + n * q_sn + off,
-                        dq_in + b * din_sb + n * din_sn + off, wqf, cs, do_rope, eps, q_scale, dwq_acc, dwq != nullptr);
-    if (k_in)
-      norm_rope_bwd_vec(k_in + b * in_sb + n * in_sn + off, dk_out + b * kv_sb + n * kv_sn + off,
-                        dk_in + b * din_sb + n * din_sn + off, wkf, cs, do_rope, eps, 1.0f, dwk_acc, dwk != nullptr);
-  }
+  qknorm_rope_bwd_token(q_in, k_in, dq_out, dk_out, dq_in, dk_in, wq, wk, cs_tab, H, in_sb, in_sn, q_sb, q_sn, kv_sb, kv_sn,
+                        din_sb, din_sn, pos_off, eps, q_scale, n, b, dwq != nullptr, dwk != nullptr, dwq_acc, dwk_acc);
   // norm-weight gradients (only when asked for): sum over the wave's 4 heads-in-flight, then over the 4 waves through
   // LDS, then ONE atomic per dim per workgroup into accumulator row (token % dw_slots) — every token of every layer
   // call lands on the same 128 floats otherwise, and the kernel becomes a queue on those addresses
   if (dwq != nullptr || dwk != nullptr) {
-    const int wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float a = dwq_acc[i], c = dwk_acc[i];
-      a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-      c += __shfl_xor(c, 16, 64); c += __shfl_xor(c, 32, 64);
-      if ((threadIdx.x & 63) < 16) {
-        s_dw[0][wave][sub * 8 + i] = a;
-        s_dw[1][wave][sub * 8 + i] = c;
-      }
-    }
-    __syncthreads();
+    qknorm_dw_stage(dwq_acc, dwk_acc, s_dw);
     const int slot = (int)((n + b * gridDim.x) % dw_slots);
     if (threadIdx.x < 128) {
       const int d = threadIdx.x;
@@ -579,6 +473,10 @@ __global__ __launch_bounds__(256) void silu_grad_kernel(const float* __restrict_
   }
 }
 
+void silu_grad_launch(const float* a, float* da, int64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(silu_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, da, n);
+}
+
 extern "C" int lcv_linear_f32_smallm_bwd(const float* dy, const void* w, const float* a, float* da, int64_t M,
                                          int64_t N, int64_t K, int act_in, void* stream) {
   LCV_CHECK_ARG(dy && w && a && da, "linear_f32_smallm_bwd: null pointer");
@@ -596,8 +494,7 @@ extern "C" int lcv_linear_f32_smallm_bwd(const float* dy, const void* w, const f
     LCV_LAUNCH_CHECK("linear_f32_smallm_bwd");
   }
   if (act_in == 1) {
-    const int64_t n = M * K;
-    hipLaunchKernelGGL(silu_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, da, n);
+    silu_grad_launch(a, da, M * K, s);
     LCV_LAUNCH_CHECK("silu_grad");
   }
   return LCV_OK;
@@ -714,16 +611,21 @@ __global__ __launch_bounds__(256) void tn_skinny_reduce_kernel(const float* __re
   *reinterpret_cast<f32x4*>(out + i) = acc * scale;
 }
 
+// rows per workgroup: ~32 row groups per call; ~64 when there are few column blocks (K <= 4096: 8), so that two workgroups share a CU
+static int64_t tn_skinny_rpb(int64_t M, int64_t K) {
+  const int64_t groups = (K + 511) / 512 <= 8 ? 64 : 32;
+  int64_t rpb = ((M + groups - 1) / groups + 31) / 32 * 32;
+  if (rpb > TN_MAXROWS) rpb = TN_MAXROWS;
+  if (rpb < 64) rpb = 64;
+  return rpb;
+}
+
 extern "C" int lcv_tn_skinny(const void* g, const void* x, float* out, int64_t M, int64_t K, int64_t R,
                              int64_t Rpad, int64_t ldx, float scale, float* ws, int64_t ws_bytes, void* stream) {
   LCV_CHECK_ARG(g && x && out, "tn_skinny: null pointer");
   LCV_CHECK_ARG(K % 8 == 0 && ldx % 8 == 0 && R >= 1 && R <= Rpad, "tn_skinny: bad shape");
   if (M == 0) return LCV_OK;
-  // ~32 row groups per call; ~64 when there are few column blocks (K <= 4096: 8), so that two workgroups share a CU
-  const int64_t groups = (K + 511) / 512 <= 8 ? 64 : 32;
-  int64_t rpb = ((M + groups - 1) / groups + 31) / 32 * 32;
-  if (rpb > TN_MAXROWS) rpb = TN_MAXROWS;
-  if (rpb < 64) rpb = 64;
+  const int64_t rpb = tn_skinny_rpb(M, K);
   const dim3 grid((unsigned)((K + 511) / 512), (unsigned)((M + rpb - 1) / rpb));
   // with a workspace of >= lcv_tn_skinny_ws_bytes(M, K, R): per-group partial sums + a fixed-order reduction (`out` need not
   // be zeroed and is overwritten); without: fp32 atomics into a zero-filled `out`
@@ -746,9 +648,6 @@ extern "C" int lcv_tn_skinny(const void* g, const void* x, float* out, int64_t M
 }
 
 extern "C" int64_t lcv_tn_skinny_ws_bytes(int64_t M, int64_t K, int64_t R) {
-  const int64_t groups = (K + 511) / 512 <= 8 ? 64 : 32;
-  int64_t rpb = ((M + groups - 1) / groups + 31) / 32 * 32;
-  if (rpb > TN_MAXROWS) rpb = TN_MAXROWS;
-  if (rpb < 64) rpb = 64;
+  const int64_t rpb = tn_skinny_rpb(M, K);
   return ((M + rpb - 1) / rpb) * R * K * 4;
 }

@@ -12,22 +12,8 @@
 //   p  = bf16(p + (-lr/(1-b1^t)) * (m / d))               _foreach_addcdiv_
 // For fp32 parameters (the delta methods) the same sequence runs without the bf16 roundings.
 // Algorithmic bytes: 14 B / parameter (bf16: p, g, m, v read; p, m, v written).
-#include "lcv_common.h"
+#include "optim_common.h"
 #include <math.h>
-
-static constexpr int CHUNK = 2048;  // elements per workgroup (256 threads x 8)
-// per-tensor sum-of-squares accumulators: chunk c of a tensor adds into slot c % NORM_SLOTS of that tensor's row, the
-// coefficient kernel adds the row up.  One slot per tensor makes a 45 M-element weight (22 000 chunks) a queue on one address.
-static constexpr int NORM_SLOTS = 64;
-
-__device__ __forceinline__ int find_tensor(const lcv_adam_tensor* t, int n, int64_t chunk) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (t[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 template <bool F32>
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const lcv_adam_tensor* __restrict__ tensors, int n,
@@ -35,28 +21,8 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const lcv_adam_tensor* 
   const int ti = find_tensor(tensors, n, blockIdx.x);
   const lcv_adam_tensor t = tensors[ti];
   const int64_t chunk = (int64_t)blockIdx.x - t.first_chunk;
-  const int64_t base = chunk * CHUNK + threadIdx.x * 8;
-  float acc = 0.f;
-  if (!F32 && base + 8 <= t.numel && (((uintptr_t)t.grad) & 15) == 0) {      // whole 16-byte packet
-    float g[8];
-    unpack8(*reinterpret_cast<const u16x8*>((const bf16_t*)t.grad + base), g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc = fmaf(g[e], g[e], acc);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int64_t i = base + e;
-      if (i < t.numel) {
-        const float g = F32 ? ((const float*)t.grad)[i] : bf2f(((const bf16_t*)t.grad)[i]);
-        acc += g * g;
-      }
-    }
-  }
-  __shared__ float part[4];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(per_tensor + (int64_t)ti * NORM_SLOTS + (chunk % NORM_SLOTS), part[0] + part[1] + part[2] + part[3]);
+  const float sumsq = grad_chunk_sumsq<F32>(t, chunk);
+  if (threadIdx.x == 0) atomicAdd(per_tensor + (int64_t)ti * NORM_SLOTS + (chunk % NORM_SLOTS), sumsq);
 }
 
 // total norm exactly as clip_grad_norm_ composes it: per-tensor norms (rounded to the grad dtype), then the
@@ -88,6 +54,11 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
     out[0] = total;
     out[1] = fminf(coef, 1.0f);
   }
+}
+
+void clip_coef_launch(const float* per_tensor, int n, float max_norm, float* out, bool f32, hipStream_t s) {
+  if (f32) hipLaunchKernelGGL(clip_coef_kernel<true>, dim3(1), dim3(256), 0, s, per_tensor, n, max_norm, out);
+  else hipLaunchKernelGGL(clip_coef_kernel<false>, dim3(1), dim3(256), 0, s, per_tensor, n, max_norm, out);
 }
 
 struct AdamScalars {
@@ -142,15 +113,12 @@ extern "C" int lcv_grad_norm_clip(const lcv_adam_tensor* tensors, int64_t n_tens
     lcv_set_error("grad_norm_clip: memset failed");
     return LCV_EDEVICE;
   }
-  if (param_f32) {
+  if (param_f32)
     hipLaunchKernelGGL(grad_sumsq_kernel<true>, dim3((unsigned)total_chunks), dim3(256), 0, s, tensors, (int)n_tensors, per_tensor_ws);
-    LCV_LAUNCH_CHECK("grad_sumsq");
-    hipLaunchKernelGGL(clip_coef_kernel<true>, dim3(1), dim3(256), 0, s, per_tensor_ws, (int)n_tensors, max_norm, norm_coef_out);
-  } else {
+  else
     hipLaunchKernelGGL(grad_sumsq_kernel<false>, dim3((unsigned)total_chunks), dim3(256), 0, s, tensors, (int)n_tensors, per_tensor_ws);
-    LCV_LAUNCH_CHECK("grad_sumsq");
-    hipLaunchKernelGGL(clip_coef_kernel<false>, dim3(1), dim3(256), 0, s, per_tensor_ws, (int)n_tensors, max_norm, norm_coef_out);
-  }
+  LCV_LAUNCH_CHECK("grad_sumsq");
+  clip_coef_launch(per_tensor_ws, (int)n_tensors, max_norm, norm_coef_out, param_f32 != 0, s);
   LCV_LAUNCH_CHECK("clip_coef");
   return LCV_OK;
 }

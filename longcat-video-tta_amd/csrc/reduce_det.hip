@@ -2,9 +2,13 @@
 // (include/lcv_hip_det.h): the AdaLN / LayerNorm parameter gradients, dgate, the q/k norm-weight gradients, the small-M
 // linear's input gradient and the per-tensor sums of squares of the gradient-norm clip.
 //
-// Row math: each kernel below is its counterpart of elementwise_bwd.hip / optim.hip operation for operation (same loads,
-// same wave_sum use, same dres add), so dx / dy / dq_in / dk_in carry the same bits.  Only where a sum leaves the thread
-// differs.  Nothing here uses a float read-modify-write that another thread can interleave with, in global memory or LDS.
+// Row math: the gate, q/k-norm and grad-norm kernels below call the functions their counterparts of elementwise_bwd.hip /
+// optim.hip call (bwd_rows.h: gate_bwd_row, qknorm_rope_bwd_token / qknorm_dw_stage; optim_common.h: grad_chunk_sumsq), and
+// the SiLU derivative and the clip coefficient ARE the default kernels (silu_grad_launch, clip_coef_launch).  The rownorm and
+// small-M kernels restate their counterparts operation for operation (same loads, same wave_sum use, same dres add): shared
+// functions cost those four a measurable ~1 % (profiles/bwd_rows.md).  Either way dx / dy / dq_in / dk_in carry the same
+// bits, and only where a sum leaves the thread differs.
+// Nothing here uses a float read-modify-write that another thread can interleave with, in global memory or LDS.
 //
 // Summation order (the output is a pure function of the inputs and the shapes):
 //   rownorm (AdaLN, LayerNorm affine)  a workgroup owns DET_ROWNORM_RPB consecutive rows OF ONE FRAME; wave w takes rows
@@ -19,13 +23,12 @@
 //   small-M linear   per 256-row slab of W as in the default kernel; workspace [slabs][M][K]; colsum over slabs in index order.
 //   grad norm  one partial per 2 048-element chunk (fma chain per thread, wave_sum, w0 + w1 + w2 + w3); per tensor one
 //       workgroup: thread t adds chunks t, t+256, ... in that order, then wave_sum and w0 + w1 + w2 + w3.
-#include "lcv_common.h"
+#include "bwd_rows.h"
+#include "optim_common.h"
 #include "../../include/lcv_hip_det.h"
 
-#define ROWNORM_MAXCH 8
 #define DET_ROWNORM_RPB 64   // rows per workgroup: 2*C floats of workspace per 64 rows of C bf16 = 1/16 of x's bytes
 #define DET_GATE_RPB 32      // C floats per 32 rows = 1/16 of y's bytes
-#define DET_GATE_MAXPK 2     // C <= 4096: 512 packets per row over 256 threads
 #define DET_QK_GROUP 160     // ~sqrt(25 200): tokens per first-level group of the norm-weight sums
 
 // out[g * out_gstride + w] (+)= sum over p in [0, np) of part[(g * P + p) * pstride + w], p ascending, np = min(P, total - g*P).
@@ -272,35 +275,15 @@ __global__ __launch_bounds__(256) void gate_residual_bwd_det_kernel(const bf16_t
   const int64_t frame = blockIdx.x / bpf;
   const int64_t lo = frame * S + (int64_t)(blockIdx.x - frame * bpf) * DET_GATE_RPB;
   const int64_t hi = (lo + DET_GATE_RPB < (frame + 1) * S) ? lo + DET_GATE_RPB : (frame + 1) * S;
-  float acc[DET_GATE_MAXPK][8];
+  float acc[GATE_MAXPK][8];
 #pragma unroll
-  for (int u = 0; u < DET_GATE_MAXPK; ++u)
+  for (int u = 0; u < GATE_MAXPK; ++u)
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[u][i] = 0.f;
-  for (int64_t row = lo; row < hi; ++row) {
-#pragma unroll
-    for (int u = 0; u < DET_GATE_MAXPK; ++u) {
-      const int pkc = threadIdx.x + u * 256;
-      if (pkc < cpk) {
-        const int64_t pk = row * cpk + pkc;
-        const int64_t goff = frame * mod_stride + pkc * 8;
-        float d[8], o[8], yf[8];
-        unpack8(*reinterpret_cast<const u16x8*>(dout + pk * 8), d);
-        unpack8(*reinterpret_cast<const u16x8*>(y + pk * 8), yf);
-        const f32x4 g0 = *reinterpret_cast<const f32x4*>(gate + goff);
-        const f32x4 g1 = *reinterpret_cast<const f32x4*>(gate + goff + 4);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          o[i] = d[i] * ((i < 4) ? g0[i] : g1[i - 4]);
-          acc[u][i] = fmaf(d[i], yf[i], acc[u][i]);
-        }
-        *reinterpret_cast<u16x8*>(dy + pk * 8) = pack8(o);
-      }
-    }
-  }
+  for (int64_t row = lo; row < hi; ++row) gate_bwd_row(y, gate, dout, dy, row, frame, cpk, mod_stride, acc);
   float* prow = part + (int64_t)blockIdx.x * cpk * 8;
 #pragma unroll
-  for (int u = 0; u < DET_GATE_MAXPK; ++u) {
+  for (int u = 0; u < GATE_MAXPK; ++u) {
     const int pkc = threadIdx.x + u * 256;
     if (pkc < cpk) {
       *reinterpret_cast<f32x4*>(prow + pkc * 8) = f32x4{acc[u][0], acc[u][1], acc[u][2], acc[u][3]};
@@ -315,8 +298,8 @@ extern "C" int lcv_det_gate_residual_bwd(const void* y, const float* mod, const 
   if (!dmod) return lcv_gate_residual_bwd(y, mod, dout, dy, nullptr, B, T, S, C, mod_stride, gate_off, stream);
   LCV_CHECK_ARG(y && mod && dout && dy, "det_gate_residual_bwd: null pointer");
   LCV_CHECK_ARG(C % 8 == 0 && gate_off % 4 == 0 && mod_stride % 4 == 0, "det_gate_residual_bwd: bad alignment");
-  LCV_CHECK_ARG(C / 8 <= 256 * DET_GATE_MAXPK, "det_gate_residual_bwd: C=%ld is above the %d channels the fixed-order form takes",
-                (long)C, 256 * DET_GATE_MAXPK * 8);
+  LCV_CHECK_ARG(C / 8 <= 256 * GATE_MAXPK, "det_gate_residual_bwd: C=%ld is above the %d channels the fixed-order form takes",
+                (long)C, 256 * GATE_MAXPK * 8);
   const int64_t frames = B * T;
   if (frames * S * C == 0) return LCV_OK;
   const int64_t bpf = (S + DET_GATE_RPB - 1) / DET_GATE_RPB;
@@ -335,57 +318,6 @@ extern "C" int lcv_det_gate_residual_bwd(const void* y, const float* mod, const 
 // ---------------------------------------------------------------------------
 // q/k RMSNorm + RoPE backward:  dx = r * (dn - n * mean(dn * n)),  dn = w * rope^T(dout)   (qknorm_rope_bwd_kernel)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void norm_rope_bwd_vec(const bf16_t* xin, const bf16_t* dout, bf16_t* dxin,
-                                                  const float (&w)[8], const float (&cs)[8], bool do_rope,
-                                                  float eps, float out_scale, float (&dwacc)[8], bool want_dw) {
-  float x[8], d[8];
-  unpack8(*reinterpret_cast<const u16x8*>(xin), x);
-  unpack8(*reinterpret_cast<const u16x8*>(dout), d);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) d[i] *= out_scale;  // the forward multiplied its output by out_scale
-  float ss = 0.f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
-  ss += __shfl_xor(ss, 8, 64);
-  ss += __shfl_xor(ss, 4, 64);
-  ss += __shfl_xor(ss, 2, 64);
-  ss += __shfl_xor(ss, 1, 64);
-  const float r = rsqrtf(ss * (1.0f / 128.0f) + eps);
-  float dn[8], n[8];
-  float dot = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float d0 = d[2 * i], d1 = d[2 * i + 1];
-    if (do_rope) {
-      const float c = cs[2 * i], s = cs[2 * i + 1];
-      const float t0 = d0 * c + d1 * s;
-      const float t1 = d1 * c - d0 * s;
-      d0 = t0;
-      d1 = t1;
-    }
-    dn[2 * i] = d0 * w[2 * i];
-    dn[2 * i + 1] = d1 * w[2 * i + 1];
-    if (want_dw) {  // y = rope(n * w): dw += rope^T(dout) * n
-      dwacc[2 * i] += d0 * (x[2 * i] * r);
-      dwacc[2 * i + 1] += d1 * (x[2 * i + 1] * r);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    n[i] = x[i] * r;
-    dot += dn[i] * n[i];
-  }
-  dot += __shfl_xor(dot, 8, 64);
-  dot += __shfl_xor(dot, 4, 64);
-  dot += __shfl_xor(dot, 2, 64);
-  dot += __shfl_xor(dot, 1, 64);
-  dot *= (1.0f / 128.0f);
-  float o[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) o[i] = r * (dn[i] - n[i] * dot);
-  *reinterpret_cast<u16x8*>(dxin) = pack8(o);
-}
-
 __global__ __launch_bounds__(256) void qknorm_rope_bwd_det_kernel(
     const bf16_t* __restrict__ q_in, const bf16_t* __restrict__ k_in, const bf16_t* __restrict__ dq_out,
     const bf16_t* __restrict__ dk_out, bf16_t* __restrict__ dq_in, bf16_t* __restrict__ dk_in,
@@ -394,46 +326,12 @@ __global__ __launch_bounds__(256) void qknorm_rope_bwd_det_kernel(
     int64_t din_sn, int64_t pos_off, float eps, float q_scale, bool want_dwq, bool want_dwk, float* __restrict__ part) {
   __shared__ float s_dw[2][4][128];
   const int64_t n = blockIdx.x, b = blockIdx.y;
-  const int sub = threadIdx.x & 15;
-  const int hl = threadIdx.x >> 4;
-  float cs[8] = {1, 0, 1, 0, 1, 0, 1, 0};
-  const bool do_rope = cs_tab != nullptr;
-  if (do_rope) {
-    const float* p = cs_tab + ((pos_off + n) * 64 + sub * 4) * 2;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(p);
-    const f32x4 c = *reinterpret_cast<const f32x4*>(p + 4);
-    cs[0] = a[0]; cs[1] = a[1]; cs[2] = a[2]; cs[3] = a[3];
-    cs[4] = c[0]; cs[5] = c[1]; cs[6] = c[2]; cs[7] = c[3];
-  }
-  float wqf[8], wkf[8];
-  unpack8(*reinterpret_cast<const u16x8*>(wq + sub * 8), wqf);
-  unpack8(*reinterpret_cast<const u16x8*>(wk + sub * 8), wkf);
   float dwq_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dwk_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int h0 = 0; h0 < H; h0 += 16) {
-    const int h = h0 + hl;
-    if (h >= H) continue;
-    const int64_t off = (int64_t)h * 128 + sub * 8;
-    if (q_in)
-      norm_rope_bwd_vec(q_in + b * in_sb + n * in_sn + off, dq_out + b * q_sb + n * q_sn + off,
-                        dq_in + b * din_sb + n * din_sn + off, wqf, cs, do_rope, eps, q_scale, dwq_acc, want_dwq);
-    if (k_in)
-      norm_rope_bwd_vec(k_in + b * in_sb + n * in_sn + off, dk_out + b * kv_sb + n * kv_sn + off,
-                        dk_in + b * din_sb + n * din_sn + off, wkf, cs, do_rope, eps, 1.0f, dwk_acc, want_dwk);
-  }
+  qknorm_rope_bwd_token(q_in, k_in, dq_out, dk_out, dq_in, dk_in, wq, wk, cs_tab, H, in_sb, in_sn, q_sb, q_sn, kv_sb, kv_sn,
+                        din_sb, din_sn, pos_off, eps, q_scale, n, b, want_dwq, want_dwk, dwq_acc, dwk_acc);
   // this token's norm-weight gradients: the wave's 4 heads-in-flight by shuffles, the 4 waves through LDS in wave order,
   // then the token's own row of the workspace (dwq | dwk); a side that was not asked for or has no input is written as zeros
-  const int wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    float a = dwq_acc[i], c = dwk_acc[i];
-    a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-    c += __shfl_xor(c, 16, 64); c += __shfl_xor(c, 32, 64);
-    if ((threadIdx.x & 63) < 16) {
-      s_dw[0][wave][sub * 8 + i] = a;
-      s_dw[1][wave][sub * 8 + i] = c;
-    }
-  }
-  __syncthreads();
+  qknorm_dw_stage(dwq_acc, dwk_acc, s_dw);
   float* prow = part + (b * gridDim.x + n) * 256;
   if (threadIdx.x < 128) {
     const int d = threadIdx.x;
@@ -525,15 +423,6 @@ __global__ __launch_bounds__(256) void linear_f32_smallm_bwd_det_kernel(const fl
   }
 }
 
-__global__ __launch_bounds__(256) void det_silu_grad_kernel(const float* __restrict__ a, float* __restrict__ da, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) {
-    const float x = a[i];
-    const float sig = 1.0f / (1.0f + __expf(-x));
-    da[i] *= sig * (1.0f + x * (1.0f - sig));
-  }
-}
-
 extern "C" int lcv_det_linear_f32_smallm_bwd(const float* dy, const void* w, const float* a, float* da, int64_t M,
                                              int64_t N, int64_t K, int act_in, void* ws, int64_t ws_bytes, void* stream) {
   LCV_CHECK_ARG(dy && w && a && da, "det_linear_f32_smallm_bwd: null pointer");
@@ -556,8 +445,7 @@ extern "C" int lcv_det_linear_f32_smallm_bwd(const float* dy, const void* w, con
   int rc = det_colsum(part, slabs, slabs, M * K, M * K, da, 0, 0, s, "det_linear_f32_smallm_bwd: slabs");
   if (rc != LCV_OK) return rc;
   if (act_in == 1) {
-    const int64_t n = M * K;
-    hipLaunchKernelGGL(det_silu_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a, da, n);
+    silu_grad_launch(a, da, M * K, s);
     LCV_LAUNCH_CHECK("det_silu_grad");
   }
   return LCV_OK;
@@ -566,46 +454,14 @@ extern "C" int lcv_det_linear_f32_smallm_bwd(const float* dy, const void* w, con
 // ---------------------------------------------------------------------------
 // gradient-norm clip (grad_sumsq_kernel / clip_coef_kernel of optim.hip): one partial per chunk, one workgroup per tensor
 // ---------------------------------------------------------------------------
-static constexpr int CHUNK = 2048;       // elements per workgroup (256 threads x 8), as the optimizer kernels
-static constexpr int NORM_SLOTS = 64;    // width of a tensor's row of per_tensor_ws
-
-__device__ __forceinline__ int find_tensor(const lcv_adam_tensor* t, int n, int64_t chunk) {
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (t[mid].first_chunk <= chunk) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 template <bool F32>
 __global__ __launch_bounds__(256) void grad_sumsq_det_kernel(const lcv_adam_tensor* __restrict__ tensors, int n,
                                                              float* __restrict__ chunk_part) {
   const int ti = find_tensor(tensors, n, blockIdx.x);
   const lcv_adam_tensor t = tensors[ti];
   const int64_t chunk = (int64_t)blockIdx.x - t.first_chunk;
-  const int64_t base = chunk * CHUNK + threadIdx.x * 8;
-  float acc = 0.f;
-  if (!F32 && base + 8 <= t.numel && (((uintptr_t)t.grad) & 15) == 0) {      // whole 16-byte packet
-    float g[8];
-    unpack8(*reinterpret_cast<const u16x8*>((const bf16_t*)t.grad + base), g);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc = fmaf(g[e], g[e], acc);
-  } else {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int64_t i = base + e;
-      if (i < t.numel) {
-        const float g = F32 ? ((const float*)t.grad)[i] : bf2f(((const bf16_t*)t.grad)[i]);
-        acc += g * g;
-      }
-    }
-  }
-  __shared__ float part[4];
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) chunk_part[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+  const float sumsq = grad_chunk_sumsq<F32>(t, chunk);
+  if (threadIdx.x == 0) chunk_part[blockIdx.x] = sumsq;
 }
 
 // tensor blockIdx.x: its chunks' partials in a block-wide fixed tree; the sum goes to slot 0 of the tensor's row, zeros to the rest
@@ -625,36 +481,6 @@ __global__ __launch_bounds__(256) void tensor_sumsq_det_kernel(const lcv_adam_te
     per_tensor[(int64_t)blockIdx.x * NORM_SLOTS + threadIdx.x] = threadIdx.x == 0 ? part[0] + part[1] + part[2] + part[3] : 0.f;
 }
 
-// total norm exactly as clip_grad_norm_ composes it (clip_coef_kernel of optim.hip, unchanged arithmetic)
-template <bool F32>
-__global__ __launch_bounds__(256) void clip_coef_det_kernel(const float* __restrict__ per_tensor, int n, float max_norm,
-                                                            float* __restrict__ out) {
-  __shared__ float part[4];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    float sumsq = 0.f;
-    for (int k = 0; k < NORM_SLOTS; ++k) sumsq += per_tensor[(int64_t)i * NORM_SLOTS + k];
-    float nrm = sqrtf(sumsq);
-    if (!F32) nrm = bfround(nrm);
-    acc += nrm * nrm;
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float total = sqrtf(part[0] + part[1] + part[2] + part[3]);
-    float coef;
-    if (F32) {
-      coef = max_norm / (total + 1e-6f);
-    } else {
-      total = bfround(total);
-      coef = bfround(max_norm / bfround(total + 1e-6f));
-    }
-    out[0] = total;
-    out[1] = fminf(coef, 1.0f);
-  }
-}
-
 extern "C" int lcv_det_grad_norm_clip(const lcv_adam_tensor* tensors, int64_t n_tensors, int64_t total_chunks,
                                       int param_f32, float max_norm, float* per_tensor_ws, float* norm_coef_out, void* ws,
                                       int64_t ws_bytes, void* stream) {
@@ -672,10 +498,7 @@ extern "C" int lcv_det_grad_norm_clip(const lcv_adam_tensor* tensors, int64_t n_
   LCV_LAUNCH_CHECK("det_grad_sumsq");
   hipLaunchKernelGGL(tensor_sumsq_det_kernel, dim3((unsigned)n_tensors), dim3(256), 0, s, tensors, chunk_part, per_tensor_ws);
   LCV_LAUNCH_CHECK("det_tensor_sumsq");
-  if (param_f32)
-    hipLaunchKernelGGL(clip_coef_det_kernel<true>, dim3(1), dim3(256), 0, s, per_tensor_ws, (int)n_tensors, max_norm, norm_coef_out);
-  else
-    hipLaunchKernelGGL(clip_coef_det_kernel<false>, dim3(1), dim3(256), 0, s, per_tensor_ws, (int)n_tensors, max_norm, norm_coef_out);
+  clip_coef_launch(per_tensor_ws, (int)n_tensors, max_norm, norm_coef_out, param_f32 != 0, s);   // clip_coef_kernel of optim.hip
   LCV_LAUNCH_CHECK("det_clip_coef");
   return LCV_OK;
 }
