@@ -385,13 +385,8 @@ static int launch_conv_rows(GemmParams& p, hipStream_t s) {
   const int tiles_per_row = (p.cv_W + Cfg::BM - 1) / Cfg::BM;
   const int64_t n_tiles = (p.M / p.cv_W) * tiles_per_row;
   LCV_CHECK_ARG(n_tiles < (int64_t(1) << 31), "conv3d: %ld row tiles", (long)n_tiles);
-  auto kern = conv_rows_kernel<WM, WN, TM, TN, EPI>;
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS_BYTES) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("conv3d: cannot raise dynamic LDS to %d", Cfg::LDS_BYTES);
-      return LCV_EDEVICE;
-  }
+  constexpr auto kern = conv_rows_kernel<WM, WN, TM, TN, EPI>;
+  if (int rc = raise_dynamic_lds<kern>("conv3d", Cfg::LDS_BYTES)) return rc;
   // one workgroup per CU, a multiple of 8 (XCDs); fewer when there are fewer tiles
   int grid = 256;
   { const char* e = lcv_knob("LCV_CONV_ROWS_GRID"); if (e && atoi(e) >= 8) grid = atoi(e) / 8 * 8; }

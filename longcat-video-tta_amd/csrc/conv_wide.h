@@ -149,18 +149,11 @@ __global__ __launch_bounds__(1024) void conv_wide_kernel(const GemmParams p) {
 
 template <int EPI>
 static int launch_conv_wide(GemmParams& p, hipStream_t s) {
-  p.tiles_m = (int)((p.M + 255) / 256);
-  p.group_m = 8;
-  p.tiles_n = (int)(p.N / 192);
+  const int ntiles = set_tile_grid(p, 256, 192, 8);
   const size_t lds = 2 * (256 + 192) * 128;
-  auto kern = conv_wide_kernel<EPI>;
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("conv3d: cannot raise dynamic LDS to %zu", lds);
-      return LCV_EDEVICE;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(1024), lds, s, p);   // 8 MFMA + 8 loader waves
+  constexpr auto kern = conv_wide_kernel<EPI>;
+  if (int rc = raise_dynamic_lds<kern>("conv3d", lds)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(1024), lds, s, p);   // 8 MFMA + 8 loader waves
   LCV_LAUNCH_CHECK("conv_wide");
   return LCV_OK;
 }

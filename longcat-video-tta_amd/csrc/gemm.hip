@@ -209,7 +209,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p,
   }
 }
 
-template <int BM, int BN, int WR, int WC, int EPI, bool CONV>
+template <int BM, int BN, int WR, int WC, int EPI>
 __global__ __launch_bounds__(WR* WC * 64) void gemm_nt_kernel(const GemmParams p) {
   using Cfg = GemmCfg<BM, BN, WR, WC>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -229,7 +229,6 @@ __global__ __launch_bounds__(WR* WC * 64) void gemm_nt_kernel(const GemmParams p
   const int ld_row = lane >> 3, ld_slot = lane & 7;
   int64_t a_row[Cfg::IA], b_row[Cfg::IB];
   int a_sw[Cfg::IA], b_sw[Cfg::IB];
-  int cv_t[Cfg::IA], cv_h[Cfg::IA], cv_w[Cfg::IA];  // conv mode: output pixel of each staged row
 #pragma unroll
   for (int t = 0; t < Cfg::IA; ++t) {
     const int row = (wave * Cfg::IA + t) * 8 + ld_row;
@@ -237,13 +236,6 @@ __global__ __launch_bounds__(WR* WC * 64) void gemm_nt_kernel(const GemmParams p
     if (g > p.M - 1) g = p.M - 1;
     a_row[t] = g;
     a_sw[t] = (ld_slot ^ ((row >> 1) & 7)) * 8;
-    if constexpr (CONV) {
-      int64_t r2 = g;
-      cv_w[t] = (int)(r2 % p.cv_W); r2 /= p.cv_W;
-      cv_h[t] = (int)(r2 % p.cv_H); r2 /= p.cv_H;
-      cv_t[t] = (int)(r2 % p.cv_T);
-      a_row[t] = r2 / p.cv_T;  // batch index
-    }
   }
 #pragma unroll
   for (int t = 0; t < Cfg::IB; ++t) {
@@ -264,30 +256,10 @@ __global__ __launch_bounds__(WR* WC * 64) void gemm_nt_kernel(const GemmParams p
     }
     unsigned char* sa = smem + buf * Cfg::STAGE_BYTES;
     unsigned char* sb = sa + Cfg::A_BYTES;
-    if constexpr (CONV) {
-      const int tap = kt / p.cv_cpt;
-      const int c0 = (kt - tap * p.cv_cpt) * 64;
-      const int dw = tap % p.cv_kw;
-      const int dh = (tap / p.cv_kw) % p.cv_kh;
-      const int dt = tap / (p.cv_kw * p.cv_kh);
 #pragma unroll
-      for (int t = 0; t < Cfg::IA; ++t) {
-        const int ti = cv_t[t] * p.cv_st + dt - p.cv_pt;  // front padding only: causal in t, (k/2 | 0) in h, w
-        int hi = cv_h[t] * p.cv_sh + dh - p.cv_ph;
-        int wi = cv_w[t] * p.cv_sw + dw - p.cv_pw;
-        const int hb = p.cv_up2x ? 2 * p.cv_Hin : p.cv_Hin, wb = p.cv_up2x ? 2 * p.cv_Win : p.cv_Win;
-        const bool ok = ti >= 0 && ti < p.cv_Tin && hi >= 0 && hi < hb && wi >= 0 && wi < wb;
-        if (p.cv_up2x) { hi >>= 1; wi >>= 1; }
-        const int64_t pix = ((a_row[t] * p.cv_Tin + ti) * p.cv_Hin + hi) * (int64_t)p.cv_Win + wi;
-        const bf16_t* src = ok ? (A + pix * lda + c0 + a_sw[t]) : (p.cv_zero + a_sw[t]);
-        __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sa + (wave * Cfg::IA + t) * 1024), 16, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int t = 0; t < Cfg::IA; ++t) {
-        const bf16_t* src = A + a_row[t] * lda + k0 + a_sw[t];
-        __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sa + (wave * Cfg::IA + t) * 1024), 16, 0, 0);
-      }
+    for (int t = 0; t < Cfg::IA; ++t) {
+      const bf16_t* src = A + a_row[t] * lda + k0 + a_sw[t];
+      __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)(sa + (wave * Cfg::IA + t) * 1024), 16, 0, 0);
     }
 #pragma unroll
     for (int t = 0; t < Cfg::IB; ++t) {
@@ -670,8 +642,6 @@ __global__ __launch_bounds__(WR* WC * 64) void gemm16_nt_kernel(const GemmParams
 //   RAW: the wait of phase p (before its first barrier) retires everything but the 4 newest half-tiles, which always
 //        includes every slot phase p+1 reads; the reader passes at least one more barrier than any waiter.
 // ---------------------------------------------------------------------------
-#define GSTAMP() do {} while (0)
-
 #include "gemm_fast_epilogue.h"
 
 template <int N>
@@ -869,11 +839,8 @@ __global__ __launch_bounds__(512) void gemm8p_nt_kernel(const GemmParams p) {
       if constexpr (P == 4) stage_w(C0{}, kt + 2, buf);
     }
     if constexpr (VM >= 0) wait_vmcnt<VM>();
-    GSTAMP();
     __builtin_amdgcn_s_barrier();
-    GSTAMP();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    GSTAMP();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(1);
     constexpr int mq = (P >= 3) ? 1 : 0;
@@ -888,9 +855,7 @@ __global__ __launch_bounds__(512) void gemm8p_nt_kernel(const GemmParams p) {
               __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nq][j][ks], af[i][ks], acc[4 * mq + i][2 * nq + j], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
-    GSTAMP();
     __builtin_amdgcn_s_barrier();
-    GSTAMP();
   };
   using V8 = std::integral_constant<int, 8>;
   using V6 = std::integral_constant<int, 6>;
@@ -1025,6 +990,33 @@ extern "C" int lcv_gemm_set_workspace(void* ws, int64_t bytes) {
   return LCV_OK;
 }
 
+// ---- launch helpers ----
+// Raises KERN's dynamic LDS limit on first use (function-local static, one per kernel: initialised once, thread-safe).
+template <auto KERN>
+static int raise_dynamic_lds(const char* who, size_t lds) {
+  static const bool ok = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess;
+  if (ok) return LCV_OK;
+  lcv_set_error("%s: cannot raise dynamic LDS to %zu", who, lds);
+  return LCV_EDEVICE;
+}
+
+// Tile grid of a launch in BM x BN tiles, GROUP_M of the tile order; one launch over all tiles, K not split.  -> tile count
+static int set_tile_grid(GemmParams& p, int bm, int bn, int group_m) {
+  p.tiles_m = (int)((p.M + bm - 1) / bm);
+  p.tiles_n = (int)((p.N + bn - 1) / bn);
+  p.group_m = group_m;
+  const int ntiles = p.tiles_m * p.tiles_n;
+  p.vid_begin = 0; p.vid_count = ntiles; p.splitk = 1; p.nk_split = 0; p.ws = nullptr;
+  return ntiles;
+}
+
+// A/B knob LCV_GEMM_GROUP_M: tile rows per group of the tile order
+static int group_m_knob(int dflt) {
+  const char* ge = lcv_knob("LCV_GEMM_GROUP_M");
+  const int g = ge ? atoi(ge) : dflt;
+  return g < 1 ? dflt : g;
+}
+
 // Tail of a persistent launch: ntiles = r * 256 + t tiles on 256 CUs cost r + 1 tile-times although the last round keeps
 // only t CUs busy.  With a workspace a SMALL tail is split s ways along K into t*s work items (one partial round of ~1/s
 // tile-time), summed and finished by the reduce kernel.  Returns the chosen s (1 = leave the tail alone).
@@ -1048,73 +1040,39 @@ static int choose_tail_split(int t, int nk, int64_t ws_bytes) {
   return best_s;
 }
 
-template <int EPI, bool PERSIST>
+// CONV: the convolution form (N >= 192 stages of the VAE): persistent, reads no knobs, no split-K tail, no fast epilogue.
+template <int EPI, bool PERSIST, bool CONV = false>
 static int launch_gemm8p(GemmParams& p, hipStream_t s) {
-  p.tiles_m = (int)((p.M + 255) / 256);
-  // tile rows per group of the tile order (A/B knob LCV_GEMM_GROUP_M): 6 measured best for the persistent kernel at the K3
-  // projection shapes (4, 6, 8, 16 -> 1267, 1285, 1240, 1172 TF/s on the qkv GEMM, in one process)
-  { const char* ge = lcv_knob("LCV_GEMM_GROUP_M"); p.group_m = ge ? atoi(ge) : 6; if (p.group_m < 1) p.group_m = 6; }
-  p.tiles_n = (int)((p.N + 255) / 256);
+  // tile rows per group: 6 measured best for the persistent kernel at the K3 projection shapes (4, 6, 8, 16 -> 1267, 1285,
+  // 1240, 1172 TF/s on the qkv GEMM, in one process)
+  const int ntiles = set_tile_grid(p, 256, 256, CONV ? 6 : group_m_knob(6));
   const size_t lds = 2 * 65536;
-  auto kern = gemm8p_nt_kernel<EPI, PERSIST>;
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("gemm_nt: cannot raise dynamic LDS to %zu", lds);
-      return LCV_EDEVICE;
-  }
-  const int ntiles = p.tiles_m * p.tiles_n;
-  p.vid_begin = 0; p.vid_count = ntiles; p.splitk = 1; p.nk_split = 0; p.ws = nullptr;
-  { const char* fe = lcv_knob("LCV_GEMM_FAST_EPI"); p.fast_epi = (fe && fe[0] == '0') ? 0 : 1; }
-  if (PERSIST && ntiles > 256 && g_gemm_ws != nullptr) {
-    const int t = ntiles % 256, nk = p.nk1 + p.nk2;
-    const int sk = choose_tail_split(t, nk, g_gemm_ws_bytes);
-    if (sk > 1) {
-      auto skern = gemm8p_nt_kernel<LCV_EPI_NONE, false, true>;
-      // (function-local static: initialised once, thread-safe)
-      static const bool sattr_ok = !(hipFuncSetAttribute((const void*)skern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-      if (!sattr_ok) {
-          lcv_set_error("gemm_nt: cannot raise dynamic LDS to %zu", lds);
-          return LCV_EDEVICE;
+  constexpr auto kern = gemm8p_nt_kernel<EPI, PERSIST, false, CONV>;
+  if (int rc = raise_dynamic_lds<kern>(CONV ? "conv3d" : "gemm_nt", lds)) return rc;
+  if constexpr (!CONV) {
+    { const char* fe = lcv_knob("LCV_GEMM_FAST_EPI"); p.fast_epi = (fe && fe[0] == '0') ? 0 : 1; }
+    if (PERSIST && ntiles > 256 && g_gemm_ws != nullptr) {
+      const int t = ntiles % 256, nk = p.nk1 + p.nk2;
+      const int sk = choose_tail_split(t, nk, g_gemm_ws_bytes);
+      if (sk > 1) {
+        constexpr auto skern = gemm8p_nt_kernel<LCV_EPI_NONE, false, true>;
+        if (int rc = raise_dynamic_lds<skern>("gemm_nt", lds)) return rc;
+        p.vid_count = ntiles - t;                           // full rounds: every CU busy to the end
+        hipLaunchKernelGGL(kern, dim3(256), dim3(512), lds, s, p);
+        LCV_LAUNCH_CHECK("gemm8p_nt");
+        p.vid_begin = ntiles - t; p.vid_count = t; p.splitk = sk; p.nk_split = (nk + sk - 1) / sk; p.ws = g_gemm_ws;
+        hipLaunchKernelGGL(skern, dim3((unsigned)(t * sk)), dim3(512), lds, s, p);
+        LCV_LAUNCH_CHECK("gemm8p_nt_splitk");
+        hipLaunchKernelGGL(gemm8p_splitk_reduce_kernel<EPI>, dim3((unsigned)t), dim3(512), 0, s, p);
+        LCV_LAUNCH_CHECK("gemm8p_splitk_reduce");
+        return LCV_OK;
       }
-      p.vid_count = ntiles - t;                           // full rounds: every CU busy to the end
-      hipLaunchKernelGGL(kern, dim3(256), dim3(512), lds, s, p);
-      LCV_LAUNCH_CHECK("gemm8p_nt");
-      p.vid_begin = ntiles - t; p.vid_count = t; p.splitk = sk; p.nk_split = (nk + sk - 1) / sk; p.ws = g_gemm_ws;
-      hipLaunchKernelGGL(skern, dim3((unsigned)(t * sk)), dim3(512), lds, s, p);
-      LCV_LAUNCH_CHECK("gemm8p_nt_splitk");
-      hipLaunchKernelGGL(gemm8p_splitk_reduce_kernel<EPI>, dim3((unsigned)t), dim3(512), 0, s, p);
-      LCV_LAUNCH_CHECK("gemm8p_splitk_reduce");
-      return LCV_OK;
     }
   }
   unsigned grid = (unsigned)ntiles;
   if (PERSIST && grid > 256) grid = 256;  // one workgroup per CU (the LDS image allows no more); a multiple of 8 XCDs
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
-  LCV_LAUNCH_CHECK("gemm8p_nt");
-  return LCV_OK;
-}
-
-// The convolution form of the 8-phase kernel (N >= 192 stages of the VAE): persistent, no split-K tail.
-template <int EPI>
-static int launch_conv8p(GemmParams& p, hipStream_t s) {
-  p.tiles_m = (int)((p.M + 255) / 256);
-  p.group_m = 6;
-  p.tiles_n = (int)((p.N + 255) / 256);
-  const size_t lds = 2 * 65536;
-  auto kern = gemm8p_nt_kernel<EPI, true, false, true>;
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("conv3d: cannot raise dynamic LDS to %zu", lds);
-      return LCV_EDEVICE;
-  }
-  const int ntiles = p.tiles_m * p.tiles_n;
-  p.vid_begin = 0; p.vid_count = ntiles; p.splitk = 1; p.nk_split = 0; p.ws = nullptr;
-  unsigned grid = (unsigned)ntiles;
-  if (grid > 256) grid = 256;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, p);
-  LCV_LAUNCH_CHECK("conv8p_igemm");
+  LCV_LAUNCH_CHECK(CONV ? "conv8p_igemm" : "gemm8p_nt");
   return LCV_OK;
 }
 
@@ -1123,21 +1081,12 @@ static int launch_conv8p(GemmParams& p, hipStream_t s) {
 // four waves x 128 x 128 on 64-deep K tiles in 128-byte rows (gemm4k.h, round 4), persistent over all tiles of the launch
 template <int EPI>
 static int launch_gemm4k(GemmParams& p, hipStream_t s) {
-  p.tiles_m = (int)((p.M + 255) / 256);
   // tile rows per group of the XCD-contiguous tile order: 3 measured best for this kernel (1 ... 64 swept in one process at the
   // qkv / w13 / proj shapes, profiles/r04_gemm_ab.md: 1435 / 1358 / 1411 TF/s at 3, 1398 / 1353 / 1420 at 6, 1254 / 1251 / 1275 at 16)
-  { const char* ge = lcv_knob("LCV_GEMM_GROUP_M"); p.group_m = ge ? atoi(ge) : 3; if (p.group_m < 1) p.group_m = 3; }
-  p.tiles_n = (int)((p.N + 255) / 256);
+  const int ntiles = set_tile_grid(p, 256, 256, group_m_knob(3));
   const size_t lds = 2 * 65536;
-  auto kern = gemm4k_nt_kernel<EPI>;
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("gemm_nt: cannot raise dynamic LDS to %zu", lds);
-      return LCV_EDEVICE;
-  }
-  const int ntiles = p.tiles_m * p.tiles_n;
-  p.vid_begin = 0; p.vid_count = ntiles; p.splitk = 1; p.nk_split = 0; p.ws = nullptr;
+  constexpr auto kern = gemm4k_nt_kernel<EPI>;
+  if (int rc = raise_dynamic_lds<kern>("gemm_nt", lds)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)(ntiles > 256 ? 256 : ntiles)), dim3(256), lds, s, p);
   LCV_LAUNCH_CHECK("gemm4k_nt");
   return LCV_OK;
@@ -1146,39 +1095,25 @@ static int launch_gemm4k(GemmParams& p, hipStream_t s) {
 template <int BM, int BN, int WR, int WC, int EPI, bool CONV, int NST = 2>
 static int launch_gemm16(GemmParams& p, hipStream_t s) {
   using Cfg = GemmCfg<BM, BN, WR, WC>;
-  p.tiles_m = (int)((p.M + BM - 1) / BM);
-  p.group_m = 8;
-  p.tiles_n = (int)((p.N + BN - 1) / BN);
+  const int ntiles = set_tile_grid(p, BM, BN, 8);
   const size_t lds = NST * Cfg::STAGE_BYTES;
   static_assert(NST * Cfg::STAGE_BYTES <= 163840, "gemm16: LDS image");
-  auto kern = gemm16_nt_kernel<BM, BN, WR, WC, EPI, CONV, NST>;
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("gemm_nt: cannot raise dynamic LDS to %zu", lds);
-      return LCV_EDEVICE;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(Cfg::NT), lds, s, p);
+  constexpr auto kern = gemm16_nt_kernel<BM, BN, WR, WC, EPI, CONV, NST>;
+  if (int rc = raise_dynamic_lds<kern>("gemm_nt", lds)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(Cfg::NT), lds, s, p);
   LCV_LAUNCH_CHECK(CONV ? "conv16_igemm" : "gemm16_nt");
   return LCV_OK;
 }
 
-template <int BM, int BN, int WR, int WC, int EPI, bool CONV>
+template <int BM, int BN, int WR, int WC, int EPI>
 static int launch_gemm(GemmParams& p, hipStream_t s) {
   using Cfg = GemmCfg<BM, BN, WR, WC>;
-  p.tiles_m = (int)((p.M + BM - 1) / BM);
-  p.group_m = 8;
-  p.tiles_n = (int)((p.N + BN - 1) / BN);
+  const int ntiles = set_tile_grid(p, BM, BN, 8);
   const size_t lds = 2 * Cfg::STAGE_BYTES;
-  auto kern = gemm_nt_kernel<BM, BN, WR, WC, EPI, CONV>;
-  // (function-local static: initialised once, thread-safe)
-  static const bool attr_ok = !(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess);
-  if (!attr_ok) {
-      lcv_set_error("gemm_nt: cannot raise dynamic LDS to %zu", lds);
-      return LCV_EDEVICE;
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(Cfg::NT), lds, s, p);
-  LCV_LAUNCH_CHECK(CONV ? "conv_igemm" : "gemm_nt");
+  constexpr auto kern = gemm_nt_kernel<BM, BN, WR, WC, EPI>;
+  if (int rc = raise_dynamic_lds<kern>("gemm_nt", lds)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(Cfg::NT), lds, s, p);
+  LCV_LAUNCH_CHECK("gemm_nt");
   return LCV_OK;
 }
 
@@ -1210,30 +1145,38 @@ static int dispatch_tile(GemmParams& p, hipStream_t s) {
   if (mode == 9 && ok8t) return launch_gemm8p<EPI, true>(p, s);
   if (mode == 6 || mode == 8 || mode == 9) return launch_gemm16<256, 256, 2, 4, EPI, false>(p, s);
   if (mode == 7) return launch_gemm16<128, 128, 2, 2, EPI, false>(p, s);
-  if (mode == 2) return launch_gemm<256, 256, 2, 4, EPI, false>(p, s);
-  return launch_gemm<128, 128, 2, 2, EPI, false>(p, s);
+  if (mode == 2) return launch_gemm<256, 256, 2, 4, EPI>(p, s);
+  return launch_gemm<128, 128, 2, 2, EPI>(p, s);
 }
 
 #include "conv_wide.h"
 
+// name of the kernel the last convolution of this thread launched, recorded where it is chosen (tests assert it)
+static thread_local const char* g_last_conv_kernel = "none";
+extern "C" const char* lcv_conv3d_last_kernel(void) { return g_last_conv_kernel; }
+
 template <int EPI>
 static int dispatch_conv(GemmParams& p, hipStream_t s) {
-  // wide stages: the 8-phase kernel when its pipeline has K tiles to fill (>= 2)
-  // wide stages.  LCV_CONV_8P=1: the 8-phase kernel with the gather in its A stream - bit-identical to the two-stage kernel and
-  // no faster on the VAE's shapes (802 vs 816 TF/s on 192 -> 192 at 360 x 640), so it stays opt-in.
   const char* e8 = lcv_knob("LCV_CONV_8P");
-  if (p.N >= 192 && p.nk1 >= 2 && e8 && e8[0] == '1') return launch_conv8p<EPI>(p, s);
-  // Cout = 192 / 384: 192-column tiles instead of 256-column tiles of which a quarter multiplies padding
   const char* e192 = lcv_knob("LCV_CONV_N192");
-  if (p.N >= 192 && p.N % 192 == 0 && !(e192 && e192[0] == '0')) {
+  const char n192 = e192 ? e192[0] : '\0';
+  if (p.N < 192) { g_last_conv_kernel = "conv16_igemm<128x128>"; return launch_gemm16<128, 128, 2, 2, EPI, true>(p, s); }
+  // wide stages.  LCV_CONV_8P=1: the 8-phase kernel with the gather in its A stream, when its pipeline has K tiles to fill
+  // (>= 2) - bit-identical to the two-stage kernel and no faster on the VAE's shapes (802 vs 816 TF/s on 192 -> 192 at
+  // 360 x 640), so it stays opt-in.
+  if (p.nk1 >= 2 && e8 && e8[0] == '1') { g_last_conv_kernel = "conv8p_igemm<256x256>"; return launch_gemm8p<EPI, true, true>(p, s); }
+  // Cout = 192 / 384: 192-column tiles instead of 256-column tiles of which a quarter multiplies padding
+  if (p.N % 192 == 0 && n192 != '0') {
     // LCV_CONV_N192=3: 192 x 192 tiles on a ring of three buffers with a counted wait - bit-identical and SLOWER (873 vs 919,
     // 952 vs 1011 TF/s): these kernels do not wait for the round trip of their requests
-    if (e192 && e192[0] == '3') return launch_gemm16<192, 192, 2, 4, EPI, true, 3>(p, s);
-    if (e192 && e192[0] == '2') return launch_gemm16<256, 192, 2, 4, EPI, true>(p, s);      // every wave stages and multiplies
-    return launch_conv_wide<EPI>(p, s);                                                     // loader waves + MFMA waves
+    if (n192 == '3') { g_last_conv_kernel = "conv16_igemm<192x192x3>"; return launch_gemm16<192, 192, 2, 4, EPI, true, 3>(p, s); }
+    // every wave stages and multiplies
+    if (n192 == '2') { g_last_conv_kernel = "conv16_igemm<256x192>"; return launch_gemm16<256, 192, 2, 4, EPI, true>(p, s); }
+    g_last_conv_kernel = "conv_wide<256x192>";                                               // loader waves + MFMA waves
+    return launch_conv_wide<EPI>(p, s);
   }
-  if (p.N >= 192) return launch_gemm16<256, 256, 2, 4, EPI, true>(p, s);
-  return launch_gemm16<128, 128, 2, 2, EPI, true>(p, s);
+  g_last_conv_kernel = "conv16_igemm<256x256>";
+  return launch_gemm16<256, 256, 2, 4, EPI, true>(p, s);
 }
 
 extern "C" int lcv_gemm_nt(const void* a, const void* w, const void* bias, const void* a2, const void* w2,
@@ -1275,9 +1218,6 @@ extern "C" int lcv_gemm_nt(const void* a, const void* w, const void* bias, const
   }
 }
 
-static thread_local const char* g_last_conv_kernel = "none";
-extern "C" const char* lcv_conv3d_last_kernel(void) { return g_last_conv_kernel; }
-
 #include "conv_rows.h"
 
 // ---------------------------------------------------------------------------
@@ -1316,15 +1256,13 @@ static int conv3d_impl(const void* x, const void* w, const void* bias, const voi
   if (conv_rows_applies(p, Cin)) {
     p.cv_cpt = (int)(Cin / 96);
     { const char* eo = lcv_knob("LCV_CONV_ROWS_ORDER"); p.splitk = (eo && eo[0] == 'w') ? 1 : 0; }   // tile sequence (conv_rows.h)
-    g_last_conv_kernel = p.N <= 16 ? "conv_rows<256x16>" : "conv_rows<256x96>";
-    if (p.N <= 16) return resid ? launch_conv_rows<8, 1, 2, 1, LCV_EPI_GATE_RESIDUAL>(p, s) : launch_conv_rows<8, 1, 2, 1, LCV_EPI_NONE>(p, s);
+    if (p.N <= 16) {
+      g_last_conv_kernel = "conv_rows<256x16>";
+      return resid ? launch_conv_rows<8, 1, 2, 1, LCV_EPI_GATE_RESIDUAL>(p, s) : launch_conv_rows<8, 1, 2, 1, LCV_EPI_NONE>(p, s);
+    }
+    g_last_conv_kernel = "conv_rows<256x96>";
     return resid ? launch_conv_rows<4, 2, 4, 3, LCV_EPI_GATE_RESIDUAL>(p, s) : launch_conv_rows<4, 2, 4, 3, LCV_EPI_NONE>(p, s);
   }
-  { const char* e8 = lcv_knob("LCV_CONV_8P"); const char* e192 = lcv_knob("LCV_CONV_N192");
-    g_last_conv_kernel = p.N < 192 ? "conv16_igemm<128x128>"
-                         : (p.nk1 >= 2 && e8 && e8[0] == '1') ? "conv8p_igemm<256x256>"
-                         : (p.N % 192 == 0 && !(e192 && e192[0] == '0')) ? ((e192 && e192[0] == '3') ? "conv16_igemm<192x192x3>" : (e192 && e192[0] == '2') ? "conv16_igemm<256x192>" : "conv_wide<256x192>")
-                                                                         : "conv16_igemm<256x256>"; }
   if (resid) return dispatch_conv<LCV_EPI_GATE_RESIDUAL>(p, s);
   return dispatch_conv<LCV_EPI_NONE>(p, s);
 }

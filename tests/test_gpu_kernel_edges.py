@@ -5,6 +5,7 @@ cancellation.  Every bound is derived from the tolerance rule of kernel_ref's do
 asserts.  Outputs the kernel must write in full (pads, tails) are NaN-filled first, through `lib.call` with caller-owned
 buffers where the ops wrapper would allocate them; input pad channels the kernel must ignore hold a large finite value.
 """
+import functools
 import math
 
 import pytest
@@ -12,7 +13,7 @@ import torch
 
 import kernel_ref as K
 
-pytestmark = pytest.mark.gpu
+gpu = pytest.mark.gpu    # per test: the file also holds CPU checks of the exact GEMM cases' own arithmetic
 
 BF16, F32 = torch.bfloat16, torch.float32
 DEV = "cuda"
@@ -60,6 +61,7 @@ def _xhat_err(x, xh, rstd, C):
 
 
 # --------------------------------------------------------------------------------------------- lcv_vae_rmsnorm_silu
+@gpu
 @pytest.mark.parametrize("rows,C,Cpad,silu", [
     (262161, 120, 128, 1),   # LPR 16: second row group (U = 2) and a second grid-stride pass past 8192 wg x 16 rows x 2
     (65541, 256, 256, 0),    # LPR 32 past its cap (8192 wg x 8 rows), apply_silu = 0
@@ -80,6 +82,7 @@ def test_vae_rmsnorm_silu_edges(rows, C, Cpad, silu):
 
 
 # ------------------------------------------------------------------------------------------------- lcv_softmax_rows
+@gpu
 @pytest.mark.parametrize("rows,n,ld_s,ld_p,scale", [
     (16, 14400, 14400, 14464, 384 ** -0.5),   # the 720p VAE mid-block row; p padded to 64 columns
     (5, 300, 301, 320, 0.7),                  # n not a multiple of 256, ld_s > n, ld_p > n
@@ -95,6 +98,7 @@ def test_softmax_rows_edges(rows, n, ld_s, ld_p, scale):
     K.assert_within(p, K.softmax_rows(s, n, ld_p, scale), 1.0, what=f"softmax_rows n={n}")
 
 
+@gpu
 @pytest.mark.parametrize("scale", [-0.05, 0.0, NAN, math.inf])
 def test_softmax_rows_rejects_a_scale_the_max_shift_does_not_guard(scale):
     from lcv_hip.lib import LcvError
@@ -108,6 +112,7 @@ def test_softmax_rows_rejects_a_scale_the_max_shift_does_not_guard(scale):
 
 
 # ------------------------------------------------------------------------------------------ lcv_gelu_tanh_fwd / _bwd
+@gpu
 def test_gelu_tanh_fwd_bwd_past_the_block_cap_and_in_saturation():
     n = 4096 * 256 * 8 + 8                     # one packet past 4096 workgroups x 256 lanes x 8: a second grid-stride pass
     x = _randn(n, seed=4, scale=3.0)
@@ -128,6 +133,7 @@ def test_gelu_tanh_fwd_bwd_past_the_block_cap_and_in_saturation():
 
 
 # -------------------------------------------------------------------------------------- lcv_linear_f32_smallm_wgrad
+@gpu
 @pytest.mark.parametrize("M,N,K_,act,want_db", [
     (3, 6 * 4096, 300, 1, True),    # the adaLN modulation width; K tail, two x-blocks (only x-block 0 writes db)
     (64, 40, 1000, 0, False),       # K > 256: four x-blocks, db not wanted
@@ -151,6 +157,7 @@ def test_linear_f32_smallm_wgrad_edges(M, N, K_, act, want_db):
 
 
 # -------------------------------------------------------------------------------------- lcv_transpose_pad, lcv_rowsum
+@gpu
 @pytest.mark.parametrize("M,N,ld,off", [
     (37, 130, 130, 0),     # N not a multiple of 4 (scalar path for the last packet), M < 64
     (200, 6, 8, 0),        # ld > N, N < 64: one vector packet and one scalar tail per row
@@ -184,11 +191,13 @@ def _rowsum_check(xin, what):
                         what=f"{what} ({'fp32' if out_f32 else 'bf16'} out)")
 
 
+@gpu
 @pytest.mark.parametrize("rows,cols", [(37, 4104), (5, 8), (3, 520)])
 def test_rowsum_cols_not_a_multiple_of_512(rows, cols):
     _rowsum_check(_randn(rows, cols, seed=11), f"rowsum {rows}x{cols}")
 
 
+@gpu
 def test_rowsum_rejects_a_misaligned_input():
     from lcv_hip.lib import LcvError
     buf = _randn(4 * 64 + 8, seed=12)
@@ -198,6 +207,7 @@ def test_rowsum_rejects_a_misaligned_input():
 
 
 # ---------------------------------------------------------------------------------------------------- lcv_euler_step
+@gpu
 @pytest.mark.parametrize("n,negate", [(2048 * 256 + 3, 1), (2048 * 256 + 3, 0), (5, 1)])
 def test_euler_step_edges(n, negate):
     dt = 0.7                                   # |dt v| ~ |x|: cancellations occur
@@ -211,6 +221,7 @@ def test_euler_step_edges(n, negate):
 
 
 # ---------------------------------------------------------------------------------------------- lcv_cfg_euler_step
+@gpu
 @pytest.mark.parametrize("zero_star,negate", [(1, 1), (1, 0), (0, 1), (0, 0)])
 def test_cfg_euler_step_edges(zero_star, negate):
     B, n = 3, 1024 * 256 + 77                   # past the 1024-workgroup cap, a tail
@@ -248,6 +259,7 @@ def test_cfg_euler_step_edges(zero_star, negate):
 
 
 # ------------------------------------------------------------------------------------------- lcv_gate_residual_bwd
+@gpu
 @pytest.mark.parametrize("B,T,S,C,want_dmod", [
     (2, 2, 37, 4096, True),     # C = 4096: both GATE_MAXPK slots; frames switch inside the 32-row workgroups
     (1, 2, 9, 4104, True),      # C > 4096: the per-element-atomic fallback
@@ -282,6 +294,7 @@ def _norm_inputs(B, T, S, C, seed):
     return x
 
 
+@gpu
 @pytest.mark.parametrize("B,T,S,C,with_dres", [
     (2, 2, 37, 4096, True),      # the product width (LDS sums 2 x 16 KiB); S >= 32, not a multiple: one frame switch per wg
     (1, 3, 9, 4096, False),      # S < 32: several frames per workgroup
@@ -352,6 +365,7 @@ def _check_rownorm_bwd(x, dy, dres, mul, dx, C, eps, what):
 
 
 # ------------------------------------------------------ lcv_adaln_modulate_fwd, lcv_layernorm_affine_fwd, lcv_gate_residual_fwd
+@gpu
 @pytest.mark.parametrize("C", [8, 520, 4096])
 def test_norm_and_gate_residual_fwd_edges(C):
     B, T, S, eps = 1, 3, 7, 1e-6                # 21 rows: not a multiple of 4 (one wave per row, 4 per workgroup)
@@ -384,6 +398,7 @@ def test_norm_and_gate_residual_fwd_edges(C):
     K.assert_within(out, ref, 1.0, 2 * U * (K.f64(x).abs() + (gate * K.f64(r)).abs()), what=f"gate_residual_fwd C={C}")
 
 
+@gpu
 def test_gate_residual_fwd_without_gate_past_the_block_cap():
     rows, C = 16200, 520                        # 1 053 000 packets of 8: past 4096 workgroups x 256 lanes
     x, r = _randn(1, rows, C, seed=35), _randn(1, rows, C, seed=36)
@@ -394,6 +409,7 @@ def test_gate_residual_fwd_without_gate_past_the_block_cap():
 
 
 # ------------------------------------------------------------------- lcv_swiglu_fwd, lcv_patchify, lcv_unpatchify(_bwd)
+@gpu
 def test_swiglu_fwd_on_views_into_one_buffer_past_the_block_cap():
     rows, F = 2049, 4104                        # 1 051 137 packets: past 4096 workgroups x 256 lanes
     gu = _randn(rows, 2 * F, seed=37, scale=2.0)
@@ -408,6 +424,7 @@ def test_swiglu_fwd_on_views_into_one_buffer_past_the_block_cap():
     K.assert_within(out, s * upf, 1.0, alt=s_alt * upf, what="swiglu_fwd")
 
 
+@gpu
 def test_patchify_pad_and_unpatchify_past_the_block_cap():
     B, Cin, T, H, W, Kpad = 1, 16, 2, 258, 258, 128     # 2 x 129^2 tokens x 32 groups = 1 065 024 threads; Kpad > 4 Cin
     x = _randn(B, Cin, T, H, W, seed=38)
@@ -434,6 +451,7 @@ def test_patchify_pad_and_unpatchify_past_the_block_cap():
 
 
 # ------------------------------------------------------------------------------------------ lcv_fm_noise, lcv_fm_mse
+@gpu
 def test_fm_noise_past_the_block_cap():
     B, per = 2, 2048 * 256 + 40
     x0, eps = _randn(B, per, seed=41), _randn(B, per, seed=42)
@@ -449,6 +467,7 @@ def test_fm_noise_past_the_block_cap():
     K.assert_within(out, a + e, 1.0, 3 * U * (a.abs() + e.abs()), what="fm_noise")
 
 
+@gpu
 @pytest.mark.parametrize("Tc", [0, 2, 4])
 def test_fm_mse_past_the_block_cap_and_deterministic(Tc):
     B, C, T, HW = 2, 16, 5, 3300               # 528 000 elements: two grid-stride passes over 1024 x 256 lanes
@@ -473,3 +492,121 @@ def test_fm_mse_past_the_block_cap_and_deterministic(Tc):
     loss2, dpred2 = _nan(1, dtype=F32), _nan(B, C, T, HW, dtype=F32)
     _call("lcv_fm_mse", _p(pred), _p(eps), _p(x0), _p(loss2), _p(dpred2), _p(ws), B, C, T, Tc, HW)
     assert torch.equal(loss, loss2) and torch.equal(dpred, dpred2)       # the early stopper's strict `<` needs these bits
+
+
+# ------------------------------------------------------------------------- lcv_gemm_nt: every tile mode, bit for bit
+# Integer-valued bf16 operands (as in tests/conv_ref.py): a in [-3, 3], w in [-2, 2], bias and residual in [-8, 8], the gate an
+# integer-valued fp32 table in [-2, 2].  With K = 128 every product and every partial sum is an integer of magnitude
+# <= 3 * 2 * 128 + 8 = 776, exact in fp32 in ANY summation order and on either MFMA shape, so the kernel's output is a function
+# of its rounding points alone: bf16(sum + bias), and bf16(resid + gate * bf16(sum + bias)) (include/lcv_hip.h).
+# M = 300 is ragged against 128 and 256 and rows_per_frame = 110 puts frame switches inside a wave tile; N = 320 is ragged
+# against 128 and 256 (and a multiple of 64, for SwiGLU); N = 512 is where LCV_GEMM_TILE=k really takes the four-wave kernel.
+_GX_M, _GX_K, _GX_RPF = 300, 128, 110
+_GX_MODES = ["1", "2", "6", "7", "8", "9", "k"]
+_GX_NS = [320, 512]
+
+
+@functools.lru_cache(maxsize=None)
+def _gx_inputs(N):
+    g = torch.Generator().manual_seed(7100 + N)
+
+    def ints(lo, hi, *shape):
+        return torch.randint(lo, hi + 1, shape, generator=g).to(F32)
+    frames = -(-_GX_M // _GX_RPF)
+    return {"a": ints(-3, 3, _GX_M, _GX_K).to(BF16), "w": ints(-2, 2, N, _GX_K).to(BF16), "bias": ints(-8, 8, N).to(BF16),
+            "resid": ints(-8, 8, _GX_M, N).to(BF16), "mod": ints(-2, 2, 1, frames, 6 * N)}
+
+
+_GX_GATE_IDX = 5
+
+
+@functools.lru_cache(maxsize=None)
+def _gx_restatement(N):
+    """float64, one rounding where the header says.  -> {case: expected tensor}"""
+    x = _gx_inputs(N)
+    s = x["a"].double() @ x["w"].double().t()
+    sb = s + x["bias"].double()
+    gate = x["mod"][0, :, _GX_GATE_IDX * N:(_GX_GATE_IDX + 1) * N].double().repeat_interleave(_GX_RPF, dim=0)[:_GX_M]
+    proj = sb.to(BF16).double()                         # the projection output is a bf16 tensor upstream
+    return {"none": s.to(BF16), "none+bias": sb.to(BF16), "none,f32": s.to(F32), "none+bias,f32": sb.to(F32),
+            "gate_residual": (x["resid"].double() + proj).to(BF16), "gate_residual+gate": (x["resid"].double() + gate * proj).to(BF16)}
+
+
+@pytest.mark.parametrize("N", _GX_NS)
+def test_gemm_exact_cases_are_exact_in_fp32_and_agree_with_the_oracle(N):
+    """CPU: the claim the bitwise test rests on, and the restatement against oracle.linear at the same shapes."""
+    from oracle import dit_oracle as orc
+    x = _gx_inputs(N)
+    for k, lo, hi in (("a", -3, 3), ("w", -2, 2), ("bias", -8, 8), ("resid", -8, 8), ("mod", -2, 2)):
+        v = x[k].double()
+        assert torch.equal(v, v.round()) and v.min() >= lo and v.max() <= hi and v.min() < 0 < v.max(), k
+    # any partial sum of any order is bounded by the sum of magnitudes; the gate stage by |resid| + |gate| * that
+    worst = (x["a"].double().abs() @ x["w"].double().abs().t()).max().item() + 8
+    assert worst <= 776 and 8 + 2 * worst < 2 ** 24
+    want = _gx_restatement(N)
+    assert torch.equal(want["none+bias,f32"], orc.linear(x["a"], x["w"], x["bias"]))
+    assert torch.equal(want["none,f32"], orc.linear(x["a"], x["w"]))
+    assert torch.equal(want["none+bias"].float(), orc.linear(x["a"], x["w"], x["bias"], orc.bf16_round))
+    gate = x["mod"][0, :, _GX_GATE_IDX * N:(_GX_GATE_IDX + 1) * N].repeat_interleave(_GX_RPF, dim=0)[:_GX_M]
+    assert torch.equal(want["gate_residual+gate"].float(),
+                       orc.bf16_round(x["resid"].float() + gate * orc.linear(x["a"], x["w"], x["bias"], orc.bf16_round)))
+
+
+def _gx_equal(got, want, mode, case):
+    got, want = got.cpu(), want.cpu()
+    assert got.shape == want.shape and got.dtype == want.dtype, (mode, case, got.shape, got.dtype)
+    bad = ~(got == want)
+    if bad.any():
+        m, n = bad.nonzero()[0].tolist()
+        pytest.fail(f"LCV_GEMM_TILE={mode}, {case}: first difference at (m, n) = ({m}, {n}): got {got[m, n].item()}, "
+                    f"want {want[m, n].item()}; {int(bad.sum())} of {bad.numel()} differ")
+
+
+def _gx_run(N, case):
+    from lcv_hip import ops
+    from lcv_hip.lib import LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_NONE, LCV_EPI_SILU, LCV_EPI_SWIGLU
+    x = {k: v.to(DEV) for k, v in _gx_inputs(N).items()}
+    a, w, b = x["a"], x["w"], x["bias"]
+    if case.startswith("none"):
+        return ops.gemm_nt(a, w, b if "+bias" in case else None, epilogue=LCV_EPI_NONE, out_f32=case.endswith(",f32"))
+    if case.startswith("gate_residual"):
+        gated = case.endswith("+gate")
+        return ops.gemm_nt(a, w, b, epilogue=LCV_EPI_GATE_RESIDUAL, resid=x["resid"], mod=x["mod"] if gated else None,
+                           gate_idx=_GX_GATE_IDX if gated else 0, rows_per_frame=_GX_RPF)
+    if case == "swiglu":
+        return ops.gemm_nt(a, w, b, epilogue=LCV_EPI_SWIGLU)
+    if case == "swiglu+aux":
+        aux = _nan(_GX_M, N)
+        return torch.cat([ops.gemm_nt(a, w, b, epilogue=LCV_EPI_SWIGLU, swiglu_aux=aux), aux], dim=1)
+    return ops.gemm_nt(a, w, b, epilogue={"gelu": LCV_EPI_GELU_TANH, "silu": LCV_EPI_SILU}[case])
+
+
+@gpu
+@pytest.mark.parametrize("mode", _GX_MODES)
+@pytest.mark.parametrize("N", _GX_NS)
+def test_gemm_every_tile_mode_equals_the_float64_restatement(N, mode, monkeypatch):
+    """NONE (with / without bias, bf16 / fp32 output) and GATE_RESIDUAL (with / without gate) on every LCV_GEMM_TILE mode:
+    the 32x32x16 kernels (1, 2), the 16x16x32 two-buffer kernels (6, 7), the 8-phase kernel (8, 9) and the four-wave kernel
+    (k, taken at N = 512; at N = 320 it falls back to 9) must each reproduce the restatement bit for bit."""
+    monkeypatch.setenv("LCV_GEMM_TILE", mode)
+    for case, want in _gx_restatement(N).items():
+        _gx_equal(_gx_run(N, case), want, mode, case)
+
+
+_GX_MODE7 = {}
+
+
+@gpu
+@pytest.mark.parametrize("mode", [m for m in _GX_MODES if m != "7"])
+@pytest.mark.parametrize("N", _GX_NS)
+def test_gemm_transcendental_epilogues_equal_mode_7_bitwise(N, mode, monkeypatch):
+    """SwiGLU (with and without the pre-activation output), GELU and SiLU call device transcendentals: nothing exact can be
+    stated on the host, but their inputs are exact, so every mode must equal mode 7 (which the oracle tests of
+    test_gpu_kernels.py bound) bit for bit."""
+    cases = ["swiglu", "swiglu+aux", "gelu", "silu"]
+    if N not in _GX_MODE7:
+        monkeypatch.setenv("LCV_GEMM_TILE", "7")
+        _GX_MODE7[N] = {case: _gx_run(N, case).cpu() for case in cases}
+    monkeypatch.setenv("LCV_GEMM_TILE", mode)
+    for case in cases:
+        _gx_equal(_gx_run(N, case), _GX_MODE7[N][case], mode, case)
