@@ -5,12 +5,12 @@ is no CPU or eager-PyTorch fallback anywhere above it.
 """
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 from pathlib import Path
 
 _LIB_PATH = Path(__file__).resolve().parent / "liblcv_hip.so"
 
-P, I64, F32, I, F64 = c_void_p, c_int64, c_float, c_int, c_double
+P, I64, F32, I, F64, U64 = c_void_p, c_int64, c_float, c_int, c_double, c_uint64
 
 # name -> argtypes (every function returns int)
 _SIGNATURES = {
@@ -85,6 +85,15 @@ _SIGNATURES_DET = {
 }
 LCV_DET_ADALN, LCV_DET_LAYERNORM, LCV_DET_GATE, LCV_DET_QKNORM, LCV_DET_SMALLM, LCV_DET_GRAD_NORM = range(6)
 
+# include/lcv_hip_lora.h (a header of its own: the LoRA dropout kernels); `p` is a double, seed / offset are uint64, row0 is the
+# global index of the first row; every function returns int
+_SIGNATURES_LORA = {
+    "lcv_lora_down_dropout": [P, P, P, I64, I64, I64, I64, I64, F32, F64, U64, U64, I64, P],
+    "lcv_tn_skinny_dropout": [P, P, P, I64, I64, I64, I64, I64, F32, F64, U64, U64, I64, P, I64, P],
+    "lcv_lora_dx_dropout_add": [P, P, P, I64, I64, I64, I64, I64, F64, U64, U64, I64, P],
+    "lcv_lora_dropout_mask": [P, I64, I64, F64, U64, U64, I64, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -138,7 +147,10 @@ def load():
     lib.lcv_lpips_ws_bytes.argtypes = [I64, I64, I64]
     lib.lcv_det_ws_bytes.restype = c_int64           # likewise
     lib.lcv_det_ws_bytes.argtypes = [I, I64, I64, I64]
-    for name, args in list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items()):
+    lib.lcv_tn_skinny_dropout_ws_bytes.restype = c_int64   # likewise
+    lib.lcv_tn_skinny_dropout_ws_bytes.argtypes = [I64, I64, I64]
+    for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
+                       + list(_SIGNATURES_LORA.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

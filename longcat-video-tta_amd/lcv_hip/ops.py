@@ -271,6 +271,63 @@ def lora_down(x: torch.Tensor, A: torch.Tensor, s: float, rpad: int = 64) -> tor
     return h
 
 
+# ------------------------------------------------------------ LoRA dropout ---
+# include/lcv_hip_lora.h: the mask is a pure function of (seed, offset, global element index); `row0` is the global index of
+# the tensor's first row (0 unless the caller holds a slice of a larger matrix)
+_U64 = (1 << 64) - 1
+
+
+def lora_down_dropout(x: torch.Tensor, A: torch.Tensor, s: float, p: float, seed: int, offset: int, rpad: int = 64,
+                      row0: int = 0) -> torch.Tensor:
+    """h [M, rpad] = bf16(s * bf16(xd A^T)), xd = bf16(x * mask * scale), zero padded."""
+    _req(x, BF16, "lora_down_dropout.x"); _req(A, BF16, "lora_down_dropout.A")
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise _lib.LcvError("lora_down_dropout: x must be 2-D with contiguous rows")
+    M, K = x.shape
+    R = A.shape[0]
+    h = torch.empty((M, rpad), dtype=BF16, device=x.device)
+    call("lcv_lora_down_dropout", _ptr(x), _ptr(A.contiguous()), _ptr(h), M, K, R, rpad, x.stride(0), float(s), float(p),
+         int(seed) & _U64, int(offset) & _U64, int(row0), _stream())
+    return h
+
+
+def tn_skinny_dropout(g: torch.Tensor, x: torch.Tensor, R: int, p: float, seed: int, offset: int, scale: float = 1.0,
+                      row0: int = 0) -> torch.Tensor:
+    """out[R, K] fp32 = scale * g[:, :R]^T @ xd  (g [M, Rpad] bf16 contiguous, x [M, K] bf16): the mask sits on x."""
+    _req(g, BF16, "tn_skinny_dropout.g"); _req(x, BF16, "tn_skinny_dropout.x")
+    if x.dim() != 2 or x.stride(1) != 1 or not g.is_contiguous():
+        raise _lib.LcvError("tn_skinny_dropout: x must be 2-D with contiguous rows, g contiguous")
+    M, K = x.shape
+    out = torch.empty((R, K), dtype=F32, device=x.device)
+    ws_bytes = int(_lib.load().lcv_tn_skinny_dropout_ws_bytes(M, K, R))
+    ws = torch.empty((max(ws_bytes, 16) // 4,), dtype=F32, device=x.device)     # per-row-group partial sums (caching allocator)
+    call("lcv_tn_skinny_dropout", _ptr(g), _ptr(x), _ptr(out), M, K, R, g.shape[1], x.stride(0), float(scale), float(p),
+         int(seed) & _U64, int(offset) & _U64, int(row0), _ptr(ws), ws_bytes, _stream())
+    return out
+
+
+def lora_dx_dropout_add(dx: torch.Tensor, g: torch.Tensor, A: torch.Tensor, p: float, seed: int, offset: int,
+                        row0: int = 0) -> torch.Tensor:
+    """dx[m, k] = bf16(dx[m, k] + mask * scale * sum_r g[m, r] A[r, k]) in place (dx [M, K] bf16 contiguous,
+    g [M, Rpad] bf16, A [R, K] bf16); returns dx."""
+    _req(dx, BF16, "lora_dx_dropout_add.dx"); _req(g, BF16, "lora_dx_dropout_add.g"); _req(A, BF16, "lora_dx_dropout_add.A")
+    if dx.dim() != 2 or not dx.is_contiguous() or g.dim() != 2 or g.stride(1) != 1:
+        raise _lib.LcvError("lora_dx_dropout_add: dx must be 2-D contiguous, g 2-D with contiguous rows")
+    M, K = dx.shape
+    R = A.shape[0]
+    call("lcv_lora_dx_dropout_add", _ptr(dx), _ptr(g), _ptr(A.contiguous()), M, K, R, g.shape[1], g.stride(0), float(p),
+         int(seed) & _U64, int(offset) & _U64, int(row0), _stream())
+    return dx
+
+
+def lora_dropout_mask(M: int, K: int, p: float, seed: int, offset: int, row0: int = 0, device="cuda") -> torch.Tensor:
+    """The 0 / 1 mask of rows [row0, row0 + M) as uint8 [M, K]: what the three kernels above regenerate."""
+    out = torch.empty((M, K), dtype=torch.uint8, device=device)
+    _req(out, torch.uint8, "lora_dropout_mask.out")
+    call("lcv_lora_dropout_mask", _ptr(out), M, K, float(p), int(seed) & _U64, int(offset) & _U64, int(row0), _stream())
+    return out
+
+
 def swiglu(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     _req(gate, BF16, "swiglu.gate"); _req(up, BF16, "swiglu.up")
     rows, F = gate.shape

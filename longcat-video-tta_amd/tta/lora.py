@@ -4,9 +4,13 @@ Interface of lora_experiment/scripts/run_lora_tta.py:224-418 (class / function /
 = optimizer parameter order, `.pt` key names) on top of one fused kernel pair:
   forward   y  = x W^T + b + (s * bf16(x A^T)) B^T      one GEMM, the rank-r term is an extra 64-deep K step
   backward  dx = dy W + g A,  g = s * bf16(dy B);  dA = g^T x;  dB = s * dy^T bf16(x A^T)   (no dW: base frozen)
+With dropout p > 0 in train() the adapter sees xd = bf16(x * mask * scale) instead of x (run_lora_tta.py:249, 259).  The
+mask is a pure function of (seed, offset, element index) (include/lcv_hip_lora.h) and is regenerated where it is needed:
+  forward   hs = s * bf16(xd A^T) by lora_down_dropout, then the same GEMM
+  backward  dx = dy W (plain GEMM) + mask * scale * (g A) by lora_dx_dropout_add;  dA = g^T xd by tn_skinny_dropout
 """
 import math
-from typing import Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -50,6 +54,55 @@ class _LoRALinearFn(torch.autograd.Function):
         return dx, None, None, dA, dB, None
 
 
+class _LoRALinearDropoutFn(torch.autograd.Function):
+    """_LoRALinearFn with the mask of (seed, offset) on the adapter's input; g, dB and both GEMMs are the same calls."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, lora_a, lora_b, scaling, p, seed, offset):
+        R = lora_a.shape[0]
+        hs = ops.lora_down_dropout(x, lora_a, scaling, p, seed, offset, RPAD)   # [M, 64] = s * bf16(xd A^T), zero padded
+        bpad = torch.zeros((lora_b.shape[0], RPAD), dtype=lora_b.dtype, device=lora_b.device)
+        bpad[:, :R].copy_(lora_b.detach())
+        y = ops.gemm_nt(x, w, b, a2=hs, w2=bpad)
+        ctx.save_for_backward(x, w, lora_a, lora_b, hs)
+        ctx.scaling, ctx.draw = scaling, (p, seed, offset)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, lora_a, lora_b, hs = ctx.saved_tensors
+        if w.requires_grad:
+            raise LcvError("LoRALinear: the base weight must stay frozen (LoRA-only backward)")
+        s = ctx.scaling
+        p, seed, offset = ctx.draw
+        R = lora_a.shape[0]
+        dy = dy.contiguous()
+        g = ops.lora_down(dy, lora_b.detach().t().contiguous(), s, RPAD)   # [M, 64] = s * bf16(dy B)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.gemm_nt(dy, A.transposed_weight(w), None)
+            ops.lora_dx_dropout_add(dx, g, lora_a.detach(), p, seed, offset)   # dx += mask * scale * (g A), one rounding
+        dA = ops.tn_skinny_dropout(g, x, R, p, seed, offset).to(lora_a.dtype)  # [R, K] = g^T xd
+        dB = ops.tn_skinny(hs, dy, R).t().contiguous().to(lora_b.dtype)        # [N, R]; hs already carries s
+        return dx, None, None, dA, dB, None, None, None, None
+
+
+# Observer of the dropout draws: when set, called as DRAW_HOOK(module, seed, offset) for every training forward with p > 0
+# (a recomputed forward under gradient checkpointing included).  For tests and for debugging a run; None costs nothing.
+DRAW_HOOK: Optional[Callable] = None
+
+
+def draw_dropout_offset(device: torch.device) -> Tuple[int, int]:
+    """One (seed, offset) pair for one mask, from the device's default generator: its seed and its current Philox offset,
+    which is then advanced by 4 (the granularity the generator accepts).  Host-side state only: no device-to-host sync.  It
+    follows torch.manual_seed, and torch.utils.checkpoint's RNG preservation replays it for a recomputed block."""
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    gen = torch.cuda.default_generators[index]
+    seed, offset = gen.initial_seed(), gen.get_offset()
+    gen.set_offset(offset + 4)
+    return seed, offset
+
+
 class LoRALinear(nn.Module):
     """Low-rank adapter around an existing nn.Linear (frozen).  Output = original(x) + up(down(x)) * alpha / rank."""
 
@@ -76,11 +129,20 @@ class LoRALinear(nn.Module):
         return self.original.out_features
 
     def forward(self, x, *args, **kwargs):
-        if isinstance(self.dropout, nn.Dropout) and self.training and self.dropout.p > 0:
-            raise LcvError("LoRA dropout > 0 is not fused; the reference default is 0.0")
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
         x2 = x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)
+        if isinstance(self.dropout, nn.Dropout) and self.training and self.dropout.p > 0:
+            if self.dropout.p >= 1:
+                raise LcvError("LoRA dropout must be below 1")
+            if not x2.is_cuda:
+                raise LcvError("LoRALinear: tensor must live on the GPU (no CPU path exists)")
+            seed, offset = draw_dropout_offset(x2.device)
+            if DRAW_HOOK is not None:
+                DRAW_HOOK(self, seed, offset)
+            y = _LoRALinearDropoutFn.apply(x2.contiguous(), self.original.weight, self.original.bias, self.lora_down.weight,
+                                           self.lora_up.weight, self.scaling, float(self.dropout.p), seed, offset)
+            return y.view(*shp[:-1], self.original.out_features)
         y = _LoRALinearFn.apply(x2.contiguous(), self.original.weight, self.original.bias, self.lora_down.weight,
                                 self.lora_up.weight, self.scaling)
         return y.view(*shp[:-1], self.original.out_features)
