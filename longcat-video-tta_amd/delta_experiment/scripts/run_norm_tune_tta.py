@@ -24,6 +24,8 @@ def build_parser():
     p.add_argument("--norm-lr", type=float, default=1e-3)
     p.add_argument("--norm-target", type=str, default="all_norm", choices=["cross_attn_norm", "qk_norm", "all_norm"])
     p.add_argument("--also-tune-delta", action="store_true")
+    p.add_argument("--master-weights", action="store_true",
+                   help="fp32 master weights for the bf16 norm weights (include/lcv_hip_master.h)")
     R.add_shared_groups(p, clip_gate=False)
     return p
 
@@ -35,10 +37,12 @@ def main(argv=None):
         make_wrapper=lambda dit: NormTuneForward(dit, args.norm_target, also_tune_delta=args.also_tune_delta),
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_norm_params(
             w, w.tuned_params, cond, train, pe, pm, num_steps=args.norm_steps, lr=args.norm_lr, device=device, dtype=torch.bfloat16,
-            early_stopper=es, train_latents_variants=tv),
+            early_stopper=es, train_latents_variants=tv, master_weights=args.master_weights),
         params_of=lambda w: w.tuned_params,
         result_extra=lambda opt: {k: opt[k] for k in ("norm_param_drift", "delta_norm") if k in opt},
-        summary_head={"norm_target": args.norm_target, "norm_steps": args.norm_steps, "norm_lr": args.norm_lr},
+        # this runner writes no config.json (as the reference's does not): the flag is recorded here, when it is set
+        summary_head={"norm_target": args.norm_target, "norm_steps": args.norm_steps, "norm_lr": args.norm_lr,
+                      **({"master_weights": True} if args.master_weights else {})},
         file_suffix="norm_tune", cleanup=lambda w: w.restore())
 
 

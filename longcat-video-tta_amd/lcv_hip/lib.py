@@ -94,6 +94,15 @@ _SIGNATURES_LORA = {
     "lcv_lora_dropout_mask": [P, I64, I64, F64, U64, U64, I64, P],
 }
 
+# include/lcv_hip_master.h (a header of its own: fp32 master weights for bf16 parameters); `low` is a device array of pointers
+# to the int16 low words, parallel to the descriptor table; every function returns int
+_SIGNATURES_MASTER = {
+    "lcv_master_sgd_step": [P, P, I64, I64, P, F64, F64, P],
+    "lcv_master_adamw_step": [P, P, I64, I64, P, F64, F64, F64, F64, F64, I64, P],
+    "lcv_master_split": [P, P, P, I64, P],
+    "lcv_master_join": [P, P, P, I64, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -150,7 +159,7 @@ def load():
     lib.lcv_tn_skinny_dropout_ws_bytes.restype = c_int64   # likewise
     lib.lcv_tn_skinny_dropout_ws_bytes.argtypes = [I64, I64, I64]
     for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
-                       + list(_SIGNATURES_LORA.items())):
+                       + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

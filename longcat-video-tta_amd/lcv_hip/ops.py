@@ -598,11 +598,16 @@ class FusedAdamWClip:
     Mirrors `AdamW(lora_params, lr, betas=(0.9, 0.999), weight_decay, eps=1e-8)` +
     `clip_grad_norm_(lora_params, max_norm)` of lora_experiment/scripts/run_lora_tta.py:462-468, 513-514,
     including the bf16 rounding points of the foreach implementation.  `param_groups` is kept so the reference's
-    warm-up loop (`for pg in optimizer.param_groups: pg["lr"] = ...`) works unchanged."""
+    warm-up loop (`for pg in optimizer.param_groups: pg["lr"] = ...`) works unchanged.
+
+    `master_weights=True` (bf16 parameters only) gives every parameter element an int16 low word (include/lcv_hip_master.h):
+    the step then runs in fp32 on join(bf16 word, low word) with fp32 moments and rounds nothing to bf16 in between, so
+    updates below half a bf16 ulp accumulate instead of vanishing.  The bf16 words stay where every GEMM reads them.
+    Anyone else who writes the parameters (a restore, a reset) calls `resync()` afterwards."""
     CHUNK = 2048
     NORM_SLOTS = 64   # partial sums of squares per tensor (csrc/optim.hip)
 
-    def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-8):
+    def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-8, master_weights=False):
         self.params = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
@@ -611,8 +616,13 @@ class FusedAdamWClip:
             raise _lib.LcvError("FusedAdamWClip: parameters must be all bf16 or all fp32")
         self.f32 = dt == F32
         self.param_groups = [dict(params=self.params, lr=lr, betas=betas, weight_decay=weight_decay, eps=eps)]
-        self.exp_avg = [torch.zeros_like(p) for p in self.params]
-        self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+        self._init_master(master_weights)
+        if self.master_weights:      # fp32 moments: +8 B / parameter
+            self.exp_avg = [torch.zeros(p.shape, dtype=F32, device=p.device) for p in self.params]
+            self.exp_avg_sq = [torch.zeros(p.shape, dtype=F32, device=p.device) for p in self.params]
+        else:
+            self.exp_avg = [torch.zeros_like(p) for p in self.params]
+            self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
         self.step_count = 0
         dev = self.params[0].device
         self._ws = torch.zeros(len(self.params) * self.NORM_SLOTS, dtype=F32, device=dev)
@@ -620,6 +630,46 @@ class FusedAdamWClip:
         self._desc = None
         self._desc_key = None
         self._have_coef = False
+
+    def _init_master(self, master_weights: bool) -> None:
+        """Zeroed int16 low words (+2 B / parameter) when master weights are on; `f32` stays False for the clip (the
+        gradients are bf16, so a tensor's norm is still a bf16 number)."""
+        self.master_weights = bool(master_weights)
+        self._low = []
+        self._low_desc = None
+        if not self.master_weights:
+            return
+        name = type(self).__name__
+        if self.f32:
+            raise _lib.LcvError(f"{name}: master_weights=True is for bf16 parameters; fp32 parameters are already exact")
+        if any(not p.is_cuda for p in self.params):
+            raise _lib.LcvError(f"{name}: master_weights=True needs parameters on the GPU (no CPU path exists)")
+        if any(not p.is_contiguous() for p in self.params):
+            raise _lib.LcvError(f"{name}: master_weights=True needs contiguous parameters")
+        self._low = [torch.zeros(p.shape, dtype=torch.int16, device=p.device) for p in self.params]
+
+    @property
+    def low_words(self):
+        """The int16 low-word tensors, one per parameter in `params` order (empty without master weights)."""
+        return list(self._low)
+
+    def resync(self) -> None:
+        """Zero the low words: the masters become exactly the bf16 words the parameters hold now.  Call it after anyone
+        but this optimizer has written the parameters."""
+        for low in self._low:
+            low.zero_()
+
+    def master_tensors(self):
+        """fp32 copies of the masters, one per parameter (lcv_master_join)."""
+        if not self.master_weights:
+            raise _lib.LcvError(f"{type(self).__name__}: master_tensors() needs master_weights=True")
+        out = []
+        for p, low in zip(self.params, self._low):
+            m = torch.empty(p.shape, dtype=F32, device=p.device)
+            if p.numel():
+                call("lcv_master_join", _ptr(p), _ptr(low), _ptr(m), p.numel(), _stream())
+            out.append(m)
+        return out
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
@@ -645,6 +695,9 @@ class FusedAdamWClip:
                 rows.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), chunk])
                 chunk += (p.numel() + self.CHUNK - 1) // self.CHUNK
             self._desc = torch.tensor(rows, dtype=torch.int64).to(self.params[0].device)
+            if self.master_weights:      # the low-word pointers, parallel to the table
+                self._low_desc = torch.tensor([self._low[i].data_ptr() for i in sel],
+                                              dtype=torch.int64).to(self.params[0].device)
             self._total_chunks = chunk
             self._n_active = len(sel)
             self._desc_key = key
@@ -691,9 +744,14 @@ class FusedAdamWClip:
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
-        call("lcv_adamw_step", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
-             _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
-             float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
+        if self.master_weights:
+            call("lcv_master_adamw_step", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
+                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
+                 float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
+        else:
+            call("lcv_adamw_step", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
+                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
+                 float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
         self._have_coef = False
         global PARAM_EPOCH
         PARAM_EPOCH += 1
@@ -1008,9 +1066,10 @@ def gelu_tanh_bwd(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
 
 class FusedSGDClip(FusedAdamWClip):
     """clip_grad_norm_ + SGD(momentum=0, weight_decay).step over a parameter list in two launches — the default
-    optimizer of full-model TTA (lora_experiment/scripts/run_full_tta.py:138-144, 179-180).  No optimizer state."""
+    optimizer of full-model TTA (lora_experiment/scripts/run_full_tta.py:138-144, 179-180).  No optimizer state, unless
+    `master_weights=True` adds the int16 low words of FusedAdamWClip's master-weight form (+2 B / parameter)."""
 
-    def __init__(self, params, lr=1e-5, weight_decay=0.01):
+    def __init__(self, params, lr=1e-5, weight_decay=0.01, master_weights=False):
         self.params = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
@@ -1019,6 +1078,7 @@ class FusedSGDClip(FusedAdamWClip):
             raise _lib.LcvError("FusedSGDClip: parameters must be all bf16 or all fp32")
         self.f32 = dt == F32
         self.param_groups = [dict(params=self.params, lr=lr, weight_decay=weight_decay)]
+        self._init_master(master_weights)
         self.exp_avg = self.params            # the descriptor table has moment slots; SGD never reads them
         self.exp_avg_sq = self.params
         self.step_count = 0
@@ -1033,8 +1093,12 @@ class FusedSGDClip(FusedAdamWClip):
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
-        call("lcv_sgd_step", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
-             _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
+        if self.master_weights:
+            call("lcv_master_sgd_step", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
+                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
+        else:
+            call("lcv_sgd_step", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
+                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
         self._have_coef = False
         global PARAM_EPOCH
         PARAM_EPOCH += 1

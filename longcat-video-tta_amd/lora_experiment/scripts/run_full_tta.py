@@ -39,6 +39,8 @@ def build_parser():
     p.add_argument("--weight-decay", type=float, default=0.01)
     p.add_argument("--max-grad-norm", type=float, default=1.0)
     p.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "adamw"])
+    p.add_argument("--master-weights", action="store_true",
+                   help="fp32 master weights: +2 B / parameter of low words, fp32 moments under adamw (include/lcv_hip_master.h)")
     p.add_argument("--batch-videos", type=int, default=1)
     p.add_argument("--batch-method", type=str, default="similarity", choices=["similarity", "sequential"])
     p.add_argument("--retrieval-pool-dir", type=str, default=None)
@@ -78,6 +80,7 @@ def main(argv=None):
             "method": "full_tta",
             "training": {"learning_rate": args.learning_rate, "num_steps": args.num_steps, "warmup_steps": args.warmup_steps,
                          "weight_decay": args.weight_decay, "max_grad_norm": args.max_grad_norm, "optimizer": args.optimizer,
+                         "master_weights": args.master_weights,
                          "total_params": total_params, "trainable_params": trainable_params},
             "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                            "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
@@ -115,7 +118,8 @@ def main(argv=None):
             tr = finetune_full_on_conditioning(dit, cond, train, pe, pm, num_steps=args.num_steps, lr=args.learning_rate,
                                                warmup_steps=args.warmup_steps, weight_decay=args.weight_decay,
                                                max_grad_norm=args.max_grad_norm, device=device, dtype=torch.bfloat16,
-                                               early_stopper=es, optimizer_type=args.optimizer, train_latents_variants=variants)
+                                               early_stopper=es, optimizer_type=args.optimizer, train_latents_variants=variants,
+                                               master_weights=args.master_weights)
             result = {"idx": idx, "video_name": e["name"], "video_path": e["path"], "caption": blob.get("caption", ""),
                       "train_time": tr["train_time"], "es_check_time": tr.get("es_check_time", 0.0),
                       "final_loss": tr["losses"][-1] if tr["losses"] else None, "num_train_steps": len(tr["losses"]),

@@ -64,6 +64,8 @@ def build_parser():
     p.add_argument("--warmup-steps", type=int, default=3)
     p.add_argument("--weight-decay", type=float, default=0.01)
     p.add_argument("--max-grad-norm", type=float, default=1.0)
+    p.add_argument("--master-weights", action="store_true",
+                   help="fp32 master weights for the bf16 adapters (include/lcv_hip_master.h); both LoRA implementations")
     p.add_argument("--max-videos", type=int, default=100)
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--device", type=str, default="cuda")
@@ -151,7 +153,7 @@ def main(argv=None):
                      "num_modules": len(lora_modules), "trainable_params": counts["trainable"]},
             "training": {"learning_rate": args.learning_rate, "num_steps": args.num_steps,
                          "warmup_steps": args.warmup_steps, "weight_decay": args.weight_decay,
-                         "max_grad_norm": args.max_grad_norm},
+                         "max_grad_norm": args.max_grad_norm, "master_weights": args.master_weights},
             "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                            "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
                            "resolution": args.resolution},
@@ -191,7 +193,8 @@ def main(argv=None):
                                                num_steps=args.num_steps, lr=args.learning_rate,
                                                warmup_steps=args.warmup_steps, weight_decay=args.weight_decay,
                                                max_grad_norm=args.max_grad_norm, device=device, dtype=torch.bfloat16,
-                                               early_stopper=es, lora_param_fn=get_params, train_latents_variants=variants)
+                                               early_stopper=es, lora_param_fn=get_params, train_latents_variants=variants,
+                                               master_weights=args.master_weights)
             result = {"idx": idx, "video_name": e["name"], "video_path": e["path"], "caption": blob.get("caption", ""),
                       "train_time": tr["train_time"], "es_check_time": tr.get("es_check_time", 0.0),
                       "final_loss": tr["losses"][-1] if tr["losses"] else None, "num_train_steps": len(tr["losses"]),
