@@ -1,0 +1,58 @@
+// What the master-weight optimizer kernels share (optim_master.hip, optim_moments8.hip): the (bf16 word, int16 low word) <->
+// fp32 master format, AdamW's scalars and its per-element op sequence.  Both files are built with -ffp-contract=off.
+#pragma once
+#include "optim_common.h"
+#include <math.h>
+
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+
+// Every fp32 operation below is one correctly rounded IEEE operation and stays one: contraction is off for the including file,
+// and the arithmetic is written with plain operators.  (hipcc's __fmul_rn / __fadd_rn are `x * y` / `x + y` compiled under the
+// default -ffp-contract=fast, so a product and the sum that takes it may still fuse into one fma; its __fsqrt_rn is the
+// 1-ulp native square root.  `/` and __builtin_sqrtf are the correctly rounded forms, hipcc's default for fp32.)
+#pragma clang fp contract(off)
+
+__device__ __forceinline__ float master_join(bf16_t h, short l) {
+  return __builtin_bit_cast(float, ((unsigned int)h << 16) + (unsigned int)(int)l);
+}
+// h: round to nearest bf16, ties away from zero; l: what is left, in [-32768, 32767].  Integer arithmetic mod 2^32.
+__device__ __forceinline__ void master_split(float w, bf16_t& h, short& l) {
+  const unsigned int m = __builtin_bit_cast(unsigned int, w);
+  const unsigned int hh = (m + 0x8000u) >> 16;
+  h = (bf16_t)hh;
+  l = (short)(unsigned short)(m - (hh << 16));
+}
+
+struct MasterAdamScalars {
+  float c_wd, w1, b2, c2, bc2_sqrt, eps, step_size;
+};
+
+// scalars formed in double exactly as lcv_adamw_step (torch/optim/adamw.py) forms them, then narrowed to fp32
+static inline MasterAdamScalars master_adam_scalars(double lr, double beta1, double beta2, double eps, double weight_decay,
+                                                    int64_t step) {
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  MasterAdamScalars sc;
+  sc.c_wd = (float)(1.0 - lr * weight_decay);
+  sc.w1 = (float)(1.0 - beta1);
+  sc.b2 = (float)beta2;
+  sc.c2 = (float)(1.0 - beta2);
+  sc.bc2_sqrt = (float)sqrt(bc2);
+  sc.eps = (float)eps;
+  sc.step_size = (float)((lr / bc1) * -1.0);
+  return sc;
+}
+
+// the fp32 op sequence of adamw_kernel<true> (optim.hip), each operation correctly rounded; p, m, v in and out
+__device__ __forceinline__ void master_adamw_elem(float& p, float& m, float& v, float g, float coef, const MasterAdamScalars& s) {
+  g = g * coef;
+  p = p * s.c_wd;
+  const float dm = s.w1 * (g - m);
+  m = m + dm;
+  v = v * s.b2;
+  const float dv = (s.c2 * g) * g;
+  v = v + dv;
+  const float d = __builtin_sqrtf(v) / s.bc2_sqrt + s.eps;
+  const float dp = s.step_size * (m / d);
+  p = p + dp;
+}

@@ -2,27 +2,7 @@
 // second tensor, join(h, l) is an fp32 number, and the optimizer steps run on that number with no bf16 rounding in between.
 // Same descriptor table, chunking (optim_common.h) and 16-byte packet / scalar-tail split as optim.hip.  HBM-bound streaming
 // kernels: SGD 6 B read + 4 B written per parameter (4 + 2 for the rounding form), AdamW 14 + 12.
-#include "optim_common.h"
-#include <math.h>
-
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-
-// Every fp32 operation below is one correctly rounded IEEE operation and stays one: contraction is off for this file, and the
-// arithmetic is written with plain operators.  (hipcc's __fmul_rn / __fadd_rn are `x * y` / `x + y` compiled under the
-// default -ffp-contract=fast, so a product and the sum that takes it may still fuse into one fma; its __fsqrt_rn is the
-// 1-ulp native square root.  `/` and __builtin_sqrtf are the correctly rounded forms, hipcc's default for fp32.)
-#pragma clang fp contract(off)
-
-__device__ __forceinline__ float master_join(bf16_t h, short l) {
-  return __builtin_bit_cast(float, ((unsigned int)h << 16) + (unsigned int)(int)l);
-}
-// h: round to nearest bf16, ties away from zero; l: what is left, in [-32768, 32767].  Integer arithmetic mod 2^32.
-__device__ __forceinline__ void master_split(float w, bf16_t& h, short& l) {
-  const unsigned int m = __builtin_bit_cast(unsigned int, w);
-  const unsigned int hh = (m + 0x8000u) >> 16;
-  h = (bf16_t)hh;
-  l = (short)(unsigned short)(m - (hh << 16));
-}
+#include "master_elem.h"   // join, split, AdamW's scalars and per-element op sequence (shared with optim_moments8.hip)
 
 __device__ __forceinline__ float master_sgd_elem(float w, float g, float coef, float lr, float wd) {
   g = g * coef;
@@ -65,24 +45,6 @@ __global__ __launch_bounds__(256) void master_sgd_kernel(const lcv_adam_tensor* 
     const float w = master_sgd_elem(master_join(P[i], L[i]), bf2f(G[i]), coef, lr, wd);
     master_split(w, P[i], L[i]);
   }
-}
-
-struct MasterAdamScalars {
-  float c_wd, w1, b2, c2, bc2_sqrt, eps, step_size;
-};
-
-// the fp32 op sequence of adamw_kernel<true> (optim.hip), each operation correctly rounded; p, m, v in and out
-__device__ __forceinline__ void master_adamw_elem(float& p, float& m, float& v, float g, float coef, const MasterAdamScalars& s) {
-  g = g * coef;
-  p = p * s.c_wd;
-  const float dm = s.w1 * (g - m);
-  m = m + dm;
-  v = v * s.b2;
-  const float dv = (s.c2 * g) * g;
-  v = v + dv;
-  const float d = __builtin_sqrtf(v) / s.bc2_sqrt + s.eps;
-  const float dp = s.step_size * (m / d);
-  p = p + dp;
 }
 
 __global__ __launch_bounds__(256) void master_adamw_kernel(const lcv_adam_tensor* __restrict__ tensors, void* const* __restrict__ low,
@@ -181,17 +143,7 @@ extern "C" int lcv_master_adamw_step(const lcv_adam_tensor* tensors, void* const
                                      double weight_decay, int64_t step, void* stream) {
   LCV_CHECK_ARG(tensors && low && n_tensors > 0 && n_tensors <= 0x7fffffff && total_chunks > 0 && total_chunks <= 0x7fffffff &&
                     step >= 1, "master_adamw_step: bad arguments");
-  // scalars formed in double exactly as lcv_adamw_step (torch/optim/adamw.py) forms them, then narrowed to fp32
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  MasterAdamScalars sc;
-  sc.c_wd = (float)(1.0 - lr * weight_decay);
-  sc.w1 = (float)(1.0 - beta1);
-  sc.b2 = (float)beta2;
-  sc.c2 = (float)(1.0 - beta2);
-  sc.bc2_sqrt = (float)sqrt(bc2);
-  sc.eps = (float)eps;
-  sc.step_size = (float)((lr / bc1) * -1.0);
+  const MasterAdamScalars sc = master_adam_scalars(lr, beta1, beta2, eps, weight_decay, step);
   hipLaunchKernelGGL(master_adamw_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, tensors, low,
                      (int)n_tensors, norm_coef, sc);
   LCV_LAUNCH_CHECK("master_adamw_step");

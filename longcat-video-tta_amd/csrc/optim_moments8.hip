@@ -1,0 +1,259 @@
+// 8-bit block-scaled AdamW moments for master weights (include/lcv_hip_moments8.h): one byte per moment per parameter plus one
+// fp32 scale per moment per 512 parameters, the second moment stored as its root.  Same descriptor table, chunking and
+// thread-to-element mapping as optim_master.hip: a thread owns 8 consecutive elements (one 16-byte bf16 packet), so a wave
+// owns 512 = one block, and a workgroup's CHUNK is four blocks.  The block maxima are a wave_max over registers: no LDS, no
+// atomics, and a max does not depend on the order it is taken in.  HBM-bound: 8 B read + 6 B written per parameter.
+#include "master_elem.h"   // join, split, AdamW's scalars and per-element op sequence; contraction off from there on
+#include "lcv_hip_moments8.h"
+
+typedef unsigned char u8_t;
+static constexpr int M8_BLOCK = LCV_MOMENTS8_BLOCK;
+static_assert(M8_BLOCK == LCV_WAVE * 8 && CHUNK == 4 * M8_BLOCK, "one block per wave, four per chunk");
+
+// ---- the codes ----
+// round to 3 mantissa bits, ties away from zero, the carry runs into the exponent: sign(0) | exponent(8) | mantissa(3)
+__device__ __forceinline__ unsigned int m8_k(float z) { return (__builtin_bit_cast(unsigned int, z) + 0x80000u) >> 20; }
+
+__device__ __forceinline__ unsigned int m8_encode_m(float m, float sm) {
+  const float x = sm == 0.f ? 0.f : __builtin_fabsf(m) / sm;
+  const unsigned int k = m8_k(x);
+  if (x == 0.f || k < 890u) return 0u;                                   // flushed to +0: no sign
+  const unsigned int mag = k - 889u < 127u ? k - 889u : 127u;
+  return mag | ((__builtin_bit_cast(unsigned int, m) >> 31) << 7);
+}
+__device__ __forceinline__ unsigned int m8_encode_r(float r, float sr) {
+  const float y = sr == 0.f ? 0.f : r / sr;
+  if (y == 0.f) return 0u;
+  const int c = (int)m8_k(y) - 761;
+  return (unsigned int)(c < 1 ? 1 : (c > 255 ? 255 : c));                // clamped up, never flushed
+}
+__device__ __forceinline__ float m8_decode_m(unsigned int c, float sm) {
+  const unsigned int mag = c & 127u;
+  const float x = mag ? __builtin_bit_cast(float, (mag + 889u) << 20) : 0.f;
+  const float a = x * sm;
+  return (c & 128u) ? -a : a;
+}
+__device__ __forceinline__ float m8_decode_v(unsigned int c, float sr) {
+  const float y = c ? __builtin_bit_cast(float, (c + 761u) << 20) : 0.f;
+  const float r = y * sr;
+  return r * r;
+}
+
+// ---- a thread's 8 codes: one 8-byte packet, or byte by byte for the first nvalid ----
+__device__ __forceinline__ void m8_load_codes(const u8_t* C, int64_t base, bool packet, int nvalid, unsigned int (&c)[8]) {
+  if (packet) {
+    const u32x2 w = *reinterpret_cast<const u32x2*>(C + base);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) c[e] = (w[e >> 2] >> (8 * (e & 3))) & 255u;
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) c[e] = e < nvalid ? C[base + e] : 0u;
+}
+__device__ __forceinline__ void m8_store_codes(u8_t* C, int64_t base, bool packet, int nvalid, const unsigned int (&c)[8]) {
+  if (packet) {
+    u32x2 w;
+    w[0] = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+    w[1] = c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24);
+    *reinterpret_cast<u32x2*>(C + base) = w;
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    if (e < nvalid) C[base + e] = (u8_t)c[e];
+}
+
+// Encode a thread's 8 fresh moments (missing elements are m = r = 0: they add 0 to the maxima and store nothing) and store
+// codes and scales.  Every lane of the wave that owns block `blk` calls this; the scales go out from lane 0.
+__device__ __forceinline__ void m8_encode_store(const float (&m)[8], const float (&r)[8], u8_t* CM, u8_t* CR, float* S,
+                                                int64_t nblocks, int64_t blk, int64_t base, bool packet, int nvalid) {
+  float am = 0.f, ar = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    am = fmaxf(am, __builtin_fabsf(m[e]));
+    ar = fmaxf(ar, r[e]);
+  }
+  const float sm = wave_max(am), sr = wave_max(ar);
+  unsigned int cm[8], cr[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    cm[e] = m8_encode_m(m[e], sm);
+    cr[e] = m8_encode_r(r[e], sr);
+  }
+  m8_store_codes(CM, base, packet, nvalid, cm);
+  m8_store_codes(CR, base, packet, nvalid, cr);
+  if ((threadIdx.x & (LCV_WAVE - 1)) == 0) {
+    S[blk] = sm;
+    S[nblocks + blk] = sr;
+  }
+}
+
+// elements of this thread that exist: 8, fewer in a tensor's last packet, 0 past it
+__device__ __forceinline__ int m8_nvalid(int64_t base, int64_t numel) {
+  const int64_t left = numel - base;
+  return left >= 8 ? 8 : (left > 0 ? (int)left : 0);
+}
+
+__global__ __launch_bounds__(256) void master_adamw8_kernel(const lcv_adam_tensor* __restrict__ tensors, void* const* __restrict__ low,
+                                                            void* const* __restrict__ scales, int n, const float* __restrict__ clip,
+                                                            const MasterAdamScalars s) {
+  const int ti = find_tensor(tensors, n, blockIdx.x);
+  const lcv_adam_tensor t = tensors[ti];
+  const int64_t chunk0 = ((int64_t)blockIdx.x - t.first_chunk) * CHUNK;
+  const int64_t wave0 = chunk0 + (int64_t)(threadIdx.x & ~(LCV_WAVE - 1)) * 8;      // where this wave's block starts
+  if (wave0 >= t.numel) return;                                                     // the whole wave: no such block
+  const int64_t base = chunk0 + threadIdx.x * 8;
+  const int64_t nblocks = (t.numel + M8_BLOCK - 1) / M8_BLOCK, blk = wave0 / M8_BLOCK;
+  const float coef = clip ? clip[1] : 1.0f;
+  bf16_t* P = (bf16_t*)t.param;
+  short* L = (short*)low[ti];
+  const bf16_t* G = (const bf16_t*)t.grad;
+  u8_t* CM = (u8_t*)t.exp_avg;
+  u8_t* CR = (u8_t*)t.exp_avg_sq;
+  float* S = (float*)scales[ti];
+  const float sm0 = S[blk], sr0 = S[nblocks + blk];
+  const int nvalid = m8_nvalid(base, t.numel);
+  // whole packets: 16 bytes of h, l and g, 8 bytes of each code
+  const bool packet = nvalid == 8 && ((((uintptr_t)P) | ((uintptr_t)G) | ((uintptr_t)L)) & 15) == 0 &&
+                      ((((uintptr_t)CM) | ((uintptr_t)CR)) & 7) == 0;
+  u16x8 hv, gv;
+  s16x8 lv;
+  unsigned int cm[8], cr[8];
+  if (packet) {
+    hv = *reinterpret_cast<const u16x8*>(P + base);
+    lv = *reinterpret_cast<const s16x8*>(L + base);
+    gv = *reinterpret_cast<const u16x8*>(G + base);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const bool in = e < nvalid;
+      hv[e] = in ? P[base + e] : (bf16_t)0;
+      lv[e] = in ? L[base + e] : (short)0;
+      gv[e] = in ? G[base + e] : (bf16_t)0;
+    }
+  }
+  m8_load_codes(CM, base, packet, nvalid, cm);
+  m8_load_codes(CR, base, packet, nvalid, cr);
+  float m[8], r[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    m[e] = 0.f; r[e] = 0.f;
+    if (e < nvalid) {
+      float p = master_join(hv[e], lv[e]), v = m8_decode_v(cr[e], sr0);
+      m[e] = m8_decode_m(cm[e], sm0);
+      master_adamw_elem(p, m[e], v, bf2f(gv[e]), coef, s);      // the update uses the fp32 moments, before they are quantised
+      bf16_t h; short l;
+      master_split(p, h, l);
+      hv[e] = h; lv[e] = l;
+      r[e] = __builtin_sqrtf(v);                                // the root the step took
+    }
+  }
+  if (packet) {
+    *reinterpret_cast<u16x8*>(P + base) = hv;
+    *reinterpret_cast<s16x8*>(L + base) = lv;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (e < nvalid) { P[base + e] = hv[e]; L[base + e] = lv[e]; }
+  }
+  m8_encode_store(m, r, CM, CR, S, nblocks, blk, base, packet, nvalid);
+}
+
+// one tensor, fp32 moments -> codes and scales.  One workgroup per CHUNK elements.
+__global__ __launch_bounds__(256) void moments8_encode_kernel(const float* __restrict__ M, const float* __restrict__ V, u8_t* __restrict__ CM,
+                                                              u8_t* __restrict__ CR, float* __restrict__ S, int64_t n) {
+  const int64_t chunk0 = (int64_t)blockIdx.x * CHUNK;
+  const int64_t wave0 = chunk0 + (int64_t)(threadIdx.x & ~(LCV_WAVE - 1)) * 8;
+  if (wave0 >= n) return;
+  const int64_t base = chunk0 + threadIdx.x * 8;
+  const int nvalid = m8_nvalid(base, n);
+  const bool packet = nvalid == 8 && ((((uintptr_t)M) | ((uintptr_t)V)) & 15) == 0 && ((((uintptr_t)CM) | ((uintptr_t)CR)) & 7) == 0;
+  float m[8], r[8];
+  if (packet) {
+    const f32x4 m0 = *reinterpret_cast<const f32x4*>(M + base), m1 = *reinterpret_cast<const f32x4*>(M + base + 4);
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(V + base), v1 = *reinterpret_cast<const f32x4*>(V + base + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      m[e] = m0[e]; m[e + 4] = m1[e];
+      r[e] = __builtin_sqrtf(v0[e]); r[e + 4] = __builtin_sqrtf(v1[e]);
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      m[e] = e < nvalid ? M[base + e] : 0.f;
+      r[e] = e < nvalid ? __builtin_sqrtf(V[base + e]) : 0.f;
+    }
+  }
+  m8_encode_store(m, r, CM, CR, S, (n + M8_BLOCK - 1) / M8_BLOCK, wave0 / M8_BLOCK, base, packet, nvalid);
+}
+
+__global__ __launch_bounds__(256) void moments8_decode_kernel(const u8_t* __restrict__ CM, const u8_t* __restrict__ CR,
+                                                              const float* __restrict__ S, float* __restrict__ M, float* __restrict__ V,
+                                                              int64_t n) {
+  const int64_t base = (int64_t)blockIdx.x * CHUNK + threadIdx.x * 8;
+  const int nvalid = m8_nvalid(base, n);
+  if (nvalid == 0) return;
+  const int64_t nblocks = (n + M8_BLOCK - 1) / M8_BLOCK, blk = base / M8_BLOCK;
+  const float sm = S[blk], sr = S[nblocks + blk];
+  const bool packet = nvalid == 8 && ((((uintptr_t)M) | ((uintptr_t)V)) & 15) == 0 && ((((uintptr_t)CM) | ((uintptr_t)CR)) & 7) == 0;
+  unsigned int cm[8], cr[8];
+  m8_load_codes(CM, base, packet, nvalid, cm);
+  m8_load_codes(CR, base, packet, nvalid, cr);
+  if (packet) {
+    f32x4 m0, m1, v0, v1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      m0[e] = m8_decode_m(cm[e], sm); m1[e] = m8_decode_m(cm[e + 4], sm);
+      v0[e] = m8_decode_v(cr[e], sr); v1[e] = m8_decode_v(cr[e + 4], sr);
+    }
+    *reinterpret_cast<f32x4*>(M + base) = m0; *reinterpret_cast<f32x4*>(M + base + 4) = m1;
+    *reinterpret_cast<f32x4*>(V + base) = v0; *reinterpret_cast<f32x4*>(V + base + 4) = v1;
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    if (e < nvalid) {
+      M[base + e] = m8_decode_m(cm[e], sm);
+      V[base + e] = m8_decode_v(cr[e], sr);
+    }
+}
+
+extern "C" int lcv_master_adamw8_step(const lcv_adam_tensor* tensors, void* const* low, void* const* scales, int64_t n_tensors,
+                                      int64_t total_chunks, const float* norm_coef, double lr, double beta1, double beta2,
+                                      double eps, double weight_decay, int64_t step, void* stream) {
+  LCV_CHECK_ARG(tensors && low && scales && n_tensors > 0 && n_tensors <= 0x7fffffff && total_chunks > 0 &&
+                    total_chunks <= 0x7fffffff && step >= 1, "master_adamw8_step: bad arguments");
+  const MasterAdamScalars sc = master_adam_scalars(lr, beta1, beta2, eps, weight_decay, step);
+  hipLaunchKernelGGL(master_adamw8_kernel, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, tensors, low, scales,
+                     (int)n_tensors, norm_coef, sc);
+  LCV_LAUNCH_CHECK("master_adamw8_step");
+  return LCV_OK;
+}
+
+static bool moments8_grid(int64_t n, unsigned& blocks) {
+  if (n < 1) return false;
+  const int64_t b = (n + CHUNK - 1) / CHUNK;
+  if (b > 0x7fffffff) return false;
+  blocks = (unsigned)b;
+  return true;
+}
+
+extern "C" int lcv_moments8_encode(const float* m_f32, const float* v_f32, void* cm, void* cr, float* scales, int64_t n,
+                                   void* stream) {
+  unsigned blocks = 0;
+  LCV_CHECK_ARG(m_f32 && v_f32 && cm && cr && scales && moments8_grid(n, blocks), "moments8_encode: bad arguments");
+  hipLaunchKernelGGL(moments8_encode_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, m_f32, v_f32, (u8_t*)cm, (u8_t*)cr,
+                     scales, n);
+  LCV_LAUNCH_CHECK("moments8_encode");
+  return LCV_OK;
+}
+
+extern "C" int lcv_moments8_decode(const void* cm, const void* cr, const float* scales, float* m_f32, float* v_f32, int64_t n,
+                                   void* stream) {
+  unsigned blocks = 0;
+  LCV_CHECK_ARG(m_f32 && v_f32 && cm && cr && scales && moments8_grid(n, blocks), "moments8_decode: bad arguments");
+  hipLaunchKernelGGL(moments8_decode_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const u8_t*)cm, (const u8_t*)cr,
+                     scales, m_f32, v_f32, n);
+  LCV_LAUNCH_CHECK("moments8_decode");
+  return LCV_OK;
+}

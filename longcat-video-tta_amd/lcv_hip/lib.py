@@ -103,6 +103,14 @@ _SIGNATURES_MASTER = {
     "lcv_master_join": [P, P, P, I64, P],
 }
 
+# include/lcv_hip_moments8.h (a header of its own: 8-bit block-scaled AdamW moments for master weights); `scales` of the step is
+# a device array of pointers to fp32 [2][ceil(numel/512)], parallel to the descriptor table; every function returns int
+_SIGNATURES_MOMENTS8 = {
+    "lcv_master_adamw8_step": [P, P, P, I64, I64, P, F64, F64, F64, F64, F64, I64, P],
+    "lcv_moments8_encode": [P, P, P, P, P, I64, P],
+    "lcv_moments8_decode": [P, P, P, P, P, I64, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -159,7 +167,7 @@ def load():
     lib.lcv_tn_skinny_dropout_ws_bytes.restype = c_int64   # likewise
     lib.lcv_tn_skinny_dropout_ws_bytes.argtypes = [I64, I64, I64]
     for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
-                       + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items())):
+                       + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

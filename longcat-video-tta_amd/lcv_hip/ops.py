@@ -603,11 +603,18 @@ class FusedAdamWClip:
     `master_weights=True` (bf16 parameters only) gives every parameter element an int16 low word (include/lcv_hip_master.h):
     the step then runs in fp32 on join(bf16 word, low word) with fp32 moments and rounds nothing to bf16 in between, so
     updates below half a bf16 ulp accumulate instead of vanishing.  The bf16 words stay where every GEMM reads them.
-    Anyone else who writes the parameters (a restore, a reset) calls `resync()` afterwards."""
+    Anyone else who writes the parameters (a restore, a reset) calls `resync()` afterwards.
+
+    `moments_8bit=True` (with `master_weights=True` only) keeps each moment in one byte per element plus one fp32 scale per
+    moment per 512 elements (include/lcv_hip_moments8.h): about 2.016 B / parameter of moments instead of 8.  The parameter
+    update still uses the fp32 moments of the step; only what is kept between steps is quantised."""
     CHUNK = 2048
     NORM_SLOTS = 64   # partial sums of squares per tensor (csrc/optim.hip)
+    MOMENTS8_BLOCK = 512   # elements per scale (LCV_MOMENTS8_BLOCK)
+    moments_8bit = False
 
-    def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-8, master_weights=False):
+    def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-8, master_weights=False,
+                 moments_8bit=False):
         self.params = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
@@ -617,7 +624,18 @@ class FusedAdamWClip:
         self.f32 = dt == F32
         self.param_groups = [dict(params=self.params, lr=lr, betas=betas, weight_decay=weight_decay, eps=eps)]
         self._init_master(master_weights)
-        if self.master_weights:      # fp32 moments: +8 B / parameter
+        self.moments_8bit = bool(moments_8bit)
+        self._scales = []
+        self._scale_desc = None
+        if self.moments_8bit:        # uint8 codes and fp32 block scales, zeroed: the state "all moments zero"
+            if not self.master_weights:
+                raise _lib.LcvError("FusedAdamWClip: moments_8bit=True needs master_weights=True (the 8-bit moments exist "
+                                    "for the master-weight step only)")
+            self.exp_avg = [torch.zeros(p.shape, dtype=torch.uint8, device=p.device) for p in self.params]
+            self.exp_avg_sq = [torch.zeros(p.shape, dtype=torch.uint8, device=p.device) for p in self.params]
+            self._scales = [torch.zeros((2, (p.numel() + self.MOMENTS8_BLOCK - 1) // self.MOMENTS8_BLOCK), dtype=F32,
+                                        device=p.device) for p in self.params]
+        elif self.master_weights:    # fp32 moments: +8 B / parameter
             self.exp_avg = [torch.zeros(p.shape, dtype=F32, device=p.device) for p in self.params]
             self.exp_avg_sq = [torch.zeros(p.shape, dtype=F32, device=p.device) for p in self.params]
         else:
@@ -671,6 +689,26 @@ class FusedAdamWClip:
             out.append(m)
         return out
 
+    def moment_tensors(self):
+        """fp32 copies of the moments, one (exp_avg, exp_avg_sq) pair per parameter; decoded (lcv_moments8_decode) under
+        moments_8bit=True."""
+        out = []
+        for i, p in enumerate(self.params):
+            if not self.moments_8bit:
+                out.append((self.exp_avg[i].to(F32, copy=True), self.exp_avg_sq[i].to(F32, copy=True)))
+                continue
+            m = torch.zeros(p.shape, dtype=F32, device=p.device)
+            v = torch.zeros(p.shape, dtype=F32, device=p.device)
+            if p.numel():
+                call("lcv_moments8_decode", _ptr(self.exp_avg[i]), _ptr(self.exp_avg_sq[i]), _ptr(self._scales[i]), _ptr(m),
+                     _ptr(v), p.numel(), _stream())
+            out.append((m, v))
+        return out
+
+    def state_bytes(self) -> int:
+        """Bytes of optimizer state: both moments and, under moments_8bit=True, their scales.  The low words are not counted."""
+        return sum(t.numel() * t.element_size() for ts in (self.exp_avg, self.exp_avg_sq, self._scales) for t in ts)
+
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
             p.grad = None if set_to_none else (p.grad.zero_() if p.grad is not None else None)
@@ -698,6 +736,9 @@ class FusedAdamWClip:
             if self.master_weights:      # the low-word pointers, parallel to the table
                 self._low_desc = torch.tensor([self._low[i].data_ptr() for i in sel],
                                               dtype=torch.int64).to(self.params[0].device)
+            if self.moments_8bit:        # and the block-scale pointers
+                self._scale_desc = torch.tensor([self._scales[i].data_ptr() for i in sel],
+                                                dtype=torch.int64).to(self.params[0].device)
             self._total_chunks = chunk
             self._n_active = len(sel)
             self._desc_key = key
@@ -744,7 +785,11 @@ class FusedAdamWClip:
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
-        if self.master_weights:
+        if self.moments_8bit:
+            call("lcv_master_adamw8_step", _ptr(d), _ptr(self._low_desc), _ptr(self._scale_desc), self._n_active,
+                 self._total_chunks, _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
+                 float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
+        elif self.master_weights:
             call("lcv_master_adamw_step", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
                  _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
                  float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
@@ -1081,6 +1126,7 @@ class FusedSGDClip(FusedAdamWClip):
         self._init_master(master_weights)
         self.exp_avg = self.params            # the descriptor table has moment slots; SGD never reads them
         self.exp_avg_sq = self.params
+        self._scales = []
         self.step_count = 0
         dev = self.params[0].device
         self._ws = torch.zeros(len(self.params) * self.NORM_SLOTS, dtype=F32, device=dev)
@@ -1088,6 +1134,12 @@ class FusedSGDClip(FusedAdamWClip):
         self._desc = None
         self._desc_key = None
         self._have_coef = False
+
+    def moment_tensors(self):
+        raise _lib.LcvError("FusedSGDClip: SGD (momentum 0) keeps no moments")
+
+    def state_bytes(self) -> int:
+        return 0
 
     def step(self):
         d = self._descriptors()

@@ -79,6 +79,22 @@ def add_clip_gate_args(parser):
     return parser
 
 
+def add_adam_8bit_arg(parser):
+    parser.add_argument("--adam-8bit", action="store_true",
+                        help="with --master-weights: AdamW moments in 1 B each plus block scales, about 2.016 B / parameter "
+                             "instead of 8 (include/lcv_hip_moments8.h)")
+
+
+def parse_with_adam_8bit(parser, argv=None):
+    """parse_args, then the two refusals of --adam-8bit as the parser's own one-line errors (exit status 2)."""
+    args = parser.parse_args(argv)
+    if args.adam_8bit and not args.master_weights:
+        parser.error("--adam-8bit needs --master-weights (the 8-bit moments exist for the master-weight AdamW step only)")
+    if args.adam_8bit and getattr(args, "optimizer", "adamw") != "adamw":
+        parser.error("--adam-8bit needs --optimizer adamw (SGD keeps no moments)")
+    return args
+
+
 def normalize_tta_frame_args(args):
     """Post-parse normalisation of lora_experiment/scripts/run_lora_tta.py:743-758 (GT-leak clamp included)."""
     if args.tta_total_frames is None:

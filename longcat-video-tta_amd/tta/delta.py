@@ -219,12 +219,13 @@ class FiLMAdapterWrapper(_HookedWrapper):
 
 def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bool, cond_latents, train_latents,
               prompt_embeds, prompt_mask, num_steps, lr, device, dtype, early_stopper, train_latents_variants,
-              master_weights=False):
+              master_weights=False, moments_8bit=False):
     """AdamW(0.9, 0.999, wd 0.01, eps 1e-15), clip at 1.0, no warm-up (run_delta_a.py:224-305 and its siblings) on the
     shared engine.  Clipping comes in the three shapes the reference scripts use: per parameter (delta-B,
     run_delta_b.py:386-388), one global norm, or — bf16 norm weights tuned together with an fp32 delta vector — one fused
     optimizer per dtype tied by a joint clip coefficient.  `master_weights` goes to the bf16 optimizers only (fp32
-    parameters are already exact); the optimizers are made per call, so per video, and their low words start at zero."""
+    parameters are already exact), and so does `moments_8bit` (the norm-tuning path only); the optimizers are made per call, so
+    per video, and their low words start at zero."""
     joint = False
     if per_param_clip:
         groups = [[p] for p in params]
@@ -234,7 +235,8 @@ def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bo
     else:
         groups = [params]
     opts = [FusedAdamWClip(g, lr=lr, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-15,
-                           master_weights=master_weights and g[0].dtype == torch.bfloat16) for g in groups]
+                           master_weights=master_weights and g[0].dtype == torch.bfloat16,
+                           moments_8bit=moments_8bit and g[0].dtype == torch.bfloat16) for g in groups]
 
     def clip_and_step():
         live = [o for o in opts if any(p.grad is not None for p in o.params)]
@@ -379,14 +381,15 @@ class NormTuneForward(nn.Module):
 def optimize_norm_params(wrapper: NormTuneForward, norm_params: List[nn.Parameter], cond_latents, train_latents, prompt_embeds,
                          prompt_mask, num_steps: int = 20, lr: float = 1e-3, device: str = "cuda",
                          dtype: torch.dtype = torch.bfloat16, early_stopper: Optional[AnchoredEarlyStopper] = None,
-                         train_latents_variants: Optional[List[Dict]] = None, master_weights: bool = False) -> Dict:
+                         train_latents_variants: Optional[List[Dict]] = None, *, moments_8bit: bool = False,
+                         master_weights: bool = False) -> Dict:
     """run_norm_tune_tta.py:215-283 (same positional order: the parameter list is the second argument): AdamW(eps 1e-15) over
     `norm_params` (bf16 norm weights, plus the fp32 delta vector of --also-tune-delta), one global clip at 1.0.  Returns the
     reference's keys (`losses`, `early_stopping_info`) and, beside them, the check time and how far the parameters moved."""
     norm_params = list(norm_params)
     losses, est, es_state = _optimize(wrapper, norm_params, False, cond_latents, train_latents, prompt_embeds,
                                       prompt_mask, num_steps, lr, device, dtype, early_stopper, train_latents_variants,
-                                      master_weights=master_weights)
+                                      master_weights=master_weights, moments_8bit=moments_8bit)
     out = {"losses": losses, "early_stopping_info": es_state, "es_check_time": est}
     if getattr(wrapper, "_orig", None) and len(wrapper._orig) == len(wrapper.norm_params):
         out["norm_param_drift"] = sum((p.detach().float() - o.float()).norm().item() for p, o in zip(wrapper.norm_params, wrapper._orig))

@@ -209,11 +209,11 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
                                   device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                                   early_stopper: Optional[AnchoredEarlyStopper] = None, lora_param_fn=None,
                                   train_latents_variants: Optional[List[Dict]] = None,
-                                  master_weights: bool = False) -> Dict:
+                                  *, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     params = _adapter_params(lora_modules, lora_param_fn)
     # made per call, so per video: the low words of `master_weights` start at zero next to freshly reset adapters
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
-                         master_weights=master_weights)
+                         master_weights=master_weights, moments_8bit=moments_8bit)
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
     return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
                           num_steps, lr, warmup_steps, early_stopper, grad_sync=_sp_sync(dit, opt))
@@ -222,11 +222,11 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
 def finetune_lora_batch(dit: nn.Module, lora_modules, batch_data: List[Dict], num_steps: int = 20, lr: float = 2e-4,
                         warmup_steps: int = 3, weight_decay: float = 0.01, max_grad_norm: float = 1.0,
                         device: str = "cuda", dtype: torch.dtype = torch.bfloat16, lora_param_fn=None,
-                        master_weights: bool = False) -> Dict:
+                        *, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Shared adapters trained round-robin over the eval video and its neighbours; no early stopping (:558-634)."""
     params = _adapter_params(lora_modules, lora_param_fn)
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
-                         master_weights=master_weights)
+                         master_weights=master_weights, moments_8bit=moments_8bit)
     feed = _RoundRobin(batch_data, device)
     return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
                           num_steps, lr, warmup_steps, None, grad_sync=_sp_sync(dit, opt))
