@@ -1,5 +1,6 @@
-"""float64 restatements of the HBM-bound kernels of the C ABI (norms, glue, VAE helpers, dense-gradient helpers) and the
-per-element check they are held to in tests/test_gpu_kernel_edges.py.  A plain helper module (compare tests/delta_cases.py):
+"""float64 restatements of the HBM-bound kernels of the C ABI (norms, glue, VAE helpers, dense-gradient helpers; the LoRA,
+SwiGLU-backward, q/k-norm and UMT5 kernels) and the per-element check they are held to in tests/test_gpu_kernel_edges.py and
+tests/test_gpu_{lora,bwd,umt5}_kernel_edges.py.  A plain helper module (compare tests/delta_cases.py):
 nothing here calls the product's ops; every restatement is the formula of the kernel's header comment (include/lcv_hip.h)
 evaluated in float64 with torch, on whatever device its inputs live on.
 
@@ -24,6 +25,22 @@ Tolerance rule.  Every bound below is derived from this rule, never tuned to pas
   4. fp32 elementwise updates (euler_step, cfg_euler_step): <= 2 fp32 ulps of the float64 value, since hipcc may contract
      x += dt*v into an FMA (lcv_hip/build.py passes no -ffp-contract flag), plus the rule-1 floor u * |dt*v| where x and
      dt*v cancel (the product's own rounding, when it is not contracted).
+  5. Chains of bf16 roundings (lora_down: bf16(s * bf16(x A^T)); t5_rmsnorm: bf16(w * bf16(x rstd)); the q/k norm:
+     bf16(bf16(x r) * w), then RoPE, then one rounding; geglu: bf16(bf16(gelu(g)) * up); the T5 attention's probabilities).
+     The kernel's fp32 value v' in front of an INNER rounding differs from the float64 value v by its fp32 error delta (a few
+     u |v|, or depth * u * sum|terms| after a reduction), so it may round to the other bf16 neighbour:
+         |bf16(v') - bf16(v)| <= delta + ulp_bf16(|v| + delta)                                   (`inner_rounding_err`)
+     (half an ulp of each rounding; the ulp is taken at |v| + delta because v' may lie one binade up).  Each inner rounding
+     contributes that much, and the contribution is carried LINEARLY to the output through the float64 partial derivatives of
+     what follows it (|s|, |w|, |cos| + |sin|, |v_j| ...); an error that enters a further inner rounding is that rounding's
+     delta.  On top come the outer rounding's 1 ulp (rule 1) and, after a reduction, depth * u * sum|terms| (rule 3) with
+     depth the kernel's own summation tree, stated next to each check.  Where the fp32 error in front of the inner rounding is
+     purely relative (no cancellation), the tighter statement of rule 1 is used instead: the other neighbour is admissible
+     only near a midpoint (`bf16_neighbours` / `alt`: swiglu_bwd's dup, the attention's probabilities).
+
+The `check_*` functions below hold the restatement, the derived bound and the assert of one entry point each, so that the GPU
+tests (the kernel's result) and the CPU tests of tests/test_kernel_ref.py (deliberately wrong float64 "results") go through
+the very same assert.
 
 `assert_within` fails on the WORST element and names its index, value, reference and bound; the worst ratio of error to
 bound is also recorded in conftest's parity log (the kernel_parity.json of a GPU run), so that tolerances can later be
@@ -181,3 +198,253 @@ def rownorm_bwd(x, dy, mul, eps: float):
     g = f64(dy) * mul
     dx = rstd * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
     return dx, xh, rstd, g
+
+
+# ------------------------------------------------------------------------------- rule 5 and the entry points held to it
+def bf16r(v):
+    """One bf16 rounding point (round to nearest even), back in float64."""
+    return v.to(torch.bfloat16).to(torch.float64)
+
+
+def inner_rounding_err(v, delta=0.0):
+    """Rule 5: a bound on |bf16(v') - bf16(v)| for any v' with |v' - v| <= delta."""
+    v = f64(v).abs()
+    return delta + bf16_ulp(v + delta)
+
+
+def silu_grad(x):
+    """d/dx of x * sigmoid(x): sig * (1 + x * (1 - sig))."""
+    x = f64(x)
+    sig = 1.0 / (1.0 + torch.exp(-x))
+    return sig * (1.0 + x * (1.0 - sig))
+
+
+def silu_grad_err(x):
+    """Bound on the fp32 error of f = sig * (1 + x * (1 - sig)), sig = 1 / (1 + __expf(-x)) (swiglu_bwd, silu_grad_kernel).
+    es = (|x| + 4) u is sig's relative error (the exponent argument's rounding |x| u, __expf, 1 + e, the division).  1 - sig
+    carries sig * es + u (1 - sig); times x and rounded: |x| (sig es + 2 u (1 - sig)); 1 + that is rounded: u |inner|.  The
+    outer product multiplies inner's error by sig and adds (es + u) |f|.  Where sig lies below fp32's normal range (x < -87.3:
+    __expf(-x) overflows past 88.7, and a subnormal 1 / (1 + e) may be flushed) the kernel's sig may be 0: es = 1 there."""
+    x = f64(x)
+    sig = 1.0 / (1.0 + torch.exp(-x))
+    inner = 1.0 + x * (1.0 - sig)
+    es = (x.abs() + 4) * U
+    es = torch.where(sig < 2.0 ** -126, torch.ones_like(es), es)
+    return sig * (x.abs() * (sig * es + 2 * U * (1.0 - sig)) + U * inner.abs()) + (es + U) * (sig * inner).abs()
+
+
+# ---- lcv_tn_skinny
+def tn_skinny_rpb(M: int, K: int):
+    """tn_skinny_rpb of csrc/elementwise_bwd.hip: rows per workgroup and the number of row groups (grid.y)."""
+    groups = 64 if (K + 511) // 512 <= 8 else 32
+    rpb = ((M + groups - 1) // groups + 31) // 32 * 32
+    rpb = max(64, min(rpb, 1024))
+    return rpb, (M + rpb - 1) // rpb
+
+
+def tn_tail_row(g, x, R: int):
+    """Make the last row heavy, in place: g[M-1, :R] = 16, x[M-1, :] = -16.  Rule 3's bound grows with depth * sum|terms|; at
+    M = 66 000 (depth 325) it is about as large as one ordinary row's product, so a kernel that lost its tail row would pass.
+    A product of 256 is hundreds of times that bound at every shape of the tests and adds < 1 % to sum|terms|."""
+    g[-1, :R] = 16.0
+    x[-1, :] = -16.0
+
+
+def check_tn_skinny(got, g, x, R: int, scale: float, what: str):
+    """out[r, k] = scale * sum_m g[m, r] x[m, k], fp32.  g [M, Rpad] (columns >= R are never read), x [M, K] (a view)."""
+    M, K = x.shape
+    gf, xf = f64(g)[:, :R], f64(x)
+    ref = scale * (gf.t() @ xf)
+    rpb, groups = tn_skinny_rpb(M, K)
+    # rule 3.  Workspace path: a wave's fma chain over its rpb / 4 rows, 3 adds for the other waves' partials, then the row
+    # groups in order; + 1 for the multiplication by scale.  Atomic path: the same count of additions in another order.
+    depth = rpb // 4 + 3 + groups + 1
+    return assert_within(got, ref, 0.0, depth * U * abs(scale) * (gf.abs().t() @ xf.abs()), fmt="fp32", what=what)
+
+
+# ---- lcv_lora_down
+def check_lora_down(got, x, A, R: int, Rpad: int, s: float, what: str):
+    """h[M, Rpad] = bf16(s * bf16(x A^T)), columns R..Rpad-1 exactly +0.  x [M, K] (a view), A [R, K]."""
+    K = x.shape[1]
+    xf, Af = f64(x), f64(A)[:R]
+    t = xf @ Af.t()
+    ref = torch.zeros(x.shape[0], Rpad, dtype=torch.float64, device=x.device)
+    ref[:, :R] = s * bf16r(t)
+    # rule 5.  t' is an fp32 sum: each lane's chain of 8 products per 512 columns, then a 6-level wave tree (rule 3) ->
+    # delta; the inner rounding's share is carried to h by |s|; the outer rounding is assert_within's 1 ulp
+    delta = (8 * math.ceil(K / 512) + 6) * U * (xf.abs() @ Af.abs().t())
+    floor = torch.zeros_like(ref)
+    floor[:, :R] = abs(s) * inner_rounding_err(t, delta)
+    worst = assert_within(got, ref, 1.0, floor, what=what)
+    pad = got.detach()[:, R:].cpu()
+    assert (pad.view(torch.int16) == 0).all(), f"{what}: a pad column is not +0"
+    return worst
+
+
+# ---- lcv_linear_f32_smallm_bwd
+def check_linear_f32_smallm_bwd(got, dy, w, a, act_in: int, what: str):
+    """da[M, K] fp32 = act_in'(a) * (dy[M, N] @ w[N, K])."""
+    N = dy.shape[1]
+    acc, terms = f64(dy) @ f64(w), f64(dy).abs() @ f64(w).abs()
+    # rule 3: the thread's chain over one 256-row slab of w, then one atomic per slab
+    depth = 256 + math.ceil(N / 256)
+    if not act_in:
+        return assert_within(got, acc, 0.0, depth * U * terms, fmt="fp32", what=what)
+    f = silu_grad(a)
+    # the SiLU derivative on top: |f| times the sum's error, the factor's own fp32 error (silu_grad_err) times |sum|, and
+    # the rounding of the product (assert_within's 1 fp32 ulp)
+    return assert_within(got, f * acc, 1.0, f.abs() * depth * U * terms + silu_grad_err(a) * acc.abs(), fmt="fp32", what=what)
+
+
+# ---- lcv_swiglu_bwd / lcv_swiglu_bwd_interleaved
+def swiglu_il_index(F: int, device=None):
+    """The fused layout of lcv_swiglu_bwd_interleaved: per 64 columns 32 gate values, then their 32 up partners.
+    -> (columns of gate feature 0..F-1, columns of up feature 0..F-1) in a [rows, 2F] row."""
+    c = torch.arange(F, device=device)
+    gate = (c // 32) * 64 + c % 32
+    return gate, gate + 32
+
+
+def check_swiglu_bwd(dgate, dup, gate, up, dout, what: str):
+    """dup = bf16(dout * bf16(silu(g))), dgate = bf16(dout * up * silu'(g))."""
+    gf, uf, df = f64(gate), f64(up), f64(dout)
+    # dup, rule 1 with `alt`: silu(g) = g * sig has the relative error (|g| + 4) u of sig (see silu_grad_err) and no
+    # cancellation, so only next to a midpoint may the inner rounding take the other neighbour
+    s, s_alt = bf16_neighbours(silu(gf), (gf.abs() + 4) * U)
+    w0 = assert_within(dup, df * s, 1.0, alt=df * s_alt, what=f"{what} dup")
+    # dgate, rule 1: one rounding; silu'(g) cancels (it is 0 at g = -1.278): floor |dout up| * silu_grad_err(g), + 2 u |ref|
+    # for the two products in front
+    ref = df * uf * silu_grad(gf)
+    w1 = assert_within(dgate, ref, 1.0, (df * uf).abs() * silu_grad_err(gf) + 2 * U * ref.abs(), what=f"{what} dgate")
+    return max(w0, w1)
+
+
+# ---- lcv_qknorm_rope_fwd / _bwd
+def _rope_pairs(t):
+    return t[..., 0::2], t[..., 1::2]
+
+
+def _interleave(a, b):
+    return torch.stack([a, b], dim=-1).flatten(-2)
+
+
+def check_qknorm_rope_fwd(got, x, w, cs, eps: float, scale: float, what: str):
+    """y = bf16(scale * rope(bf16(bf16(x r) * w))), r = rsqrt(mean(x^2) + eps) over D = 128; rope on interleaved pairs:
+    (y0, y1) = (n0 c - n1 s, n1 c + n0 s).  x [B, N, H, 128], w [128], cs [N, 64, 2] (the rows of the tokens) or None."""
+    xf, wf = f64(x), f64(w)
+    r = 1.0 / torch.sqrt((xf * xf).mean(-1, keepdim=True) + eps)
+    v1 = xf * r
+    n1 = bf16r(v1)
+    v2 = n1 * wf
+    n2 = bf16r(v2)
+    # rule 5.  First inner rounding: r's fp32 error is 16 u relative (8-element chain + 4 shuffle levels for the sum, the
+    # division by 128 is exact, + eps, rsqrtf <= 2 ulp), + u for x * r.  Second inner rounding: its input carries the
+    # first's error times |w| (+ u |v2| for the product).
+    e1 = inner_rounding_err(v1, 17 * U * v1.abs())
+    e2 = inner_rounding_err(v2, e1 * wf.abs() + U * v2.abs())
+    if cs is None:
+        ref, floor = n2 * scale, e2 * scale
+    else:
+        c, s = f64(cs)[None, :, None, :, 0], f64(cs)[None, :, None, :, 1]
+        a0, a1 = _rope_pairs(n2)
+        f0, f1 = _rope_pairs(e2)
+        ref = _interleave(a0 * c - a1 * s, a1 * c + a0 * s) * scale
+        # carried through the rotation by |cos| and |sin|; the rotation itself is three fp32 roundings of terms that may
+        # cancel: 2 u (|n0 c| + |n1 s|) (rule 1's floor); the product with scale is inside assert_within's 1 ulp
+        floor = (_interleave(f0 * c.abs() + f1 * s.abs(), f1 * c.abs() + f0 * s.abs())
+                 + 2 * U * _interleave((a0 * c).abs() + (a1 * s).abs(), (a1 * c).abs() + (a0 * s).abs())) * scale
+    return assert_within(got, ref, 1.0, floor, what=what)
+
+
+def qknorm_rope_bwd(x, dout, w, cs, eps: float, scale: float):
+    """The backward the kernel states (weights enter as in the forward without its inner roundings): d = scale * dout,
+    t = rope^T(d) = (d0 c + d1 s, d1 c - d0 s), dn = t w, n = x r, dx = r (dn - n mean(dn n)), dw = sum_{b, token, head} t n.
+    -> dx, dw [128] and the intermediates the bounds need."""
+    xf, wf, d = f64(x), f64(w), f64(dout) * scale
+    r = 1.0 / torch.sqrt((xf * xf).mean(-1, keepdim=True) + eps)
+    n = xf * r
+    if cs is None:
+        t, tmag = d, d.abs()
+    else:
+        c, s = f64(cs)[None, :, None, :, 0], f64(cs)[None, :, None, :, 1]
+        d0, d1 = _rope_pairs(d)
+        t = _interleave(d0 * c + d1 * s, d1 * c - d0 * s)
+        m = (d0 * c).abs() + (d1 * s).abs(), (d1 * c).abs() + (d0 * s).abs()
+        tmag = _interleave(*m)
+    dn = t * wf
+    dot = (dn * n).mean(-1, keepdim=True)
+    dx = r * (dn - n * dot)
+    return dx, (t * n).sum((0, 1, 2)), dict(r=r, n=n, t=t, tmag=tmag, dn=dn, dot=dot, w=wf)
+
+
+def check_qknorm_rope_bwd(dx_got, dw_got, x, dout, w, cs, eps: float, scale: float, what: str):
+    """dx_got [B, N, H, 128] bf16; dw_got (or None): fp32 [dw_slots, 128] as the kernel left it, summed here over its slots."""
+    dx, dw, m = qknorm_rope_bwd(x, dout, w, cs, eps, scale)
+    r, n, t, tmag, dn, dot, wf = (m[k] for k in ("r", "n", "t", "tmag", "dn", "dot", "w"))
+    # fp32 errors of the pieces: t = rope^T(scale * dout) is a sum of two rounded products that may cancel: 3 u tmag;
+    # dn = t w: + u |dn|; n = x r: r's 16 u (see the forward) + u
+    et = 3 * U * tmag
+    edn = et * wf.abs() + U * dn.abs()
+    en = 17 * U * n.abs()
+    # the dot: rule 3 at depth 12 (8-element chain + 4 shuffle levels) over |dn n| / 128, the errors of its factors, its own
+    # rounding by the multiplication with 1/128
+    edot = 12 * U * (dn * n).abs().mean(-1, keepdim=True) + (edn * n.abs() + dn.abs() * en).mean(-1, keepdim=True) + U * dot.abs()
+    # rule 1 with the cancellation floor for r (dn - n dot): the errors that enter the difference, the roundings of n * dot
+    # and of the difference (2 u of the magnitudes), all times r; r's own relative error and the last product on the result
+    floor = r * (edn + en * dot.abs() + n.abs() * edot + 2 * U * (dn.abs() + (n * dot).abs())) + 18 * U * dx.abs()
+    worst = assert_within(dx_got, dx, 1.0, floor, what=f"{what} dx")
+    if dw_got is not None:
+        B, N, H, _ = x.shape
+        # rule 3 with atomics: B N H terms per channel (every token and head adds once); the terms' own errors on top
+        terms = (t * n).abs().sum((0, 1, 2))
+        own = (et * n.abs() + t.abs() * en + U * (t * n).abs()).sum((0, 1, 2))
+        worst = max(worst, assert_within(f64(dw_got).sum(0), dw, 0.0, B * N * H * U * terms + own, fmt="fp32", what=f"{what} dw"))
+    return worst
+
+
+# ---- lcv_t5_rmsnorm, lcv_geglu_tanh_fwd
+def check_t5_rmsnorm(got, x, w, eps: float, what: str):
+    """y = bf16(w * bf16(x * rsqrt(mean(x^2) + eps)))."""
+    C = x.shape[-1]
+    xf, wf = f64(x), f64(w)
+    v = xf / torch.sqrt((xf * xf).mean(-1, keepdim=True) + eps)
+    # rule 5: rstd's relative error is (8 ceil(C / 512) + 6 + 4) u (the lane's fma chain, the wave tree; the division, + eps,
+    # rsqrtf), + u for x * rstd; the inner rounding's share is carried by |w|
+    delta = (8 * math.ceil(C / 512) + 6 + 4 + 1) * U * v.abs()
+    return assert_within(got, wf * bf16r(v), 1.0, wf.abs() * inner_rounding_err(v, delta), what=what)
+
+
+def check_geglu_tanh(got, gate, up, what: str):
+    """out = bf16(bf16(gelu_new(gate)) * up)."""
+    gf, uf = f64(gate), f64(up)
+    v = gelu_tanh(gf)
+    # rule 5, not `alt`: 0.5 g (1 + tanh) cancels at g << 0, where the fp32 error 4 u |g| (tanhf <= 2 ulp, two roundings: the
+    # floor of the gelu_tanh_fwd test) spans many bf16 neighbours of a tiny gelu(g); it is carried to the output by |up|
+    return assert_within(got, bf16r(v) * uf, 1.0, uf.abs() * inner_rounding_err(v, 4 * U * gf.abs()), what=what)
+
+
+# ---- lcv_t5_attention
+def check_t5_attention(got, q, k, v, bias, mask, what: str):
+    """out[b, i, h, :] = bf16(sum_j bf16(p_ij) v_j), p = softmax_j(bf16(bf16(q_i . k_j) + bias[h, j - i + S - 1])) over the keys
+    with mask[b, j] != 0; a row without a valid key is exactly 0.  q, k, v [B, S, H, 64]; bias [H, 2S - 1]; mask [B, S]."""
+    B, S, H, _ = q.shape
+    Spad = (S + 63) // 64 * 64
+    qf, kf, vf = (f64(t).permute(0, 2, 1, 3) for t in (q, k, v))                  # [B, H, S, 64]
+    i = torch.arange(S, device=q.device)
+    dist = i[None, :] - i[:, None] + S - 1                                         # [query i, key j] -> j - i + S - 1
+    sc = bf16r(bf16r(qf @ kf.transpose(-1, -2)) + f64(bias)[:, dist][None])        # [B, H, S, S]
+    valid = (mask != 0)[:, None, None, :].expand_as(sc)
+    sc = torch.where(valid, sc, torch.full_like(sc, -math.inf))
+    mx = sc.amax(-1, keepdim=True)
+    e = torch.where(valid, torch.exp(sc - torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx))), torch.zeros_like(sc))
+    den = e.sum(-1, keepdim=True)
+    p = torch.where(den > 0, e / den.clamp_min(1e-300), torch.zeros_like(e))
+    # the probabilities, rule 1 with `alt`: the tests' scores are exact, so p' differs from p by the fp32 softmax alone,
+    # relatively: (|x| + 2) u for __expf(x), |x| <= 16; 14 u for the sum of positive terms (8 per lane + 6 wave levels);
+    # 2 u for 1 / sum and the product: 34 u.  Only next to a midpoint may bf16(p') be the other neighbour.
+    pb, pb_alt = bf16_neighbours(p, 34 * U)
+    ref = (pb @ vf).permute(0, 2, 1, 3)
+    # each probability that may round the other way moves the output by |pb_alt - pb| |v_j| (rule 5's linear carry); the PV
+    # sum is one fma chain over the Spad staged keys (rule 3, depth Spad); the output's rounding is assert_within's 1 ulp
+    floor = (((pb_alt - pb).abs() + Spad * U * pb) @ vf.abs()).permute(0, 2, 1, 3)
+    return assert_within(got, ref, 1.0, floor, what=what)

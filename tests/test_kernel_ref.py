@@ -1,5 +1,6 @@
 """CPU: the per-element check of tests/kernel_ref.py is sensitive enough to be worth its GPU time (one element 2 bf16 ulps
-off fails, one non-zero pad element fails, the exact rounding passes), and every compute entry point that include/lcv_hip.h
+off fails, one non-zero pad element fails, the exact rounding passes; every check_* of rule 5 passes a result computed another
+way and fails the results a kernel bug would give), and every compute entry point that include/lcv_hip.h
 declares has a kernel-level test (the coverage guard: a new entry point without one fails here, without a GPU)."""
 import ast
 import re
@@ -13,6 +14,9 @@ import kernel_ref as K
 ROOT = Path(__file__).resolve().parents[1]
 TESTS = ROOT / "tests"
 EDGES = "test_gpu_kernel_edges.py"
+LORA_EDGES = "test_gpu_lora_kernel_edges.py"
+BWD_EDGES = "test_gpu_bwd_kernel_edges.py"
+UMT5_EDGES = "test_gpu_umt5_kernel_edges.py"
 
 
 # ------------------------------------------------------------------------------------------------ assert_within itself
@@ -110,6 +114,294 @@ def test_restatements_match_the_formulas_at_hand_values():
     assert torch.allclose(dx, xr.grad, rtol=1e-10, atol=1e-12)
 
 
+# -------------------------------------------------------- rule 5 and the check_* functions: hand values, autograd, teeth
+# Each check_* of kernel_ref is fed (a) a result computed HERE in another way (autograd, torch.nn.functional, complex
+# multiplication for the rotation), rounded where the kernel rounds: it must pass; (b) deliberately wrong float64 "results"
+# of the kind a kernel bug produces: each must fail.  (b) is the proof that the derived bounds are not vacuous.
+BF16 = torch.bfloat16
+F = torch.nn.functional
+
+
+def _g(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _rn(*shape, seed, scale=1.0, dtype=BF16):
+    return (torch.randn(*shape, generator=_g(seed), dtype=torch.float64) * scale).to(dtype)
+
+
+def _fails(fn, *args):
+    with pytest.raises(AssertionError):
+        fn(*args, "wrong on purpose")
+
+
+def test_inner_rounding_err_bounds_the_two_roundings():
+    v = _ref(20000, seed=3)
+    delta = v.abs() * 2.0 ** -10 * torch.rand(v.shape, generator=_g(4), dtype=torch.float64)
+    for sign in (-1.0, 1.0):
+        moved = K.bf16r(v + sign * delta)
+        assert ((moved - K.bf16r(v)).abs() <= K.inner_rounding_err(v, delta)).all()
+    # and it is not slack beyond the rule: delta + one ulp at |v| + delta
+    assert torch.equal(K.inner_rounding_err(torch.tensor([1.0, 1.99]), 0.02), 0.02 + torch.tensor([2.0 ** -7, 2.0 ** -6], dtype=torch.float64))
+
+
+def test_silu_grad_and_the_interleaved_index_map():
+    t = torch.linspace(-12, 12, 97, dtype=torch.float64).requires_grad_(True)
+    F.silu(t).sum().backward()
+    assert torch.allclose(K.silu_grad(t.detach()), t.grad, rtol=1e-13, atol=1e-15)
+    assert abs(float(K.silu_grad(torch.tensor([0.0]))) - 0.5) < 1e-15 and abs(float(K.silu_grad(torch.tensor([-1.2784645427610738], dtype=torch.float64)))) < 1e-12
+    # the error bound is a few u where nothing cancels and stays finite in saturation
+    e = K.silu_grad_err(torch.tensor([0.0, 30.0, -30.0, 100.0, -100.0]))
+    assert torch.isfinite(e).all() and 2 * K.U < float(e[0]) < 8 * K.U
+    # 32 gate columns, then their 32 up partners, per 64 columns
+    gi, ui = K.swiglu_il_index(96)
+    assert gi.tolist() == list(range(0, 32)) + list(range(64, 96)) + list(range(128, 160))
+    assert ui.tolist() == list(range(32, 64)) + list(range(96, 128)) + list(range(160, 192))
+    assert sorted(gi.tolist() + ui.tolist()) == list(range(192))
+    assert K.tn_skinny_rpb(1, 8) == (64, 1) and K.tn_skinny_rpb(4097, 520) == (96, 43)
+    assert K.tn_skinny_rpb(66000, 8) == (1024, 65) and K.tn_skinny_rpb(2049, 4104) == (96, 22)
+
+
+def test_tn_skinny_check_has_teeth():
+    M, K_, R, Rpad, scale = 70, 24, 5, 8, 0.5
+    g, x = _rn(M, Rpad, seed=10), _rn(M, K_, seed=11)
+
+    def out(gm, xm):
+        return (scale * gm.double().t() @ xm.double()).float()
+    K.check_tn_skinny(out(g[:, :R], x), g, x, R, scale, "right")
+    _fails(K.check_tn_skinny, out(g[:-1, :R], x[:-1]), g, x, R, scale)                 # the last row dropped
+    _fails(K.check_tn_skinny, out(g[:, 1: R + 1], x), g, x, R, scale)                  # the rank columns shifted by one
+    _fails(K.check_tn_skinny, out(g[:, :R], x) * 2, g, x, R, scale)                    # accumulated twice into a non-zero out
+    # at the row-group cap (depth 325 over 66 000 terms) an ordinary tail row is below rule 3's bound; the GPU cases therefore
+    # end on a heavy row (`tn_tail_row`), which is not
+    M, K_, R = 66000, 8, 32
+    g, x = _rn(M, R, seed=30), _rn(M, K_, seed=31)
+    rpb, groups = K.tn_skinny_rpb(M, K_)
+    bound = (rpb // 4 + 3 + groups + 1) * K.U * (g.double().abs().t() @ x.double().abs())      # check_tn_skinny's, at scale 1
+    assert ((g[-1].double()[:, None] * x[-1].double()[None, :]).abs() < bound).any()   # the ordinary tail row could hide
+    K.tn_tail_row(g, x, R)
+    K.check_tn_skinny(out(g, x), g, x, R, scale, "right, heavy tail")
+    _fails(K.check_tn_skinny, out(g[:-1], x[:-1]), g, x, R, scale)                     # the last row dropped
+    assert ((g[-1].double()[:, None] * x[-1].double()[None, :]).abs() > 100 * bound).all()
+
+
+def test_lora_down_check_has_teeth():
+    M, K_, R, Rpad, s = 6, 1032, 9, 16, 0.37
+    x, A = _rn(M, K_, seed=12), _rn(R, K_, seed=13, scale=0.5)
+
+    def out(Am):
+        h = torch.zeros(M, Rpad, dtype=BF16)
+        h[:, :Am.shape[0]] = (s * (x.double() @ Am.double().t()).to(BF16).double()).to(BF16)
+        return h
+    right = out(A)
+    K.check_lora_down(right, x, A, R, Rpad, s, "right")
+    stale = right.clone()
+    stale[3, R] = 2.0 ** -100
+    _fails(K.check_lora_down, stale, x, A, R, Rpad, s)                                 # one pad column left stale
+    negz = right.clone()
+    negz[0, Rpad - 1] = -0.0
+    _fails(K.check_lora_down, negz, x, A, R, Rpad, s)                                  # the pad is +0, not -0
+    _fails(K.check_lora_down, out(A.roll(1, 0)), x, A, R, Rpad, s)                     # a rank column shifted by one
+    last = right.clone()
+    last[M - 1] = right[M - 2]
+    _fails(K.check_lora_down, last, x, A, R, Rpad, s)                                  # the last row computed from the row before
+    _fails(K.check_lora_down, (right.double() / s).to(BF16), x, A, R, Rpad, s)         # s forgotten
+
+
+def test_linear_f32_smallm_bwd_check_against_autograd_and_teeth():
+    M, N, K_ = 5, 300, 34
+    dy, a = _rn(M, N, seed=14, dtype=torch.float32), _rn(M, K_, seed=15, scale=2.0, dtype=torch.float32)
+    w = _rn(N, K_, seed=16, scale=0.5)
+    for act in (0, 1):
+        ad = a.double().requires_grad_(True)
+        ((F.silu(ad) if act else ad) @ w.double().t() * dy.double()).sum().backward()
+        K.check_linear_f32_smallm_bwd(ad.grad.float(), dy, w, a, act, "right")
+        ad2 = a.double().requires_grad_(True)
+        ((F.silu(ad2) if act else ad2) @ w[:-1].double().t() * dy[:, :-1].double()).sum().backward()
+        _fails(K.check_linear_f32_smallm_bwd, ad2.grad.float(), dy, w, a, act)         # the last row of W dropped
+        _fails(K.check_linear_f32_smallm_bwd, ad.grad.roll(1, 0).float(), dy, w, a, act)
+    _fails(K.check_linear_f32_smallm_bwd, (dy.double() @ w.double()).float(), dy, w, a, 1)   # SiLU' forgotten
+
+
+def test_swiglu_bwd_check_against_autograd_and_teeth():
+    rows, Fd = 7, 96
+    g, u, d = _rn(rows, Fd, seed=17, scale=2.0), _rn(rows, Fd, seed=18), _rn(rows, Fd, seed=19)
+    g[:, ::5] = torch.tensor([30.0, -30.0, 100.0, -100.0]).repeat(5)[: len(range(0, Fd, 5))].to(BF16)
+    d[0, 15], u[0, 15] = 8.0, 4.0                        # g = -100 there: |dout up silu'| = 32 * 3.7e-42 > one bf16 subnormal step
+    gd = g.double().requires_grad_(True)
+    (F.silu(gd) * u.double() * d.double()).sum().backward()
+    dgate = gd.grad.to(BF16)
+    dup = (d.double() * F.silu(g.double()).to(BF16).double()).to(BF16)
+    K.check_swiglu_bwd(dgate, dup, g, u, d, "right")
+    # fp32 has no sigmoid(-100) = 3.7e-44 (__expf(100) overflows): a kernel's 0 there is inside the bound, elsewhere it is not
+    gd2 = g.double()
+    ref15 = (d.double() * u.double() * K.silu_grad(gd2))[0, 15]
+    assert g[0, 15] == -100 and abs(float(ref15)) > 2.0 ** -133
+    flushed = torch.where(gd2 == -100, torch.zeros_like(gd2), (d.double() * u.double() * K.silu_grad(gd2))).to(BF16)
+    dup2 = (d.double() * F.silu(gd2).to(BF16).double()).to(BF16)
+    K.check_swiglu_bwd(flushed, dup2, g, u, d, "fp32 underflow")
+    _fails(K.check_swiglu_bwd, torch.where(gd2 == -30, torch.zeros_like(gd2), flushed.double()).to(BF16), dup2, g, u, d)
+    _fails(K.check_swiglu_bwd, dup, dgate, g, u, d)                                    # the two outputs swapped
+    last = dgate.clone()
+    last[-1] = 0
+    _fails(K.check_swiglu_bwd, last, dup, g, u, d)                                     # the last row dropped
+    _fails(K.check_swiglu_bwd, dgate, (d.double() * F.silu(g.double())).to(BF16).roll(1, 1), g, u, d)
+    # the interleaved layout read with gate and up columns exchanged
+    gi, ui = K.swiglu_il_index(Fd)
+    gu = torch.empty(rows, 2 * Fd, dtype=BF16)
+    gu[:, gi], gu[:, ui] = g, u
+    K.check_swiglu_bwd(dgate, dup, gu[:, gi], gu[:, ui], d, "right, through the layout")
+    _fails(K.check_swiglu_bwd, dgate, dup, gu[:, ui], gu[:, gi], d)
+
+
+def _qk_case(rope=True):
+    B, N, H = 2, 3, 5
+    x = _rn(B, N, H, 128, seed=20, scale=1.5)
+    x = (x.double() * torch.logspace(-3, 1.5, H, dtype=torch.float64)[:, None]).to(BF16)
+    w = (1.0 + _rn(128, seed=21, scale=0.2).double()).to(BF16)
+    th = torch.rand(N + 1, 64, generator=_g(22), dtype=torch.float64) * 6.2832
+    cs = torch.stack([torch.cos(th), torch.sin(th)], -1).float() if rope else None
+    return x, w, cs, float(torch.tensor(1e-6)), 261 / 2048
+
+
+def _qk_fwd(x, w, cs, eps, scale, round_inner=True):
+    """The forward another way: torch's rms_norm arithmetic by hand and the rotation as a complex product."""
+    rnd = (lambda t: t.to(BF16).double()) if round_inner else (lambda t: t)
+    xd = x.double() if not x.requires_grad else x
+    n = rnd(rnd(xd * torch.rsqrt(xd.pow(2).mean(-1, keepdim=True) + eps)) * (w if w.requires_grad else w.double()))
+    if cs is not None:
+        rot = torch.view_as_complex(cs.double().contiguous())[None, :, None, :]
+        n = torch.view_as_real(torch.view_as_complex(n.reshape(*n.shape[:-1], 64, 2).contiguous()) * rot).flatten(-2)
+    return n * scale
+
+
+@pytest.mark.parametrize("rope", [True, False])
+def test_qknorm_rope_fwd_check_has_teeth(rope):
+    x, w, cs, eps, scale = _qk_case(rope)
+    rows = None if cs is None else cs[:3]
+    right = _qk_fwd(x, w, rows, eps, scale).to(BF16)
+    assert K.check_qknorm_rope_fwd(right, x, w, rows, eps, scale, "right") <= 0.5
+    _fails(K.check_qknorm_rope_fwd, right[:, :, [0, 1, 3, 2, 4]], x, w, rows, eps, scale)          # two heads swapped
+    _fails(K.check_qknorm_rope_fwd, right.roll(1, 0), x, w, rows, eps, scale)                      # the batches exchanged
+    _fails(K.check_qknorm_rope_fwd, (right.double() / scale).to(BF16), x, w, rows, eps, scale)     # q_scale forgotten
+    _fails(K.check_qknorm_rope_fwd, _qk_fwd(x, w.roll(8), rows, eps, scale).to(BF16), x, w, rows, eps, scale)
+    if rope:
+        _fails(K.check_qknorm_rope_fwd, _qk_fwd(x, w, cs[1:4], eps, scale).to(BF16), x, w, rows, eps, scale)   # position + 1
+        _fails(K.check_qknorm_rope_fwd, _qk_fwd(x, w, None, eps, scale).to(BF16), x, w, rows, eps, scale)      # no rotation
+        conj = rows.clone()
+        conj[..., 1] *= -1
+        _fails(K.check_qknorm_rope_fwd, _qk_fwd(x, w, conj, eps, scale).to(BF16), x, w, rows, eps, scale)      # rotated backwards
+    # one element moved by the outer rounding's ulp and the two inner flips (3 ulps) stays inside the bound, a fourth ulp does
+    # not: the bound is rule 5, not more
+    lone = right.clone()
+    lone.view(torch.int16)[0, 0, 4, 7] += 3
+    assert K.check_qknorm_rope_fwd(lone, x, w, rows, eps, scale, "three ulps") > 0.9
+    lone.view(torch.int16)[0, 0, 4, 7] += 1
+    _fails(K.check_qknorm_rope_fwd, lone, x, w, rows, eps, scale)
+
+
+@pytest.mark.parametrize("rope", [True, False])
+def test_qknorm_rope_bwd_restatement_against_autograd_and_teeth(rope):
+    x, w, cs, eps, scale = _qk_case(rope)
+    rows = None if cs is None else cs[:3]
+    dout = _rn(*x.shape, seed=23)
+    xd, wd = x.double().requires_grad_(True), w.double().requires_grad_(True)
+    (_qk_fwd(xd, wd, rows, eps, scale, round_inner=False) * dout.double()).sum().backward()
+    dx, dw, _ = K.qknorm_rope_bwd(x, dout, w, rows, eps, scale)
+    assert torch.allclose(dx, xd.grad, rtol=1e-10, atol=1e-13)
+    # the kernel's dw is the gradient w.r.t. the weight as it enters the forward, q_scale included
+    assert torch.allclose(dw, wd.grad, rtol=1e-10, atol=1e-13)
+    right_dx = xd.grad.to(BF16)
+    slots = torch.zeros(3, 128, dtype=torch.float64)
+    for b in range(2):                                   # token n of batch b adds into row (n + b N) % slots
+        for n in range(3):
+            slots[(n + b * 3) % 3] += K.qknorm_rope_bwd(x[b: b + 1, n: n + 1], dout[b: b + 1, n: n + 1], w,
+                                                        None if rows is None else rows[n: n + 1], eps, scale)[1]
+    right_dw = slots.float()
+    K.check_qknorm_rope_bwd(right_dx, right_dw, x, dout, w, rows, eps, scale, "right")
+    K.check_qknorm_rope_bwd(right_dx, None, x, dout, w, rows, eps, scale, "right, no dw")
+    _fails(K.check_qknorm_rope_bwd, right_dx[:, :, [1, 0, 2, 3, 4]], right_dw, x, dout, w, rows, eps, scale)   # two heads swapped
+    _fails(K.check_qknorm_rope_bwd, right_dx, right_dw[:2], x, dout, w, rows, eps, scale)                      # a slot not summed
+    _fails(K.check_qknorm_rope_bwd, right_dx, right_dw / scale, x, dout, w, rows, eps, scale)                  # dw without q_scale
+    _fails(K.check_qknorm_rope_bwd, (xd.grad / scale).to(BF16), None, x, dout, w, rows, eps, scale)
+    nodot = (K.qknorm_rope_bwd(x, dout, w, rows, eps, scale)[2])
+    _fails(K.check_qknorm_rope_bwd, (nodot["r"] * nodot["dn"]).to(BF16), None, x, dout, w, rows, eps, scale)   # the dot term dropped
+    if rope:
+        shifted = K.qknorm_rope_bwd(x, dout, w, cs[1:4], eps, scale)
+        _fails(K.check_qknorm_rope_bwd, shifted[0].to(BF16), right_dw, x, dout, w, rows, eps, scale)           # position + 1
+        _fails(K.check_qknorm_rope_bwd, right_dx, shifted[1].float()[None], x, dout, w, rows, eps, scale)
+
+
+def test_t5_rmsnorm_and_geglu_checks_have_teeth():
+    rows, C = 5, 520
+    x, w = _rn(rows, C, seed=24, scale=3.0), (1.0 + _rn(C, seed=25, scale=0.3).double()).to(BF16)
+    eps = float(torch.tensor(1e-6))
+    xd = x.double()
+    right = (w.double() * (xd * torch.rsqrt(xd.pow(2).mean(-1, keepdim=True) + eps)).to(BF16).double()).to(BF16)
+    assert K.check_t5_rmsnorm(right, x, w, eps, "right") <= 0.5
+    last = right.clone()
+    last[-1] = right[-2]
+    _fails(K.check_t5_rmsnorm, last, x, w, eps)                                        # the last row dropped
+    _fails(K.check_t5_rmsnorm, right.roll(8, 1), x, w, eps)                            # one packet off
+    mean_removed = (w.double() * F.layer_norm(xd, (C,), eps=eps)).to(BF16)
+    _fails(K.check_t5_rmsnorm, mean_removed, x, w, eps)                                # a LayerNorm, not T5's RMS norm
+    wrongc = (w.double() * (xd * torch.rsqrt(xd.pow(2).sum(-1, keepdim=True) / 512 + eps)).to(BF16).double()).to(BF16)
+    _fails(K.check_t5_rmsnorm, wrongc, x, w, eps)                                      # mean over 512 instead of C
+    g, u = _rn(rows, C, seed=26, scale=2.0), _rn(rows, C, seed=27)
+    g[:, ::3] = torch.linspace(-30, 30, len(range(0, C, 3))).to(BF16)
+    right = (F.gelu(g.double(), approximate="tanh").to(BF16).double() * u.double()).to(BF16)
+    assert K.check_geglu_tanh(right, g, u, "right") <= 0.5
+    # what fp32 does in the tail (tanhf = -1 exactly, gelu = -0) is inside the bound
+    flushed = torch.where(g.double() < -6, torch.zeros_like(right), right)
+    K.check_geglu_tanh(flushed, g, u, "fp32 tail")
+    last = right.clone()
+    last[-1] = 0
+    _fails(K.check_geglu_tanh, last, g, u)                                             # the last row dropped
+    _fails(K.check_geglu_tanh, (F.gelu(g.double()).to(BF16).double() * u.double()).to(BF16), g, u)   # erf form
+    _fails(K.check_geglu_tanh, (F.gelu(u.double(), approximate="tanh").to(BF16).double() * g.double()).to(BF16), g, u)
+
+
+def _attention_by_hand(q, k, v, bias, mask):
+    """softmax with an additive -inf mask through torch.softmax; rows without a key are zero."""
+    B, S, H, _ = q.shape
+    i = torch.arange(S)
+    sc = torch.einsum("bihd,bjhd->bhij", q.double(), k.double()).to(BF16).double()
+    sc = (sc + bias.double()[:, i[None, :] - i[:, None] + S - 1][None]).to(BF16).double()
+    sc = sc.masked_fill(mask[:, None, None, :] == 0, float("-inf"))
+    p = torch.softmax(sc, -1).nan_to_num(0.0).to(BF16).double()
+    return torch.einsum("bhij,bjhd->bihd", p, v.double()).to(BF16)
+
+
+def test_t5_attention_check_has_teeth():
+    B, S, H = 2, 65, 3
+    g = _g(28)
+    q, k = ((torch.randint(-1, 2, (B, S, H, 64), generator=g).float() / 4).to(BF16) for _ in range(2))
+    v = torch.randn(B, S, H, 64, generator=g).to(BF16)
+    d = torch.arange(-(S - 1), S)
+    bias = (((7 * d[None, :] + 13 * torch.arange(H)[:, None]) % 129) - 64).float() / 16
+    mask = torch.ones(B, S, dtype=torch.int32)
+    mask[0, 40:] = 0
+    mask[1, ::3] = 0
+    right = _attention_by_hand(q, k, v, bias, mask)
+    assert K.check_t5_attention(right, q, k, v, bias, mask, "right") <= 0.5
+    _fails(K.check_t5_attention, _attention_by_hand(q, k, v, bias.flip(1), mask), q, k, v, bias, mask)      # bias by i - j
+    _fails(K.check_t5_attention, _attention_by_hand(q, k, v, bias.roll(1, 0), mask), q, k, v, bias, mask)   # another head's bias
+    _fails(K.check_t5_attention, _attention_by_hand(q, k, v, bias, mask[[0, 0]]), q, k, v, bias, mask)      # batch 0's mask for batch 1
+    _fails(K.check_t5_attention, right[:, :, [0, 2, 1]], q, k, v, bias, mask)                               # two heads swapped
+    nolast = mask.clone()
+    nolast[1, S - 1] = 0
+    _fails(K.check_t5_attention, _attention_by_hand(q, k, v, bias, nolast), q, k, v, bias, mask)            # the last key dropped
+    _fails(K.check_t5_attention, _attention_by_hand(q / 8, k, v, bias, mask), q, k, v, bias, mask)          # a 1/sqrt(d) scaling
+    # a fully masked batch row is exactly zero; anything else there fails
+    mask[1] = 0
+    right = _attention_by_hand(q, k, v, bias, mask)
+    assert (right[1] == 0).all()
+    K.check_t5_attention(right, q, k, v, bias, mask, "right, batch 1 masked")
+    stale = right.clone()
+    stale[1, 7, 2, 5] = 2.0 ** -100
+    _fails(K.check_t5_attention, stale, q, k, v, bias, mask)
+
+
 # ----------------------------------------------------------------------------------------------------- coverage guard
 # entry point -> [(test file, test function)] that checks its kernel at kernel level
 KERNEL_TESTS = {
@@ -120,21 +412,28 @@ KERNEL_TESTS = {
     "lcv_gate_residual_fwd": [(EDGES, "test_norm_and_gate_residual_fwd_edges"),
                               (EDGES, "test_gate_residual_fwd_without_gate_past_the_block_cap")],
     "lcv_gate_residual_bwd": [(EDGES, "test_gate_residual_bwd_edges")],
-    "lcv_qknorm_rope_fwd": [("test_gpu_kernels.py", "test_qknorm_rope")],
+    "lcv_qknorm_rope_fwd": [("test_gpu_kernels.py", "test_qknorm_rope"), (BWD_EDGES, "test_qknorm_rope_fwd_edges"),
+                            (BWD_EDGES, "test_qknorm_rope_fwd_leaves_v_alone_when_v_out_is_v_in")],
     "lcv_qknorm_rope_bwd": [("test_gpu_backward.py", "test_qknorm_rope_backward"),
-                            ("test_gpu_backward.py", "test_qk_norm_weight_gradients")],
+                            ("test_gpu_backward.py", "test_qk_norm_weight_gradients"), (BWD_EDGES, "test_qknorm_rope_bwd_edges")],
     "lcv_timestep_embedding": [("test_gpu_kernels.py", "test_timestep_embedding_matches_oracle")],
     "lcv_attn_fwd": [("test_gpu_kernels.py", "test_attention_fuzz_against_the_restatement_of_the_kernels_arithmetic")],
     "lcv_attn_bwd": [("test_gpu_backward.py", "test_attention_backward_fuzz_against_the_kernels_rounding_points")],
     "lcv_gemm_nt": [("test_gpu_kernels.py", "test_gemm_dispatch_fuzz_bitwise_against_the_one_barrier_kernel"),
                     ("test_gpu_kernels.py", "test_gemm_nt_lora_and_epilogues")],
-    "lcv_lora_down": [("test_gpu_kernels.py", "test_gemm_nt_lora_and_epilogues")],
-    "lcv_tn_skinny": [("test_gpu_backward.py", "test_linear_f32_backward_and_tn_skinny_and_unpatchify")],
+    "lcv_lora_down": [("test_gpu_kernels.py", "test_gemm_nt_lora_and_epilogues"), (LORA_EDGES, "test_lora_down_edges"),
+                      (LORA_EDGES, "test_lora_down_rejects_rank_33")],
+    "lcv_tn_skinny": [("test_gpu_backward.py", "test_linear_f32_backward_and_tn_skinny_and_unpatchify"),
+                      (LORA_EDGES, "test_tn_skinny_workspace_path_edges"), (LORA_EDGES, "test_tn_skinny_atomic_path_edges"),
+                      (LORA_EDGES, "test_tn_skinny_rejects_a_small_or_misaligned_workspace")],
     "lcv_linear_f32_smallm": [("test_gpu_kernels.py", "test_linear_f32_smallm")],
-    "lcv_linear_f32_smallm_bwd": [("test_gpu_backward.py", "test_linear_f32_backward_and_tn_skinny_and_unpatchify")],
+    "lcv_linear_f32_smallm_bwd": [("test_gpu_backward.py", "test_linear_f32_backward_and_tn_skinny_and_unpatchify"),
+                                  (BWD_EDGES, "test_linear_f32_smallm_bwd_edges")],
     "lcv_swiglu_fwd": [(EDGES, "test_swiglu_fwd_on_views_into_one_buffer_past_the_block_cap")],
-    "lcv_swiglu_bwd": [("test_gpu_backward.py", "test_norm_gate_swiglu_backward")],
-    "lcv_swiglu_bwd_interleaved": [("test_gpu_backward.py", "test_fused_swiglu_training_path_matches_the_unfused_form")],
+    "lcv_swiglu_bwd": [("test_gpu_backward.py", "test_norm_gate_swiglu_backward"),
+                       (BWD_EDGES, "test_swiglu_bwd_on_views_into_one_buffer_past_the_block_cap_and_in_saturation")],
+    "lcv_swiglu_bwd_interleaved": [("test_gpu_backward.py", "test_fused_swiglu_training_path_matches_the_unfused_form"),
+                                   (BWD_EDGES, "test_swiglu_bwd_interleaved_edges_and_equals_swiglu_bwd_bitwise")],
     "lcv_patchify": [(EDGES, "test_patchify_pad_and_unpatchify_past_the_block_cap")],
     "lcv_unpatchify": [(EDGES, "test_patchify_pad_and_unpatchify_past_the_block_cap")],
     "lcv_unpatchify_bwd": [(EDGES, "test_patchify_pad_and_unpatchify_past_the_block_cap")],
@@ -162,10 +461,14 @@ KERNEL_TESTS = {
     "lcv_frame_sqerr": [("test_gpu_eval.py", "test_sqerr_and_gaussian_ssim_match_oracle")],
     "lcv_frame_ssim": [("test_gpu_eval.py", "test_sqerr_and_gaussian_ssim_match_oracle"),
                        ("test_gpu_eval.py", "test_uniform7_ssim_matches_oracle")],
-    "lcv_gather_rows": [("test_gpu_umt5.py", "test_gather_norm_geglu_kernels")],
-    "lcv_t5_rmsnorm": [("test_gpu_umt5.py", "test_gather_norm_geglu_kernels")],
-    "lcv_geglu_tanh_fwd": [("test_gpu_umt5.py", "test_gather_norm_geglu_kernels")],
-    "lcv_t5_attention": [("test_gpu_umt5.py", "test_attention_kernel_matches_oracle")],
+    "lcv_gather_rows": [("test_gpu_umt5.py", "test_gather_norm_geglu_kernels"),
+                        (UMT5_EDGES, "test_gather_rows_past_the_block_cap_with_clamped_ids")],
+    "lcv_t5_rmsnorm": [("test_gpu_umt5.py", "test_gather_norm_geglu_kernels"), (UMT5_EDGES, "test_t5_rmsnorm_edges"),
+                       (UMT5_EDGES, "test_t5_rmsnorm_rejects_c_4104")],
+    "lcv_geglu_tanh_fwd": [("test_gpu_umt5.py", "test_gather_norm_geglu_kernels"),
+                           (UMT5_EDGES, "test_geglu_tanh_fwd_on_views_into_one_buffer_past_the_block_cap_and_in_saturation")],
+    "lcv_t5_attention": [("test_gpu_umt5.py", "test_attention_kernel_matches_oracle"), (UMT5_EDGES, "test_t5_attention_edges"),
+                         (UMT5_EDGES, "test_t5_attention_rejects_s_513")],
 }
 
 # host-only entry points: no kernel behind them
