@@ -30,7 +30,8 @@ _ATTN_FLAGS = ["-fno-honor-nans", "-mno-amdgpu-ieee", "-fno-slp-vectorize"]
 EXTRA = {"attn_fwd.hip": _ATTN_FLAGS, "attn_fwd_pipe.hip": _ATTN_FLAGS, "attn_bwd_dq2.hip": _ATTN_FLAGS, "attn_bwd_dkv2.hip": _ATTN_FLAGS,
          "attn_fwd_w64.hip": _ATTN_FLAGS,
          # bit-exact against an fp32 restatement: no product may fuse with the sum that takes it (the source says so too)
-         "optim_master.hip": ["-ffp-contract=off"], "optim_moments8.hip": ["-ffp-contract=off"]}
+         "optim_master.hip": ["-ffp-contract=off"], "optim_moments8.hip": ["-ffp-contract=off"],
+         "optim_accum.hip": ["-ffp-contract=off"]}
 
 
 def _compile(src: Path, hdr_mtime: float) -> Path:

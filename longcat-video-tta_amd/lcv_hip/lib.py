@@ -111,6 +111,15 @@ _SIGNATURES_MOMENTS8 = {
     "lcv_moments8_decode": [P, P, P, P, P, I64, P],
 }
 
+# include/lcv_hip_accum.h (a header of its own: fp32 gradient accumulation over micro-steps); `acc` is a device array of pointers
+# to the fp32 accumulators, parallel to the descriptor table; the g32 steps take their lcv_master_* counterparts' arguments with
+# `grad` of the table pointing to fp32; every function returns int
+_SIGNATURES_ACCUM = {
+    "lcv_grad_accumulate": [P, P, I64, I64, F64, P],
+    "lcv_master_sgd_step_g32": [P, P, I64, I64, P, F64, F64, P],
+    "lcv_master_adamw_step_g32": [P, P, I64, I64, P, F64, F64, F64, F64, F64, I64, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -167,7 +176,8 @@ def load():
     lib.lcv_tn_skinny_dropout_ws_bytes.restype = c_int64   # likewise
     lib.lcv_tn_skinny_dropout_ws_bytes.argtypes = [I64, I64, I64]
     for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
-                       + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())):
+                       + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())
+                       + list(_SIGNATURES_ACCUM.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

@@ -607,14 +607,21 @@ class FusedAdamWClip:
 
     `moments_8bit=True` (with `master_weights=True` only) keeps each moment in one byte per element plus one fp32 scale per
     moment per 512 elements (include/lcv_hip_moments8.h): about 2.016 B / parameter of moments instead of 8.  The parameter
-    update still uses the fp32 moments of the step; only what is kept between steps is quantised."""
+    update still uses the fp32 moments of the step; only what is kept between steps is quantised.
+
+    `grad_accum=N` with N > 1 (with `master_weights=True` and fp32 moments only) makes one step the mean of N micro-steps
+    (include/lcv_hip_accum.h): every parameter element gets a zeroed fp32 accumulator (+4 B / parameter); after each backward
+    `accumulate()` adds `.grad * (1/N)` into it in fp32 and drops the `.grad`s; `clip_grad_norm_` and `step()` then read the
+    accumulators as the (fp32) gradients, over every parameter that received a gradient in at least one micro-step, and refuse
+    to run before N micro-steps are in.  `zero_grad()` zeroes the accumulators and starts the next step."""
     CHUNK = 2048
     NORM_SLOTS = 64   # partial sums of squares per tensor (csrc/optim.hip)
     MOMENTS8_BLOCK = 512   # elements per scale (LCV_MOMENTS8_BLOCK)
     moments_8bit = False
+    grad_accum = 1
 
     def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-8, master_weights=False,
-                 moments_8bit=False):
+                 moments_8bit=False, *, grad_accum: int = 1):
         self.params = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
@@ -641,6 +648,7 @@ class FusedAdamWClip:
         else:
             self.exp_avg = [torch.zeros_like(p) for p in self.params]
             self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
+        self._init_accum(grad_accum)
         self.step_count = 0
         dev = self.params[0].device
         self._ws = torch.zeros(len(self.params) * self.NORM_SLOTS, dtype=F32, device=dev)
@@ -665,6 +673,74 @@ class FusedAdamWClip:
         if any(not p.is_contiguous() for p in self.params):
             raise _lib.LcvError(f"{name}: master_weights=True needs contiguous parameters")
         self._low = [torch.zeros(p.shape, dtype=torch.int16, device=p.device) for p in self.params]
+
+    def _init_accum(self, grad_accum: int) -> None:
+        """Zeroed fp32 accumulators (+4 B / parameter) when `grad_accum` > 1; nothing at 1."""
+        self.grad_accum = int(grad_accum)
+        self._acc = []
+        self._acc_live = set()       # indices of the parameters that received a gradient in a micro-step of this step
+        self._micro = 0
+        self._micro_desc = None
+        self._micro_key = None
+        if self.grad_accum < 1:
+            raise ValueError(f"grad_accum must be at least 1, got {grad_accum}")
+        if self.grad_accum == 1:
+            return
+        name = type(self).__name__
+        if not self.master_weights:
+            raise _lib.LcvError(f"{name}: grad_accum > 1 needs master_weights=True (the fp32-gradient steps exist for the "
+                                "master-weight form only)")
+        if self.moments_8bit:
+            raise _lib.LcvError(f"{name}: grad_accum > 1 needs moments_8bit=False (the 8-bit-moment step reads bf16 gradients)")
+        self._acc = [torch.zeros(p.shape, dtype=F32, device=p.device) for p in self.params]
+
+    def accumulated_grads(self):
+        """The fp32 accumulators, one per parameter in `params` order (empty at grad_accum=1)."""
+        return list(self._acc)
+
+    def accumulate(self) -> None:
+        """One micro-step: acc += float(.grad) * (1 / grad_accum) over the parameters that hold a `.grad`
+        (lcv_grad_accumulate), then those `.grad`s are dropped."""
+        name = type(self).__name__
+        if self.grad_accum == 1:
+            raise _lib.LcvError(f"{name}: accumulate() needs grad_accum > 1")
+        if self._micro >= self.grad_accum:
+            raise _lib.LcvError(f"{name}: {self._micro} of {self.grad_accum} micro-steps are already accumulated; step() and "
+                                "zero_grad() come next")
+        sel, grads = [], []
+        for i, p in enumerate(self.params):
+            if p.grad is None:
+                continue
+            sel.append(i)
+            grads.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())
+        if not sel:
+            raise _lib.LcvError(f"{name}: no parameter has a gradient")
+        key = tuple(g.data_ptr() for g in grads) + tuple(sel)
+        if self._micro_desc is None or key != self._micro_key:
+            dev = self.params[0].device
+            rows, chunk = [], 0
+            for i, g in zip(sel, grads):
+                p = self.params[i]
+                rows.append([p.data_ptr(), g.data_ptr(), 0, 0, p.numel(), chunk])
+                chunk += (p.numel() + self.CHUNK - 1) // self.CHUNK
+            self._micro_desc = (torch.tensor(rows, dtype=torch.int64).to(dev),
+                                torch.tensor([self._acc[i].data_ptr() for i in sel], dtype=torch.int64).to(dev), len(sel), chunk)
+            self._micro_key = key
+        d, acc, n, chunks = self._micro_desc
+        call("lcv_grad_accumulate", _ptr(d), _ptr(acc), n, chunks, 1.0 / self.grad_accum, _stream())
+        for i in sel:
+            self.params[i].grad = None
+        self._acc_live.update(sel)
+        self._micro += 1
+
+    def _accumulated(self):
+        """The active set and its gradients under grad_accum > 1: the accumulators of every parameter that received a gradient
+        in at least one micro-step.  Refuses before all micro-steps are in."""
+        if self._micro != self.grad_accum:
+            raise _lib.LcvError(f"{type(self).__name__}: {self._micro} of {self.grad_accum} micro-steps accumulated; call "
+                                "accumulate() after every backward before clipping or stepping")
+        sel = sorted(self._acc_live)
+        return sel, [self._acc[i] for i in sel]
 
     @property
     def low_words(self):
@@ -713,16 +789,23 @@ class FusedAdamWClip:
         for p in self.params:
             p.grad = None if set_to_none else (p.grad.zero_() if p.grad is not None else None)
         self._have_coef = False
+        if self._acc:                # grad_accum > 1: the next optimizer step starts from zeroed accumulators
+            torch._foreach_zero_(self._acc)
+            self._acc_live.clear()
+            self._micro = 0
 
     def _descriptors(self):
         """Device descriptor table over the parameters that received a gradient (torch's AdamW and
-        clip_grad_norm_ skip `grad is None` the same way)."""
-        sel, grads = [], []
-        for i, p in enumerate(self.params):
-            if p.grad is None:
-                continue
-            sel.append(i)
-            grads.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())
+        clip_grad_norm_ skip `grad is None` the same way).  Under grad_accum > 1 the gradients are the fp32 accumulators."""
+        if self.grad_accum > 1:
+            sel, grads = self._accumulated()
+        else:
+            sel, grads = [], []
+            for i, p in enumerate(self.params):
+                if p.grad is None:
+                    continue
+                sel.append(i)
+                grads.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())
         if not sel:
             raise _lib.LcvError("FusedAdamWClip: no parameter has a gradient")
         key = tuple(g.data_ptr() for g in grads) + tuple(sel)
@@ -747,15 +830,21 @@ class FusedAdamWClip:
         self._grads = grads  # keep alive until the launch
         return self._desc
 
+    @property
+    def _grad_f32(self) -> bool:
+        """Whether the clip reads fp32 gradients: fp32 parameters, or the accumulators of grad_accum > 1 (an fp32 gradient's
+        norm is an fp32 number)."""
+        return self.f32 or self.grad_accum > 1
+
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
         d = self._descriptors()
         if _DETERMINISTIC:
             if getattr(self, "_det_ws", None) is None:      # the mode was switched on after the table was built
                 self._det_ws = torch.empty((self._total_chunks,), dtype=F32, device=self.params[0].device)
-            call("lcv_det_grad_norm_clip", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
+            call("lcv_det_grad_norm_clip", _ptr(d), self._n_active, self._total_chunks, 1 if self._grad_f32 else 0,
                  float(max_norm), _ptr(self._ws), _ptr(self._norm_coef), _ptr(self._det_ws), self._total_chunks * 4, _stream())
         else:
-            call("lcv_grad_norm_clip", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
+            call("lcv_grad_norm_clip", _ptr(d), self._n_active, self._total_chunks, 1 if self._grad_f32 else 0,
                  float(max_norm), _ptr(self._ws), _ptr(self._norm_coef), _stream())
         self._have_coef = True
         return self._norm_coef[0]
@@ -766,6 +855,8 @@ class FusedAdamWClip:
         `clip_grad_norm_(all_params, max_norm)`): per-tensor norms in each tensor's own dtype, the total over their fp32
         stack, coefficient min(max_norm / (total + 1e-6), 1) — torch's rule for mixed dtypes.  Reads the per-tensor
         squares back (one sync per step); used only by the norm + delta tuning option."""
+        if any(o.grad_accum > 1 for o in opts):
+            raise _lib.LcvError("joint_clip_grad_norm_: an optimizer with grad_accum > 1 cannot take part in a joint clip")
         total_sq = 0.0
         live = [o for o in opts if any(p.grad is not None for p in o.params)]
         for o in live:
@@ -788,6 +879,10 @@ class FusedAdamWClip:
         if self.moments_8bit:
             call("lcv_master_adamw8_step", _ptr(d), _ptr(self._low_desc), _ptr(self._scale_desc), self._n_active,
                  self._total_chunks, _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
+                 float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
+        elif self.grad_accum > 1:
+            call("lcv_master_adamw_step_g32", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
+                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
                  float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
         elif self.master_weights:
             call("lcv_master_adamw_step", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
@@ -1112,9 +1207,10 @@ def gelu_tanh_bwd(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
 class FusedSGDClip(FusedAdamWClip):
     """clip_grad_norm_ + SGD(momentum=0, weight_decay).step over a parameter list in two launches — the default
     optimizer of full-model TTA (lora_experiment/scripts/run_full_tta.py:138-144, 179-180).  No optimizer state, unless
-    `master_weights=True` adds the int16 low words of FusedAdamWClip's master-weight form (+2 B / parameter)."""
+    `master_weights=True` adds the int16 low words of FusedAdamWClip's master-weight form (+2 B / parameter), and with it
+    `grad_accum=N` the fp32 accumulators of FusedAdamWClip's accumulation form (+4 B / parameter)."""
 
-    def __init__(self, params, lr=1e-5, weight_decay=0.01, master_weights=False):
+    def __init__(self, params, lr=1e-5, weight_decay=0.01, master_weights=False, *, grad_accum: int = 1):
         self.params = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
@@ -1127,6 +1223,7 @@ class FusedSGDClip(FusedAdamWClip):
         self.exp_avg = self.params            # the descriptor table has moment slots; SGD never reads them
         self.exp_avg_sq = self.params
         self._scales = []
+        self._init_accum(grad_accum)
         self.step_count = 0
         dev = self.params[0].device
         self._ws = torch.zeros(len(self.params) * self.NORM_SLOTS, dtype=F32, device=dev)
@@ -1145,7 +1242,10 @@ class FusedSGDClip(FusedAdamWClip):
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
-        if self.master_weights:
+        if self.grad_accum > 1:
+            call("lcv_master_sgd_step_g32", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
+                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
+        elif self.master_weights:
             call("lcv_master_sgd_step", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
                  _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
         else:

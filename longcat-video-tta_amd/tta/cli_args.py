@@ -95,6 +95,26 @@ def parse_with_adam_8bit(parser, argv=None):
     return args
 
 
+def add_grad_accum_arg(parser):
+    parser.add_argument("--grad-accum", type=int, default=1, metavar="N",
+                        help="with --master-weights: every optimizer step is the mean of N micro-steps (own sigma, noise and "
+                             "variant draw each), summed in fp32 accumulators, +4 B / parameter (include/lcv_hip_accum.h)")
+
+
+def parse_with_grad_accum(parser, argv=None):
+    """parse_with_adam_8bit, then the refusals of --grad-accum as the parser's own one-line errors (exit status 2)."""
+    args = parse_with_adam_8bit(parser, argv)
+    if args.grad_accum < 1:
+        parser.error(f"--grad-accum must be at least 1, got {args.grad_accum}")
+    if args.grad_accum > 1 and not args.master_weights:
+        parser.error("--grad-accum above 1 needs --master-weights (the fp32-gradient steps exist for the master-weight form only)")
+    if args.grad_accum > 1 and args.adam_8bit:
+        parser.error("--grad-accum above 1 cannot be combined with --adam-8bit (the 8-bit-moment step reads bf16 gradients)")
+    if args.grad_accum > 1 and getattr(args, "also_tune_delta", False):
+        parser.error("--grad-accum above 1 cannot be combined with --also-tune-delta (the fp32 delta vector has no accumulators)")
+    return args
+
+
 def normalize_tta_frame_args(args):
     """Post-parse normalisation of lora_experiment/scripts/run_lora_tta.py:743-758 (GT-leak clamp included)."""
     if args.tta_total_frames is None:

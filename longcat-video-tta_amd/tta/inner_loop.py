@@ -78,8 +78,15 @@ def _variant_pool(train_latents, variants) -> List[torch.Tensor]:
 def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers: Sequence, loss_at: Callable[[int], torch.Tensor],
                    clip_and_step: Callable[[], None], num_steps: int, lr: float = 0.0, warmup_steps: int = 0,
                    early_stopper: Optional[AnchoredEarlyStopper] = None, grad_sync: Optional[Callable[[], None]] = None,
-                   finish_eval: bool = True) -> Dict:
-    """`loss_at(step)` returns the differentiable loss of that step; `clip_and_step()` owns clipping + the update."""
+                   finish_eval: bool = True, grad_accum: int = 1) -> Dict:
+    """`loss_at(step)` returns the differentiable loss of that step; `clip_and_step()` owns clipping + the update.
+
+    `grad_accum=N` with N > 1 puts N micro-steps behind every optimizer step: `loss_at(step * N + k)`, backward, `grad_sync()`
+    and `opt.accumulate()` (fp32 accumulators, include/lcv_hip_accum.h) for k = 0 .. N-1, then `clip_and_step()`.  The step's
+    logged loss is the micro losses added in order in fp32, times fp32(1/N), on the device.  `num_steps`, the warm-up and the
+    early stopper's `check_every` count optimizer steps."""
+    if grad_accum < 1:
+        raise ValueError(f"grad_accum must be at least 1, got {grad_accum}")
     device = params[0].device
     log = _LossLog(num_steps, device)
     keeper = None
@@ -97,10 +104,13 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
             for opt in optimizers:
                 for group in opt.param_groups:
                     group["lr"] = lr * (step + 1) / warmup_steps
-        loss = loss_at(step)
-        loss.backward()
-        if grad_sync is not None:
-            grad_sync()
+        if grad_accum > 1:
+            loss = _accumulate_micro_steps(optimizers, loss_at, grad_sync, step, grad_accum)
+        else:
+            loss = loss_at(step)
+            loss.backward()
+            if grad_sync is not None:
+                grad_sync()
         clip_and_step()
         log.push(loss)
         del loss
@@ -131,6 +141,22 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
         module.eval()
     return {"losses": log.to_list(), "train_time": elapsed, "es_check_time": es_seconds,
             "early_stopping_info": early_stopper.state if early_stopper is not None else None}
+
+
+def _accumulate_micro_steps(optimizers, loss_at, grad_sync, step: int, n: int) -> torch.Tensor:
+    """The micro-steps of optimizer step `step`; returns the step's loss for the log (fp32, on the device)."""
+    total = None
+    for k in range(n):
+        loss = loss_at(step * n + k)
+        loss.backward()
+        if grad_sync is not None:        # per micro-step: sequence-parallel replicas hold identical gradients before they add
+            grad_sync()
+        for opt in optimizers:
+            opt.accumulate()
+        micro = loss.detach().reshape(()).to(torch.float32)
+        total = micro if total is None else total + micro
+        del loss
+    return total * torch.tensor(1.0 / n, dtype=torch.float32)
 
 
 def _put_back(params: Sequence[torch.Tensor]) -> Callable:
@@ -209,24 +235,25 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
                                   device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                                   early_stopper: Optional[AnchoredEarlyStopper] = None, lora_param_fn=None,
                                   train_latents_variants: Optional[List[Dict]] = None,
-                                  *, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
+                                  *, grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     params = _adapter_params(lora_modules, lora_param_fn)
     # made per call, so per video: the low words of `master_weights` start at zero next to freshly reset adapters
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
-                         master_weights=master_weights, moments_8bit=moments_8bit)
+                         master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum)
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
     return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
-                          num_steps, lr, warmup_steps, early_stopper, grad_sync=_sp_sync(dit, opt))
+                          num_steps, lr, warmup_steps, early_stopper, grad_sync=_sp_sync(dit, opt), grad_accum=grad_accum)
 
 
 def finetune_lora_batch(dit: nn.Module, lora_modules, batch_data: List[Dict], num_steps: int = 20, lr: float = 2e-4,
                         warmup_steps: int = 3, weight_decay: float = 0.01, max_grad_norm: float = 1.0,
                         device: str = "cuda", dtype: torch.dtype = torch.bfloat16, lora_param_fn=None,
-                        *, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
-    """Shared adapters trained round-robin over the eval video and its neighbours; no early stopping (:558-634)."""
+                        *, grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
+    """Shared adapters trained round-robin over the eval video and its neighbours; no early stopping (:558-634).  The feed
+    receives the micro-step index, so `grad_accum` = number of videos puts every video behind each update."""
     params = _adapter_params(lora_modules, lora_param_fn)
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
-                         master_weights=master_weights, moments_8bit=moments_8bit)
+                         master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum)
     feed = _RoundRobin(batch_data, device)
     return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
-                          num_steps, lr, warmup_steps, None, grad_sync=_sp_sync(dit, opt))
+                          num_steps, lr, warmup_steps, None, grad_sync=_sp_sync(dit, opt), grad_accum=grad_accum)
