@@ -1,5 +1,6 @@
-// What the master-weight optimizer kernels share (optim_master.hip, optim_moments8.hip): the (bf16 word, int16 low word) <->
-// fp32 master format, AdamW's scalars and its per-element op sequence.  Both files are built with -ffp-contract=off.
+// What the master-weight optimizer kernels share (optim_master.hip, optim_moments8.hip, optim_accum.hip, optim_anchor.hip):
+// the (bf16 word, int16 low word) <-> fp32 master format, AdamW's scalars and its per-element op sequences.  All of them are
+// built with -ffp-contract=off.
 #pragma once
 #include "optim_common.h"
 #include <math.h>
@@ -43,10 +44,8 @@ static inline MasterAdamScalars master_adam_scalars(double lr, double beta1, dou
   return sc;
 }
 
-// the fp32 op sequence of adamw_kernel<true> (optim.hip), each operation correctly rounded; p, m, v in and out
-__device__ __forceinline__ void master_adamw_elem(float& p, float& m, float& v, float g, float coef, const MasterAdamScalars& s) {
-  g = g * coef;
-  p = p * s.c_wd;
+// AdamW after the decay: both moments, then the parameter.  g is already scaled by the clip coefficient.
+__device__ __forceinline__ void master_adamw_moments_update(float& p, float& m, float& v, float g, const MasterAdamScalars& s) {
   const float dm = s.w1 * (g - m);
   m = m + dm;
   v = v * s.b2;
@@ -55,4 +54,35 @@ __device__ __forceinline__ void master_adamw_elem(float& p, float& m, float& v, 
   const float d = __builtin_sqrtf(v) / s.bc2_sqrt + s.eps;
   const float dp = s.step_size * (m / d);
   p = p + dp;
+}
+
+// the fp32 op sequence of adamw_kernel<true> (optim.hip), each operation correctly rounded; p, m, v in and out
+__device__ __forceinline__ void master_adamw_elem(float& p, float& m, float& v, float g, float coef, const MasterAdamScalars& s) {
+  g = g * coef;
+  p = p * s.c_wd;
+  master_adamw_moments_update(p, m, v, g, s);
+}
+
+// ---- decay toward a base weight w0 instead of toward zero (include/lcv_hip_anchor.h) ----
+// master_sgd_elem (optim_master.hip) with wd * (w - w0) in place of wd * w
+__device__ __forceinline__ float master_sgd_anchor_elem(float w, float w0, float g, float coef, float lr, float wd) {
+  g = g * coef;
+  if (wd != 0.f) {
+    const float d = w - w0;
+    const float t = wd * d;
+    g = g + t;
+  }
+  const float u = -lr * g;
+  return w + u;
+}
+
+// master_adamw_elem with p = p - a * (p - w0) in place of p = p * c_wd; a = (float)(lr * weight_decay).  Always taken: a = 0
+// subtracts a zero.
+__device__ __forceinline__ void master_adamw_anchor_elem(float& p, float& m, float& v, float w0, float g, float coef, float a,
+                                                         const MasterAdamScalars& s) {
+  g = g * coef;
+  const float d = p - w0;
+  const float t = a * d;
+  p = p - t;
+  master_adamw_moments_update(p, m, v, g, s);
 }

@@ -29,12 +29,13 @@ def build_parser():
                    help="fp32 master weights for the bf16 norm weights (include/lcv_hip_master.h)")
     C.add_adam_8bit_arg(p)
     C.add_grad_accum_arg(p)
+    C.add_decay_to_base_arg(p)
     R.add_shared_groups(p, clip_gate=False)
     return p
 
 
 def parse_args(argv=None):
-    return C.parse_with_grad_accum(build_parser(), argv)
+    return C.parse_with_decay_to_base(build_parser(), argv)
 
 
 def main(argv=None):
@@ -45,14 +46,15 @@ def main(argv=None):
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_norm_params(
             w, w.tuned_params, cond, train, pe, pm, num_steps=args.norm_steps, lr=args.norm_lr, device=device, dtype=torch.bfloat16,
             early_stopper=es, train_latents_variants=tv, master_weights=args.master_weights,
-            moments_8bit=args.adam_8bit, grad_accum=args.grad_accum),
+            moments_8bit=args.adam_8bit, grad_accum=args.grad_accum, decay_to_base=args.decay_to_base),
         params_of=lambda w: w.tuned_params,
-        result_extra=lambda opt: {k: opt[k] for k in ("norm_param_drift", "delta_norm") if k in opt},
+        result_extra=lambda opt: {k: opt[k] for k in ("norm_param_drift", "delta_norm", "drift_norm") if k in opt},
         # this runner writes no config.json (as the reference's does not): the flag is recorded here, when it is set
         summary_head={"norm_target": args.norm_target, "norm_steps": args.norm_steps, "norm_lr": args.norm_lr,
                       **({"master_weights": True} if args.master_weights else {}),
                       **({"adam_8bit": True} if args.adam_8bit else {}),
-                      **({"grad_accum": args.grad_accum} if args.grad_accum > 1 else {})},
+                      **({"grad_accum": args.grad_accum} if args.grad_accum > 1 else {}),
+                      **({"decay_to_base": True} if args.decay_to_base else {})},
         file_suffix="norm_tune", cleanup=lambda w: w.restore())
 
 

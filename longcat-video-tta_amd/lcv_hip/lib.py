@@ -120,6 +120,16 @@ _SIGNATURES_ACCUM = {
     "lcv_master_adamw_step_g32": [P, P, I64, I64, P, F64, F64, F64, F64, F64, I64, P],
 }
 
+# include/lcv_hip_anchor.h (a header of its own: decay toward the base weights and the drift norm); `anchor` is a device array of
+# pointers to the bf16 base words, parallel to the descriptor table; the steps take their counterparts' arguments with `anchor`
+# after `low` (after `scales` in the 8-bit form) and `grad_f32` in front of the stream; every function returns int
+_SIGNATURES_ANCHOR = {
+    "lcv_master_sgd_step_anchor": [P, P, P, I64, I64, P, F64, F64, I, P],
+    "lcv_master_adamw_step_anchor": [P, P, P, I64, I64, P, F64, F64, F64, F64, F64, I64, I, P],
+    "lcv_master_adamw8_step_anchor": [P, P, P, P, I64, I64, P, F64, F64, F64, F64, F64, I64, P],
+    "lcv_master_drift_sumsq": [P, P, P, I64, I64, P, I64, P, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -177,7 +187,7 @@ def load():
     lib.lcv_tn_skinny_dropout_ws_bytes.argtypes = [I64, I64, I64]
     for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
                        + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())
-                       + list(_SIGNATURES_ACCUM.items())):
+                       + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

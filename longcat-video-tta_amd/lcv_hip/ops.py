@@ -613,15 +613,21 @@ class FusedAdamWClip:
     (include/lcv_hip_accum.h): every parameter element gets a zeroed fp32 accumulator (+4 B / parameter); after each backward
     `accumulate()` adds `.grad * (1/N)` into it in fp32 and drops the `.grad`s; `clip_grad_norm_` and `step()` then read the
     accumulators as the (fp32) gradients, over every parameter that received a gradient in at least one micro-step, and refuse
-    to run before N micro-steps are in.  `zero_grad()` zeroes the accumulators and starts the next step."""
+    to run before N micro-steps are in.  `zero_grad()` zeroes the accumulators and starts the next step.
+
+    `anchor=[...]` (with `master_weights=True` only; contiguous bf16 GPU tensors shaped like `params`, held by reference, not
+    copied) turns the weight decay into a pull toward those base words instead of toward zero (include/lcv_hip_anchor.h): the
+    step reads 2 B / parameter more and allocates nothing.  `drift_norm()` is the distance from them."""
     CHUNK = 2048
     NORM_SLOTS = 64   # partial sums of squares per tensor (csrc/optim.hip)
     MOMENTS8_BLOCK = 512   # elements per scale (LCV_MOMENTS8_BLOCK)
     moments_8bit = False
     grad_accum = 1
+    _anchor = ()
+    _drift = None
 
     def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-8, master_weights=False,
-                 moments_8bit=False, *, grad_accum: int = 1):
+                 moments_8bit=False, *, grad_accum: int = 1, anchor=None):
         self.params = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
@@ -631,6 +637,7 @@ class FusedAdamWClip:
         self.f32 = dt == F32
         self.param_groups = [dict(params=self.params, lr=lr, betas=betas, weight_decay=weight_decay, eps=eps)]
         self._init_master(master_weights)
+        self._init_anchor(anchor)
         self.moments_8bit = bool(moments_8bit)
         self._scales = []
         self._scale_desc = None
@@ -673,6 +680,68 @@ class FusedAdamWClip:
         if any(not p.is_contiguous() for p in self.params):
             raise _lib.LcvError(f"{name}: master_weights=True needs contiguous parameters")
         self._low = [torch.zeros(p.shape, dtype=torch.int16, device=p.device) for p in self.params]
+
+    def _check_anchor(self, anchor):
+        """A list of base words that fits `params`: contiguous bf16 GPU tensors of the parameters' shapes."""
+        name = type(self).__name__
+        anchor = [a for a in anchor]
+        if len(anchor) != len(self.params):
+            raise _lib.LcvError(f"{name}: anchor has {len(anchor)} tensors for {len(self.params)} parameters")
+        for a, p in zip(anchor, self.params):
+            if a.dtype != BF16 or not a.is_cuda or not a.is_contiguous() or a.shape != p.shape or a.device != p.device:
+                raise _lib.LcvError(f"{name}: every anchor must be a contiguous bf16 tensor on the parameter's GPU with its "
+                                    f"shape; got {a.dtype} {tuple(a.shape)} on {a.device} for {tuple(p.shape)}")
+        return anchor
+
+    def _init_anchor(self, anchor) -> None:
+        """The base words the decay pulls toward, held by reference; nothing without them."""
+        self._anchor = []
+        self._anchor_desc = None
+        self._drift = None
+        if anchor is None:
+            return
+        if not self.master_weights:
+            raise _lib.LcvError(f"{type(self).__name__}: anchor needs master_weights=True (a pull of lr * wd * (w - w0) is far "
+                                "below half a bf16 ulp; the anchor steps exist for the master-weight form only)")
+        self._anchor = self._check_anchor(anchor)
+
+    def drift_norm(self, anchor=None) -> torch.Tensor:
+        """|theta - theta0| over ALL parameters (with or without a gradient) as a 0-dim fp32 device tensor, no host sync
+        (lcv_master_drift_sumsq, fixed order): theta is join(bf16 word, low word) under master weights and the bf16 word
+        without them; theta0 the optimizer's anchor, or the list passed in."""
+        name = type(self).__name__
+        if self.f32:
+            raise _lib.LcvError(f"{name}: drift_norm() is for bf16 parameters")
+        if anchor is not None:
+            anchor = self._check_anchor(anchor)
+        elif self._anchor:
+            anchor = self._anchor
+        else:
+            raise _lib.LcvError(f"{name}: drift_norm() needs an anchor (the optimizer holds none)")
+        if any(not p.is_cuda or not p.is_contiguous() for p in self.params):
+            raise _lib.LcvError(f"{name}: drift_norm() needs contiguous parameters on the GPU")
+        dev = self.params[0].device
+        key = tuple(a.data_ptr() for a in anchor) + tuple(p.data_ptr() for p in self.params)
+        if self._drift is None or self._drift[0] != key:
+            rows, ptrs, lows, chunk = [], [], [], 0
+            for i, (p, a) in enumerate(zip(self.params, anchor)):
+                if p.numel() == 0:
+                    continue
+                rows.append([p.data_ptr(), 0, 0, 0, p.numel(), chunk])
+                ptrs.append(a.data_ptr())
+                if self.master_weights:
+                    lows.append(self._low[i].data_ptr())
+                chunk += (p.numel() + self.CHUNK - 1) // self.CHUNK
+            if not rows:
+                raise _lib.LcvError(f"{name}: drift_norm() over no elements")
+            self._drift = (key, torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(ptrs, dtype=torch.int64).to(dev),
+                           torch.tensor(lows, dtype=torch.int64).to(dev) if lows else None, len(rows), chunk,
+                           torch.empty((chunk,), dtype=F32, device=dev))
+        _, d, a_desc, low_desc, n, chunks, part = self._drift
+        out = torch.empty(2, dtype=F32, device=dev)
+        call("lcv_master_drift_sumsq", _ptr(d), _ptr(low_desc), _ptr(a_desc), n, chunks, _ptr(part), chunks * 4, _ptr(out),
+             _stream())
+        return out[1]
 
     def _init_accum(self, grad_accum: int) -> None:
         """Zeroed fp32 accumulators (+4 B / parameter) when `grad_accum` > 1; nothing at 1."""
@@ -819,6 +888,9 @@ class FusedAdamWClip:
             if self.master_weights:      # the low-word pointers, parallel to the table
                 self._low_desc = torch.tensor([self._low[i].data_ptr() for i in sel],
                                               dtype=torch.int64).to(self.params[0].device)
+            if self._anchor:             # the base-word pointers
+                self._anchor_desc = torch.tensor([self._anchor[i].data_ptr() for i in sel],
+                                                 dtype=torch.int64).to(self.params[0].device)
             if self.moments_8bit:        # and the block-scale pointers
                 self._scale_desc = torch.tensor([self._scales[i].data_ptr() for i in sel],
                                                 dtype=torch.int64).to(self.params[0].device)
@@ -876,7 +948,17 @@ class FusedAdamWClip:
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
-        if self.moments_8bit:
+        if self._anchor:                 # decay toward the base words (include/lcv_hip_anchor.h)
+            coef = _ptr(self._norm_coef) if self._have_coef else None
+            hyper = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                     self.step_count)
+            if self.moments_8bit:
+                call("lcv_master_adamw8_step_anchor", _ptr(d), _ptr(self._low_desc), _ptr(self._scale_desc),
+                     _ptr(self._anchor_desc), self._n_active, self._total_chunks, coef, *hyper, _stream())
+            else:
+                call("lcv_master_adamw_step_anchor", _ptr(d), _ptr(self._low_desc), _ptr(self._anchor_desc), self._n_active,
+                     self._total_chunks, coef, *hyper, 1 if self.grad_accum > 1 else 0, _stream())
+        elif self.moments_8bit:
             call("lcv_master_adamw8_step", _ptr(d), _ptr(self._low_desc), _ptr(self._scale_desc), self._n_active,
                  self._total_chunks, _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
                  float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
@@ -1208,9 +1290,10 @@ class FusedSGDClip(FusedAdamWClip):
     """clip_grad_norm_ + SGD(momentum=0, weight_decay).step over a parameter list in two launches — the default
     optimizer of full-model TTA (lora_experiment/scripts/run_full_tta.py:138-144, 179-180).  No optimizer state, unless
     `master_weights=True` adds the int16 low words of FusedAdamWClip's master-weight form (+2 B / parameter), and with it
-    `grad_accum=N` the fp32 accumulators of FusedAdamWClip's accumulation form (+4 B / parameter)."""
+    `grad_accum=N` the fp32 accumulators of FusedAdamWClip's accumulation form (+4 B / parameter), or `anchor=[...]` the
+    decay toward those base words of FusedAdamWClip's anchor form (nothing allocated)."""
 
-    def __init__(self, params, lr=1e-5, weight_decay=0.01, master_weights=False, *, grad_accum: int = 1):
+    def __init__(self, params, lr=1e-5, weight_decay=0.01, master_weights=False, *, grad_accum: int = 1, anchor=None):
         self.params = [p for p in params]
         if not self.params:
             raise ValueError("optimizer got an empty parameter list")
@@ -1220,6 +1303,7 @@ class FusedSGDClip(FusedAdamWClip):
         self.f32 = dt == F32
         self.param_groups = [dict(params=self.params, lr=lr, weight_decay=weight_decay)]
         self._init_master(master_weights)
+        self._init_anchor(anchor)
         self.exp_avg = self.params            # the descriptor table has moment slots; SGD never reads them
         self.exp_avg_sq = self.params
         self._scales = []
@@ -1242,7 +1326,11 @@ class FusedSGDClip(FusedAdamWClip):
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
-        if self.grad_accum > 1:
+        if self._anchor:                 # decay toward the base words (include/lcv_hip_anchor.h)
+            call("lcv_master_sgd_step_anchor", _ptr(d), _ptr(self._low_desc), _ptr(self._anchor_desc), self._n_active,
+                 self._total_chunks, _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]),
+                 float(g["weight_decay"]), 1 if self.grad_accum > 1 else 0, _stream())
+        elif self.grad_accum > 1:
             call("lcv_master_sgd_step_g32", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
                  _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
         elif self.master_weights:

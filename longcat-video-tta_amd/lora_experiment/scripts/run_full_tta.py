@@ -43,6 +43,7 @@ def build_parser():
                    help="fp32 master weights: +2 B / parameter of low words, fp32 moments under adamw (include/lcv_hip_master.h)")
     C.add_adam_8bit_arg(p)
     C.add_grad_accum_arg(p)
+    C.add_decay_to_base_arg(p)
     p.add_argument("--batch-videos", type=int, default=1)
     p.add_argument("--batch-method", type=str, default="similarity", choices=["similarity", "sequential"])
     p.add_argument("--retrieval-pool-dir", type=str, default=None)
@@ -51,7 +52,7 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    return C.parse_with_grad_accum(build_parser(), argv)
+    return C.parse_with_decay_to_base(build_parser(), argv)
 
 
 def main(argv=None):
@@ -87,7 +88,7 @@ def main(argv=None):
             "training": {"learning_rate": args.learning_rate, "num_steps": args.num_steps, "warmup_steps": args.warmup_steps,
                          "weight_decay": args.weight_decay, "max_grad_norm": args.max_grad_norm, "optimizer": args.optimizer,
                          "master_weights": args.master_weights, "adam_8bit": args.adam_8bit,
-                         "grad_accum": args.grad_accum,
+                         "grad_accum": args.grad_accum, **({"decay_to_base": True} if args.decay_to_base else {}),
                          "total_params": total_params, "trainable_params": trainable_params},
             "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                            "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
@@ -127,11 +128,15 @@ def main(argv=None):
                                                max_grad_norm=args.max_grad_norm, device=device, dtype=torch.bfloat16,
                                                early_stopper=es, optimizer_type=args.optimizer, train_latents_variants=variants,
                                                master_weights=args.master_weights, moments_8bit=args.adam_8bit,
-                                               grad_accum=args.grad_accum)
+                                               grad_accum=args.grad_accum,
+                                               # the anchors are the reset's base copy: nothing more is allocated
+                                               **(dict(decay_to_base=True, base_state=base_state) if args.decay_to_base else {}))
             result = {"idx": idx, "video_name": e["name"], "video_path": e["path"], "caption": blob.get("caption", ""),
                       "train_time": tr["train_time"], "es_check_time": tr.get("es_check_time", 0.0),
                       "final_loss": tr["losses"][-1] if tr["losses"] else None, "num_train_steps": len(tr["losses"]),
                       "batch_size": 1, "num_neighbors": 0, "early_stopping_info": tr.get("early_stopping_info"), "success": True}
+            if args.decay_to_base:
+                result["drift_norm"] = tr["drift_norm"]
             gen_time = 0.0
             if not args.skip_generation:
                 out, gen_time = R.generate_continuation(pipe, blob, args, idx, device, entry=e)

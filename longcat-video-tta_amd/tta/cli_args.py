@@ -115,6 +115,21 @@ def parse_with_grad_accum(parser, argv=None):
     return args
 
 
+def add_decay_to_base_arg(parser):
+    parser.add_argument("--decay-to-base", action="store_true",
+                        help="with --master-weights: the weight decay pulls toward the base weights instead of toward zero, and "
+                             "every result row carries drift_norm, the distance from them (include/lcv_hip_anchor.h)")
+
+
+def parse_with_decay_to_base(parser, argv=None):
+    """parse_with_grad_accum, then the refusal of --decay-to-base as the parser's own one-line error (exit status 2)."""
+    args = parse_with_grad_accum(parser, argv)
+    if args.decay_to_base and not args.master_weights:
+        parser.error("--decay-to-base needs --master-weights (a pull of lr * wd * (w - w0) is far below half a bf16 ulp; the "
+                     "anchor steps exist for the master-weight form only)")
+    return args
+
+
 def normalize_tta_frame_args(args):
     """Post-parse normalisation of lora_experiment/scripts/run_lora_tta.py:743-758 (GT-leak clamp included)."""
     if args.tta_total_frames is None:

@@ -50,27 +50,47 @@ def _trainable(dit: nn.Module) -> List[torch.Tensor]:
 
 
 def _make_optimizer(kind: str, params, lr: float, weight_decay: float, master_weights: bool = False,
-                    moments_8bit: bool = False, grad_accum: int = 1):
+                    moments_8bit: bool = False, grad_accum: int = 1, anchor=None):
     if kind == "adamw":
         return FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
-                              master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum)
+                              master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum, anchor=anchor)
     if kind == "sgd":
         if moments_8bit:
             raise ValueError("moments_8bit is for optimizer_type 'adamw': SGD keeps no moments")
-        return FusedSGDClip(params, lr=lr, weight_decay=weight_decay, master_weights=master_weights, grad_accum=grad_accum)
+        return FusedSGDClip(params, lr=lr, weight_decay=weight_decay, master_weights=master_weights, grad_accum=grad_accum,
+                            anchor=anchor)
     raise ValueError(f"unknown optimizer_type {kind!r} (sgd | adamw)")
 
 
+def _anchors(dit: nn.Module, base_state: Optional[Dict[str, torch.Tensor]]) -> List[torch.Tensor]:
+    """The base words of the trainable parameters, in `_trainable` order: the `base_state` entries matched by name (not
+    copied), or bf16 clones of the parameters as they are now."""
+    named = [(name, p) for name, p in dit.named_parameters() if p.requires_grad]
+    if base_state is None:
+        return [p.detach().clone() for _, p in named]
+    missing = [name for name, _ in named if name not in base_state]
+    if missing:
+        raise ValueError(f"base_state lacks {len(missing)} trainable parameters, the first: {missing[0]!r}")
+    return [base_state[name] for name, _ in named]
+
+
 def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper, optimizer_type,
-         master_weights=False, moments_8bit=False, grad_accum=1):
+         master_weights=False, moments_8bit=False, grad_accum=1, decay_to_base=False, base_state=None):
     params = _trainable(dit)
+    # `decay_to_base`: the weight decay pulls toward the base words (include/lcv_hip_anchor.h), which are the caller's
+    # `base_state` entries or, without one, +2 B / parameter of clones; a `base_state` alone only measures the drift
+    want_drift = bool(decay_to_base) or base_state is not None
+    anchor = _anchors(dit, base_state) if want_drift else None
     # made per call, so per video: the per-video reset writes the bf16 words, and the low words of `master_weights`
     # (+2 B / parameter; AdamW: +8 B of fp32 moments, or +2.016 B of 8-bit ones under `moments_8bit`) start at zero next to them;
     # `grad_accum` > 1 adds +4 B / parameter of fp32 accumulators (54 GB for the whole model: a memory decision)
-    opt = _make_optimizer(optimizer_type, params, lr, weight_decay, master_weights, moments_8bit, grad_accum)
+    opt = _make_optimizer(optimizer_type, params, lr, weight_decay, master_weights, moments_8bit, grad_accum,
+                          anchor=anchor if decay_to_base else None)
     out = run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
                          num_steps, lr, warmup_steps, early_stopper, grad_accum=grad_accum)
     opt.zero_grad(set_to_none=True)            # the gradients of 13.6 B parameters are dead weight during generation
+    if want_drift:                             # |theta - theta0| over the trainable parameters, read once per video
+        out["drift_norm"] = float(opt.drift_norm(anchor).item())
     return out
 
 
@@ -80,16 +100,18 @@ def finetune_full_on_conditioning(dit: nn.Module, cond_latents: torch.Tensor, tr
                                   max_grad_norm: float = 1.0, device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                                   early_stopper: Optional[AnchoredEarlyStopper] = None,
                                   train_latents_variants: Optional[List[Dict]] = None, optimizer_type: str = "sgd",
-                                  *, grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
+                                  *, decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
+                                  grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
     return _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper,
-                optimizer_type, master_weights, moments_8bit, grad_accum)
+                optimizer_type, master_weights, moments_8bit, grad_accum, decay_to_base, base_state)
 
 
 def finetune_full_batch(dit: nn.Module, batch_data: List[Dict], num_steps: int = 10, lr: float = 1e-5, warmup_steps: int = 2,
                         weight_decay: float = 0.01, max_grad_norm: float = 1.0, device: str = "cuda",
                         dtype: torch.dtype = torch.bfloat16, optimizer_type: str = "sgd",
-                        *, grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
+                        *, decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
+                        grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Round-robin over the eval video and its retrieved neighbours (run_full_tta.py:230-306); no early stopping."""
     return _run(dit, _RoundRobin(batch_data, device), num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype,
-                None, optimizer_type, master_weights, moments_8bit, grad_accum)
+                None, optimizer_type, master_weights, moments_8bit, grad_accum, decay_to_base, base_state)
