@@ -1,4 +1,5 @@
-// What the master-weight optimizer kernels share (optim_master.hip, optim_moments8.hip, optim_accum.hip, optim_anchor.hip):
+// What the master-weight optimizer kernels share (optim_master.hip, optim_moments8.hip, optim_accum.hip, optim_anchor.hip,
+// optim_ema.hip):
 // the (bf16 word, int16 low word) <-> fp32 master format, AdamW's scalars and its per-element op sequences.  All of them are
 // built with -ffp-contract=off.
 #pragma once
@@ -85,4 +86,12 @@ __device__ __forceinline__ void master_adamw_anchor_elem(float& p, float& m, flo
   const float t = a * d;
   p = p - t;
   master_adamw_moments_update(p, m, v, g, s);
+}
+
+// ---- the fp32 average of the masters over the steps (include/lcv_hip_ema.h) ----
+// e = beta * e + (1 - beta) * w in the form w - b * (w - e): b = 0 gives w and w = e gives e back, both exactly
+__device__ __forceinline__ float master_ema_elem(float w, float e, float b) {
+  const float d = w - e;
+  const float t = b * d;
+  return w - t;
 }

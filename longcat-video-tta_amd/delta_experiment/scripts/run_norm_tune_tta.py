@@ -30,12 +30,13 @@ def build_parser():
     C.add_adam_8bit_arg(p)
     C.add_grad_accum_arg(p)
     C.add_decay_to_base_arg(p)
+    C.add_weight_ema_args(p)
     R.add_shared_groups(p, clip_gate=False)
     return p
 
 
 def parse_args(argv=None):
-    return C.parse_with_decay_to_base(build_parser(), argv)
+    return C.parse_with_weight_ema(build_parser(), argv, C.parse_with_decay_to_base)
 
 
 def main(argv=None):
@@ -46,7 +47,8 @@ def main(argv=None):
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_norm_params(
             w, w.tuned_params, cond, train, pe, pm, num_steps=args.norm_steps, lr=args.norm_lr, device=device, dtype=torch.bfloat16,
             early_stopper=es, train_latents_variants=tv, master_weights=args.master_weights,
-            moments_8bit=args.adam_8bit, grad_accum=args.grad_accum, decay_to_base=args.decay_to_base),
+            moments_8bit=args.adam_8bit, grad_accum=args.grad_accum, decay_to_base=args.decay_to_base,
+            **C.weight_ema_kwargs(args)),
         params_of=lambda w: w.tuned_params,
         result_extra=lambda opt: {k: opt[k] for k in ("norm_param_drift", "delta_norm", "drift_norm") if k in opt},
         # this runner writes no config.json (as the reference's does not): the flag is recorded here, when it is set
@@ -54,7 +56,8 @@ def main(argv=None):
                       **({"master_weights": True} if args.master_weights else {}),
                       **({"adam_8bit": True} if args.adam_8bit else {}),
                       **({"grad_accum": args.grad_accum} if args.grad_accum > 1 else {}),
-                      **({"decay_to_base": True} if args.decay_to_base else {})},
+                      **({"decay_to_base": True} if args.decay_to_base else {}),
+                      **C.weight_ema_record(args)},
         file_suffix="norm_tune", cleanup=lambda w: w.restore())
 
 

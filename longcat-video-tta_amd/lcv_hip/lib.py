@@ -130,6 +130,14 @@ _SIGNATURES_ANCHOR = {
     "lcv_master_drift_sumsq": [P, P, P, I64, I64, P, I64, P, P],
 }
 
+# include/lcv_hip_ema.h (a header of its own: the fp32 weight average over the optimizer steps); `ema` is a device array of pointers
+# to the fp32 averages, parallel to the descriptor table, after `low`; update takes beta in front of the stream; all return int
+_SIGNATURES_EMA = {
+    "lcv_master_ema_load": [P, P, P, I64, I64, P],
+    "lcv_master_ema_update": [P, P, P, I64, I64, F64, P],
+    "lcv_master_ema_swap": [P, P, P, I64, I64, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -187,7 +195,7 @@ def load():
     lib.lcv_tn_skinny_dropout_ws_bytes.argtypes = [I64, I64, I64]
     for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
                        + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())
-                       + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items())):
+                       + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

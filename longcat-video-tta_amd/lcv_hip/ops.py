@@ -591,6 +591,14 @@ def tn_skinny(g, x, R, scale=1.0):
     return out
 
 
+def ema_beta(beta: float, t: int, warmup: bool = False) -> float:
+    """The beta of the t-th update (t counts from 1) of the weight average: `beta`, or under `warmup` the smaller of it and
+    (1 + t) / (10 + t) - 0.18, 0.25, ..., 0.55 at t = 10, 0.70 at t = 20 - so that an average started at the base weights does
+    not lag a run of 10-20 steps.  Formed in double."""
+    beta = float(beta)
+    return min(beta, (1.0 + t) / (10.0 + t)) if warmup else beta
+
+
 # ===================================================================== fused clip + AdamW
 class FusedAdamWClip:
     """clip_grad_norm_ + AdamW.step over a fixed parameter list in two launches (norm, update).
@@ -617,7 +625,12 @@ class FusedAdamWClip:
 
     `anchor=[...]` (with `master_weights=True` only; contiguous bf16 GPU tensors shaped like `params`, held by reference, not
     copied) turns the weight decay into a pull toward those base words instead of toward zero (include/lcv_hip_anchor.h): the
-    step reads 2 B / parameter more and allocates nothing.  `drift_norm()` is the distance from them."""
+    step reads 2 B / parameter more and allocates nothing.  `drift_norm()` is the distance from them.
+
+    `enable_weight_ema(beta)` (with `master_weights=True` only, once, before the first step) keeps an fp32 average of the masters
+    (include/lcv_hip_ema.h, +4 B / parameter): every `step()` ends with e = w - beta_t * (w - e) in a launch of its own.
+    `ema_swap()` exchanges the average and the masters bit for bit, so the model can be scored or run with the average and
+    training can go on afterwards; while the average is in the parameters (`ema_in_params`) the optimizer refuses to train."""
     CHUNK = 2048
     NORM_SLOTS = 64   # partial sums of squares per tensor (csrc/optim.hip)
     MOMENTS8_BLOCK = 512   # elements per scale (LCV_MOMENTS8_BLOCK)
@@ -625,6 +638,10 @@ class FusedAdamWClip:
     grad_accum = 1
     _anchor = ()
     _drift = None
+    weight_ema = None        # the beta of enable_weight_ema(), or None: no average is kept
+    ema_in_params = False    # True between an ema_swap() and the next: the parameters hold the average
+    _ema = ()
+    _ema_table_cache = None
 
     def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-8, master_weights=False,
                  moments_8bit=False, *, grad_accum: int = 1, anchor=None):
@@ -743,6 +760,84 @@ class FusedAdamWClip:
              _stream())
         return out[1]
 
+    def enable_weight_ema(self, beta: float, warmup: bool = False) -> None:
+        """Start the fp32 average of the masters (+4 B / parameter) at the masters themselves (lcv_master_ema_load).  Once, before
+        the first `step()`.  `warmup`: the t-th update uses `ema_beta(beta, t, True)` instead of `beta`."""
+        name = type(self).__name__
+        if self.weight_ema is not None:
+            raise _lib.LcvError(f"{name}: enable_weight_ema() was already called")
+        beta = float(beta)
+        if not 0.0 <= beta < 1.0:            # a NaN fails both
+            raise ValueError(f"{name}: the beta of the weight average must be in [0, 1), got {beta}")
+        if not self.master_weights:
+            raise _lib.LcvError(f"{name}: enable_weight_ema() needs master_weights=True (an increment (1 - beta) * (w - e) is far "
+                                "below half a bf16 ulp; the average is kept in fp32 beside the master weights only)")
+        if self.step_count:
+            raise _lib.LcvError(f"{name}: enable_weight_ema() comes before the first step(), not after {self.step_count}")
+        self._ema = [torch.empty(p.shape, dtype=F32, device=p.device) for p in self.params]
+        self.weight_ema = beta
+        self._ema_warmup = bool(warmup)
+        self.ema_in_params = False
+        self.ema_reset()
+
+    def _ema_table(self):
+        """The descriptor table over ALL non-empty parameters (with or without a gradient, as drift_norm's) with the low-word
+        and the average pointers beside it, all three under one cache key."""
+        key = tuple(p.data_ptr() for p in self.params)
+        if self._ema_table_cache is None or self._ema_table_cache[0] != key:
+            dev = self.params[0].device
+            rows, lows, emas, chunk = [], [], [], 0
+            for p, low, e in zip(self.params, self._low, self._ema):
+                if p.numel() == 0:
+                    continue
+                rows.append([p.data_ptr(), 0, 0, 0, p.numel(), chunk])
+                lows.append(low.data_ptr())
+                emas.append(e.data_ptr())
+                chunk += (p.numel() + self.CHUNK - 1) // self.CHUNK
+            if not rows:
+                raise _lib.LcvError(f"{type(self).__name__}: a weight average over no elements")
+            self._ema_table_cache = (key, torch.tensor(rows, dtype=torch.int64).to(dev),
+                                     torch.tensor(lows, dtype=torch.int64).to(dev),
+                                     torch.tensor(emas, dtype=torch.int64).to(dev), len(rows), chunk)
+        _, d, low_desc, ema_desc, n, chunks = self._ema_table_cache
+        return _ptr(d), _ptr(low_desc), _ptr(ema_desc), n, chunks
+
+    def _ema_needs(self, what: str) -> None:
+        if self.weight_ema is None:
+            raise _lib.LcvError(f"{type(self).__name__}: {what} needs enable_weight_ema()")
+
+    def _ema_guard(self, what: str) -> None:
+        """Nobody trains the average by accident."""
+        if self.ema_in_params:
+            raise _lib.LcvError(f"{type(self).__name__}: {what} while the parameters hold the weight average (ema_in_params); "
+                                "call ema_swap() to put the masters back first")
+
+    def ema_tensors(self):
+        """The fp32 averages themselves, one per parameter in `params` order (empty without enable_weight_ema()).  While
+        `ema_in_params` they hold the masters."""
+        return list(self._ema)
+
+    def ema_reset(self) -> None:
+        """Load the average again from the masters and start its update count (the t of `ema_beta`) at zero."""
+        self._ema_needs("ema_reset()")
+        self._ema_guard("ema_reset()")
+        call("lcv_master_ema_load", *self._ema_table(), _stream())
+        self._ema_t = 0
+
+    def _ema_update(self) -> None:
+        """What step() ends with when an average is kept: its own launch after whichever step kernel ran."""
+        self._ema_t += 1
+        call("lcv_master_ema_update", *self._ema_table(), ema_beta(self.weight_ema, self._ema_t, self._ema_warmup), _stream())
+
+    def ema_swap(self) -> None:
+        """Exchange the average and the masters (lcv_master_ema_swap) and toggle `ema_in_params`: after one call the parameters
+        are the average in valid master format (bf16 word = its round-to-nearest), after two every bit is back."""
+        self._ema_needs("ema_swap()")
+        call("lcv_master_ema_swap", *self._ema_table(), _stream())
+        self.ema_in_params = not self.ema_in_params
+        global PARAM_EPOCH           # the parameters changed under cached copies of them, as after a step
+        PARAM_EPOCH += 1
+
     def _init_accum(self, grad_accum: int) -> None:
         """Zeroed fp32 accumulators (+4 B / parameter) when `grad_accum` > 1; nothing at 1."""
         self.grad_accum = int(grad_accum)
@@ -771,6 +866,7 @@ class FusedAdamWClip:
         """One micro-step: acc += float(.grad) * (1 / grad_accum) over the parameters that hold a `.grad`
         (lcv_grad_accumulate), then those `.grad`s are dropped."""
         name = type(self).__name__
+        self._ema_guard("accumulate()")
         if self.grad_accum == 1:
             raise _lib.LcvError(f"{name}: accumulate() needs grad_accum > 1")
         if self._micro >= self.grad_accum:
@@ -818,7 +914,8 @@ class FusedAdamWClip:
 
     def resync(self) -> None:
         """Zero the low words: the masters become exactly the bf16 words the parameters hold now.  Call it after anyone
-        but this optimizer has written the parameters."""
+        but this optimizer has written the parameters.  A weight average (enable_weight_ema) is left alone: it neither moves to
+        the new masters nor restarts; `ema_reset()` does that."""
         for low in self._low:
             low.zero_()
 
@@ -909,6 +1006,7 @@ class FusedAdamWClip:
         return self.f32 or self.grad_accum > 1
 
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
+        self._ema_guard("clip_grad_norm_()")
         d = self._descriptors()
         if _DETERMINISTIC:
             if getattr(self, "_det_ws", None) is None:      # the mode was switched on after the table was built
@@ -945,6 +1043,7 @@ class FusedAdamWClip:
         return total
 
     def step(self):
+        self._ema_guard("step()")
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
@@ -975,6 +1074,8 @@ class FusedAdamWClip:
                  _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
                  float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
         self._have_coef = False
+        if self.weight_ema is not None:  # the average follows the masters this step left (include/lcv_hip_ema.h)
+            self._ema_update()
         global PARAM_EPOCH
         PARAM_EPOCH += 1
 
@@ -1291,7 +1392,8 @@ class FusedSGDClip(FusedAdamWClip):
     optimizer of full-model TTA (lora_experiment/scripts/run_full_tta.py:138-144, 179-180).  No optimizer state, unless
     `master_weights=True` adds the int16 low words of FusedAdamWClip's master-weight form (+2 B / parameter), and with it
     `grad_accum=N` the fp32 accumulators of FusedAdamWClip's accumulation form (+4 B / parameter), or `anchor=[...]` the
-    decay toward those base words of FusedAdamWClip's anchor form (nothing allocated)."""
+    decay toward those base words of FusedAdamWClip's anchor form (nothing allocated); `enable_weight_ema(beta)` keeps the fp32
+    average of FusedAdamWClip's form (+4 B / parameter)."""
 
     def __init__(self, params, lr=1e-5, weight_decay=0.01, master_weights=False, *, grad_accum: int = 1, anchor=None):
         self.params = [p for p in params]
@@ -1323,6 +1425,7 @@ class FusedSGDClip(FusedAdamWClip):
         return 0
 
     def step(self):
+        self._ema_guard("step()")
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
@@ -1340,5 +1443,7 @@ class FusedSGDClip(FusedAdamWClip):
             call("lcv_sgd_step", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
                  _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
         self._have_coef = False
+        if self.weight_ema is not None:  # the average follows the masters this step left (include/lcv_hip_ema.h)
+            self._ema_update()
         global PARAM_EPOCH
         PARAM_EPOCH += 1

@@ -44,6 +44,7 @@ def build_parser():
     C.add_adam_8bit_arg(p)
     C.add_grad_accum_arg(p)
     C.add_decay_to_base_arg(p)
+    C.add_weight_ema_args(p)
     p.add_argument("--batch-videos", type=int, default=1)
     p.add_argument("--batch-method", type=str, default="similarity", choices=["similarity", "sequential"])
     p.add_argument("--retrieval-pool-dir", type=str, default=None)
@@ -52,7 +53,7 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    return C.parse_with_decay_to_base(build_parser(), argv)
+    return C.parse_with_weight_ema(build_parser(), argv, C.parse_with_decay_to_base)
 
 
 def main(argv=None):
@@ -89,6 +90,7 @@ def main(argv=None):
                          "weight_decay": args.weight_decay, "max_grad_norm": args.max_grad_norm, "optimizer": args.optimizer,
                          "master_weights": args.master_weights, "adam_8bit": args.adam_8bit,
                          "grad_accum": args.grad_accum, **({"decay_to_base": True} if args.decay_to_base else {}),
+                         **C.weight_ema_record(args),
                          "total_params": total_params, "trainable_params": trainable_params},
             "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                            "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
@@ -130,7 +132,8 @@ def main(argv=None):
                                                master_weights=args.master_weights, moments_8bit=args.adam_8bit,
                                                grad_accum=args.grad_accum,
                                                # the anchors are the reset's base copy: nothing more is allocated
-                                               **(dict(decay_to_base=True, base_state=base_state) if args.decay_to_base else {}))
+                                               **(dict(decay_to_base=True, base_state=base_state) if args.decay_to_base else {}),
+                                               **C.weight_ema_kwargs(args))
             result = {"idx": idx, "video_name": e["name"], "video_path": e["path"], "caption": blob.get("caption", ""),
                       "train_time": tr["train_time"], "es_check_time": tr.get("es_check_time", 0.0),
                       "final_loss": tr["losses"][-1] if tr["losses"] else None, "num_train_steps": len(tr["losses"]),

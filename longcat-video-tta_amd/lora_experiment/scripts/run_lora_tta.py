@@ -58,7 +58,8 @@ def build_parser():
     p.add_argument("--target-modules", type=str, default="qkv,proj")
     p.add_argument("--lora-target-blocks", type=str, default="all")
     p.add_argument("--use-builtin-lora", action="store_true")
-    p.add_argument("--save-lora-weights", action="store_true")
+    p.add_argument("--save-lora-weights", action="store_true",
+                   help="write every video's adapters; with --weight-ema they are the averaged adapters")
     p.add_argument("--learning-rate", type=float, default=2e-4)
     p.add_argument("--num-steps", type=int, default=20)
     p.add_argument("--warmup-steps", type=int, default=3)
@@ -68,6 +69,7 @@ def build_parser():
                    help="fp32 master weights for the bf16 adapters (include/lcv_hip_master.h); both LoRA implementations")
     C.add_adam_8bit_arg(p)
     C.add_grad_accum_arg(p)
+    C.add_weight_ema_args(p)
     p.add_argument("--max-videos", type=int, default=100)
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--device", type=str, default="cuda")
@@ -94,7 +96,7 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    return C.parse_with_grad_accum(build_parser(), argv)
+    return C.parse_with_weight_ema(build_parser(), argv)
 
 
 def main(argv=None):
@@ -160,7 +162,8 @@ def main(argv=None):
             "training": {"learning_rate": args.learning_rate, "num_steps": args.num_steps,
                          "warmup_steps": args.warmup_steps, "weight_decay": args.weight_decay,
                          "max_grad_norm": args.max_grad_norm, "master_weights": args.master_weights,
-                         "adam_8bit": args.adam_8bit, "grad_accum": args.grad_accum},
+                         "adam_8bit": args.adam_8bit, "grad_accum": args.grad_accum,
+                         **C.weight_ema_record(args)},
             "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                            "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
                            "resolution": args.resolution},
@@ -202,7 +205,8 @@ def main(argv=None):
                                                max_grad_norm=args.max_grad_norm, device=device, dtype=torch.bfloat16,
                                                early_stopper=es, lora_param_fn=get_params, train_latents_variants=variants,
                                                master_weights=args.master_weights, moments_8bit=args.adam_8bit,
-                                               grad_accum=args.grad_accum)
+                                               grad_accum=args.grad_accum,
+                                               **C.weight_ema_kwargs(args))
             result = {"idx": idx, "video_name": e["name"], "video_path": e["path"], "caption": blob.get("caption", ""),
                       "train_time": tr["train_time"], "es_check_time": tr.get("es_check_time", 0.0),
                       "final_loss": tr["losses"][-1] if tr["losses"] else None, "num_train_steps": len(tr["losses"]),

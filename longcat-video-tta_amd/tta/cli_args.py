@@ -130,6 +130,46 @@ def parse_with_decay_to_base(parser, argv=None):
     return args
 
 
+def add_weight_ema_args(parser):
+    parser.add_argument("--weight-ema", type=float, default=None, metavar="BETA",
+                        help="with --master-weights: keep an fp32 exponential moving average of the weights over the optimizer "
+                             "steps (e = BETA * e + (1 - BETA) * w, +4 B / parameter, include/lcv_hip_ema.h); the early stopper "
+                             "scores the average and generation (and --save-lora-weights, which then writes the averaged "
+                             "adapters) reads it")
+    parser.add_argument("--weight-ema-warmup", action="store_true",
+                        help="with --weight-ema: BETA_t = min(BETA, (1 + t) / (10 + t)) at the t-th step, so an average that starts "
+                             "at the base weights does not lag a short run")
+
+
+def parse_with_weight_ema(parser, argv=None, parse=None):
+    """`parse` (default parse_with_grad_accum), then the refusals of --weight-ema as the parser's own one-line errors (exit
+    status 2)."""
+    args = (parse or parse_with_grad_accum)(parser, argv)
+    if args.weight_ema_warmup and args.weight_ema is None:
+        parser.error("--weight-ema-warmup needs --weight-ema BETA")
+    if args.weight_ema is None:
+        return args
+    if not args.master_weights:
+        parser.error("--weight-ema needs --master-weights (an increment (1 - BETA) * (w - e) is far below half a bf16 ulp; the "
+                     "average is kept in fp32 beside the master weights only)")
+    if not 0.0 <= args.weight_ema < 1.0:         # a NaN fails both
+        parser.error(f"--weight-ema BETA must be in [0, 1), got {args.weight_ema}")
+    if getattr(args, "also_tune_delta", False):
+        parser.error("--weight-ema cannot be combined with --also-tune-delta (the fp32 delta vector has no master-weight form "
+                     "to average beside)")
+    return args
+
+
+def weight_ema_kwargs(args) -> dict:
+    """The loop functions' keywords for --weight-ema; nothing when the flag is absent."""
+    return {} if args.weight_ema is None else {"weight_ema": args.weight_ema, "ema_warmup": args.weight_ema_warmup}
+
+
+def weight_ema_record(args) -> dict:
+    """What config.json (`training`) and the norm-tuning summary.json record of --weight-ema; nothing when the flag is absent."""
+    return {} if args.weight_ema is None else {"weight_ema": args.weight_ema, "weight_ema_warmup": args.weight_ema_warmup}
+
+
 def normalize_tta_frame_args(args):
     """Post-parse normalisation of lora_experiment/scripts/run_lora_tta.py:743-758 (GT-leak clamp included)."""
     if args.tta_total_frames is None:

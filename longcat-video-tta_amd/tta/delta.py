@@ -219,7 +219,8 @@ class FiLMAdapterWrapper(_HookedWrapper):
 
 def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bool, cond_latents, train_latents,
               prompt_embeds, prompt_mask, num_steps, lr, device, dtype, early_stopper, train_latents_variants,
-              master_weights=False, moments_8bit=False, grad_accum=1, decay_to_base=False, info=None):
+              master_weights=False, moments_8bit=False, grad_accum=1, decay_to_base=False, info=None,
+              weight_ema=None, ema_warmup=False):
     """AdamW(0.9, 0.999, wd 0.01, eps 1e-15), clip at 1.0, no warm-up (run_delta_a.py:224-305 and its siblings) on the
     shared engine.  Clipping comes in the three shapes the reference scripts use: per parameter (delta-B,
     run_delta_b.py:386-388), one global norm, or — bf16 norm weights tuned together with an fp32 delta vector — one fused
@@ -229,7 +230,13 @@ def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bo
     the fp32 accumulators belong to the master-weight form, and the joint clip of a second, fp32 optimizer reads `.grad`s.
     `decay_to_base` (the norm-tuning path only, needs `master_weights`) makes the weight decay of the bf16 optimizers a pull
     toward bf16 clones of their parameters taken here (include/lcv_hip_anchor.h) and puts their distance from those clones
-    into `info["drift_norm"]` after the loop; an fp32 delta vector keeps its decay toward zero, which is its base."""
+    into `info["drift_norm"]` after the loop; an fp32 delta vector keeps its decay toward zero, which is its base.
+    `weight_ema` (the norm-tuning path only, needs `master_weights`) keeps the fp32 average of the bf16 parameters over the steps
+    (include/lcv_hip_ema.h), which the stopper scores and the parameters end as; like `grad_accum` it needs every parameter
+    bf16."""
+    if weight_ema is not None and any(p.dtype != torch.bfloat16 for p in params):
+        raise ValueError("weight_ema cannot train fp32 parameters (the delta vector of --also-tune-delta): the average is kept "
+                         "beside master weights, which their optimizer does not have")
     if grad_accum > 1 and any(p.dtype != torch.bfloat16 for p in params):
         raise ValueError("grad_accum > 1 cannot train fp32 parameters (the delta vector of --also-tune-delta): their optimizer "
                          "has no accumulators and the joint clip reads .grad")
@@ -246,6 +253,9 @@ def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bo
                            moments_8bit=moments_8bit and g[0].dtype == torch.bfloat16, grad_accum=grad_accum,
                            anchor=[p.detach().clone() for p in g] if decay_to_base and g[0].dtype == torch.bfloat16 else None)
             for g in groups]
+    if weight_ema is not None:
+        for o in opts:
+            o.enable_weight_ema(weight_ema, ema_warmup)
 
     def clip_and_step():
         live = [o for o in opts if o.grad_accum > 1 or any(p.grad is not None for p in o.params)]
@@ -393,20 +403,22 @@ class NormTuneForward(nn.Module):
 def optimize_norm_params(wrapper: NormTuneForward, norm_params: List[nn.Parameter], cond_latents, train_latents, prompt_embeds,
                          prompt_mask, num_steps: int = 20, lr: float = 1e-3, device: str = "cuda",
                          dtype: torch.dtype = torch.bfloat16, early_stopper: Optional[AnchoredEarlyStopper] = None,
-                         train_latents_variants: Optional[List[Dict]] = None, *, decay_to_base: bool = False,
-                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
+                         train_latents_variants: Optional[List[Dict]] = None, *, weight_ema: Optional[float] = None,
+                         ema_warmup: bool = False, decay_to_base: bool = False, grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """run_norm_tune_tta.py:215-283 (same positional order: the parameter list is the second argument): AdamW(eps 1e-15) over
     `norm_params` (bf16 norm weights, plus the fp32 delta vector of --also-tune-delta), one global clip at 1.0.  Returns the
     reference's keys (`losses`, `early_stopping_info`) and, beside them, the check time and how far the parameters moved.
     `grad_accum` > 1 (micro-steps per update, fp32 accumulators) is for the bf16 norm weights alone: with the fp32 delta
     vector in the list it raises.  `decay_to_base` (with `master_weights`) decays the bf16 norm weights toward their values at
-    entry instead of toward zero and adds `drift_norm`, their distance from those values."""
+    entry instead of toward zero and adds `drift_norm`, their distance from those values.  `weight_ema` (with `master_weights`;
+    `ema_warmup` as in `lcv_hip.ops.ema_beta`) keeps the fp32 average of the bf16 norm weights over the steps: the stopper
+    scores it and the weights end as it; with the fp32 delta vector in the list it raises, as `grad_accum` does."""
     norm_params = list(norm_params)
     info: Dict = {}
     losses, est, es_state = _optimize(wrapper, norm_params, False, cond_latents, train_latents, prompt_embeds,
                                       prompt_mask, num_steps, lr, device, dtype, early_stopper, train_latents_variants,
                                       master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
-                                      decay_to_base=decay_to_base, info=info)
+                                      decay_to_base=decay_to_base, info=info, weight_ema=weight_ema, ema_warmup=ema_warmup)
     out = {"losses": losses, "early_stopping_info": es_state, "es_check_time": est}
     out.update(info)
     if getattr(wrapper, "_orig", None) and len(wrapper._orig) == len(wrapper.norm_params):

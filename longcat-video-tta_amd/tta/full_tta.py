@@ -75,7 +75,8 @@ def _anchors(dit: nn.Module, base_state: Optional[Dict[str, torch.Tensor]]) -> L
 
 
 def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper, optimizer_type,
-         master_weights=False, moments_8bit=False, grad_accum=1, decay_to_base=False, base_state=None):
+         master_weights=False, moments_8bit=False, grad_accum=1, decay_to_base=False, base_state=None, weight_ema=None,
+         ema_warmup=False):
     params = _trainable(dit)
     # `decay_to_base`: the weight decay pulls toward the base words (include/lcv_hip_anchor.h), which are the caller's
     # `base_state` entries or, without one, +2 B / parameter of clones; a `base_state` alone only measures the drift
@@ -86,10 +87,13 @@ def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, de
     # `grad_accum` > 1 adds +4 B / parameter of fp32 accumulators (54 GB for the whole model: a memory decision)
     opt = _make_optimizer(optimizer_type, params, lr, weight_decay, master_weights, moments_8bit, grad_accum,
                           anchor=anchor if decay_to_base else None)
+    if weight_ema is not None:                 # +4 B / parameter of fp32 average (54 GB for the whole model: a memory decision);
+        opt.enable_weight_ema(weight_ema, ema_warmup)   # run_adaptation scores it and leaves it in the parameters
     out = run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
                          num_steps, lr, warmup_steps, early_stopper, grad_accum=grad_accum)
     opt.zero_grad(set_to_none=True)            # the gradients of 13.6 B parameters are dead weight during generation
-    if want_drift:                             # |theta - theta0| over the trainable parameters, read once per video
+    if want_drift:                             # |theta - theta0| over the trainable parameters, read once per video (after the
+        # final swap of a weight average: the drift of the weights that generate)
         out["drift_norm"] = float(opt.drift_norm(anchor).item())
     return out
 
@@ -100,18 +104,20 @@ def finetune_full_on_conditioning(dit: nn.Module, cond_latents: torch.Tensor, tr
                                   max_grad_norm: float = 1.0, device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                                   early_stopper: Optional[AnchoredEarlyStopper] = None,
                                   train_latents_variants: Optional[List[Dict]] = None, optimizer_type: str = "sgd",
-                                  *, decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
+                                  *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
+                                  decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
                                   grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
     return _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper,
-                optimizer_type, master_weights, moments_8bit, grad_accum, decay_to_base, base_state)
+                optimizer_type, master_weights, moments_8bit, grad_accum, decay_to_base, base_state, weight_ema, ema_warmup)
 
 
 def finetune_full_batch(dit: nn.Module, batch_data: List[Dict], num_steps: int = 10, lr: float = 1e-5, warmup_steps: int = 2,
                         weight_decay: float = 0.01, max_grad_norm: float = 1.0, device: str = "cuda",
                         dtype: torch.dtype = torch.bfloat16, optimizer_type: str = "sgd",
-                        *, decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
+                        *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
+                        decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Round-robin over the eval video and its retrieved neighbours (run_full_tta.py:230-306); no early stopping."""
     return _run(dit, _RoundRobin(batch_data, device), num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype,
-                None, optimizer_type, master_weights, moments_8bit, grad_accum, decay_to_base, base_state)
+                None, optimizer_type, master_weights, moments_8bit, grad_accum, decay_to_base, base_state, weight_ema, ema_warmup)

@@ -84,9 +84,15 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
     `grad_accum=N` with N > 1 puts N micro-steps behind every optimizer step: `loss_at(step * N + k)`, backward, `grad_sync()`
     and `opt.accumulate()` (fp32 accumulators, include/lcv_hip_accum.h) for k = 0 .. N-1, then `clip_and_step()`.  The step's
     logged loss is the micro losses added in order in fp32, times fp32(1/N), on the device.  `num_steps`, the warm-up and the
-    early stopper's `check_every` count optimizer steps."""
+    early stopper's `check_every` count optimizer steps.
+
+    Optimizers that keep a weight average (`opt.weight_ema is not None`, include/lcv_hip_ema.h) have it swapped into the
+    parameters around every due check of the stopper - so the average is what is scored and what `keeper.capture` snapshots,
+    while training goes on from the raw masters, untouched bit for bit - and, without a stopper, once at the end, so that
+    generation reads the average."""
     if grad_accum < 1:
         raise ValueError(f"grad_accum must be at least 1, got {grad_accum}")
+    averaged = [opt for opt in optimizers if getattr(opt, "weight_ema", None) is not None]
     device = params[0].device
     log = _LossLog(num_steps, device)
     keeper = None
@@ -121,8 +127,12 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
         if due:                       # the check's own time, not the wait for the training kernels queued before it
             torch.cuda.synchronize(device)
             tick = time.perf_counter()
+            for opt in averaged:      # score the average ...
+                opt.ema_swap()
         stop, info = early_stopper.step(done, save_fn=keeper.capture)
         if due:
+            for opt in averaged:      # ... and train on from the masters, stop or not: swapping in and out is exact
+                opt.ema_swap()
             torch.cuda.synchronize(device)
             es_seconds += time.perf_counter() - tick
         if stop:
@@ -135,6 +145,9 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
         for opt in optimizers:
             if hasattr(opt, "resync"):
                 opt.resync()
+    else:
+        for opt in averaged:          # nothing was scored: the average of all steps is what generates
+            opt.ema_swap()
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - started
     if finish_eval:
@@ -235,11 +248,14 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
                                   device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                                   early_stopper: Optional[AnchoredEarlyStopper] = None, lora_param_fn=None,
                                   train_latents_variants: Optional[List[Dict]] = None,
-                                  *, grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
+                                  *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
+                                  grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     params = _adapter_params(lora_modules, lora_param_fn)
     # made per call, so per video: the low words of `master_weights` start at zero next to freshly reset adapters
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
                          master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum)
+    if weight_ema is not None:       # the fp32 average of the adapters (+4 B / parameter): scored by the stopper, left in the
+        opt.enable_weight_ema(weight_ema, ema_warmup)    # adapters at the end (see run_adaptation)
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
     return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
                           num_steps, lr, warmup_steps, early_stopper, grad_sync=_sp_sync(dit, opt), grad_accum=grad_accum)
@@ -248,12 +264,16 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
 def finetune_lora_batch(dit: nn.Module, lora_modules, batch_data: List[Dict], num_steps: int = 20, lr: float = 2e-4,
                         warmup_steps: int = 3, weight_decay: float = 0.01, max_grad_norm: float = 1.0,
                         device: str = "cuda", dtype: torch.dtype = torch.bfloat16, lora_param_fn=None,
-                        *, grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
+                        *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
+                        grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Shared adapters trained round-robin over the eval video and its neighbours; no early stopping (:558-634).  The feed
-    receives the micro-step index, so `grad_accum` = number of videos puts every video behind each update."""
+    receives the micro-step index, so `grad_accum` = number of videos puts every video behind each update.  `weight_ema`: the
+    adapters end as their fp32 average over the steps."""
     params = _adapter_params(lora_modules, lora_param_fn)
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
                          master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum)
+    if weight_ema is not None:
+        opt.enable_weight_ema(weight_ema, ema_warmup)
     feed = _RoundRobin(batch_data, device)
     return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
                           num_steps, lr, warmup_steps, None, grad_sync=_sp_sync(dit, opt), grad_accum=grad_accum)
