@@ -22,6 +22,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from longcat_video.parallel import data_parallel as dp  # noqa: E402
+from tta import cli_args as C  # noqa: E402
 from tta import runner_common as R  # noqa: E402
 
 
@@ -40,6 +41,7 @@ def build_parser():
     p.add_argument("--max-videos", type=int, default=100)
     p.add_argument("--save-videos", action="store_true")
     p.add_argument("--device", type=str, default="cuda")
+    C.add_step_cache_args(p)
     return p
 
 
@@ -52,7 +54,7 @@ def _stats(vals):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = C.parse_with_step_cache(build_parser(), argv)
     wall_start = time.time()
     rank, world, device = R.setup_distributed(args)
     torch.manual_seed(args.seed)
@@ -72,7 +74,8 @@ def main(argv=None):
             blob = R.load_entry(e, args, dit, device, total_frames=args.num_cond_frames, pipe=pipe)
             out, dt = R.generate_continuation(pipe, blob, args, idx, device, num_frames=num_frames, entry=e)
             row = {"idx": idx, "index": idx, "filename": e["name"], "caption": blob.get("caption", ""), "psnr": None,
-                   "ssim": None, "lpips": None, "resolution": args.resolution, "inference_time_s": round(dt, 2)}
+                   "ssim": None, "lpips": None, "resolution": args.resolution, "inference_time_s": round(dt, 2),
+                   **C.step_cache_result(blob)}
             if pipe.vae is not None:
                 t1 = time.time()
                 frames = pipe.decode_to_frames(out)
@@ -119,6 +122,11 @@ def main(argv=None):
                                                  "max": round(max(times), 2) if times else None}},
             "metrics": {k: _stats([r[k] for r in merged if r.get(k) is not None]) for k in ("psnr", "ssim", "lpips")},
             "runtime": {"backend": "mi355x-hip", "world_size": world},
+            # --step-cache (this runner writes no config.json and its rows go to a CSV): the flags and every video's statistics
+            # are recorded here, when the flag is set
+            **({"generation": C.step_cache_record(args),
+                "step_cache_per_video": {r["filename"]: r["step_cache"] for r in merged if "step_cache" in r}}
+               if C.step_cache_record(args) else {}),
         }
         with open(out_dir / "summary.json", "w") as f:
             json.dump(summary, f, indent=2)

@@ -29,7 +29,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = R.C.parse_with_step_cache(build_parser(), argv)
     R.run_delta_method(
         args, "delta_a",
         make_wrapper=lambda dit: DeltaAWrapper(dit, adaln_tembed_dim=dit.config.adaln_tembed_dim),

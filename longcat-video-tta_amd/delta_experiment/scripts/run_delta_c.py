@@ -25,7 +25,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = R.C.parse_with_step_cache(build_parser(), argv)
     R.run_delta_method(
         args, "delta_c",
         make_wrapper=lambda dit: DeltaCWrapper(dit, mode=args.delta_mode, out_channels=dit.config.out_channels),

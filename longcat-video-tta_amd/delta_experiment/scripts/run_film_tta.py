@@ -27,7 +27,7 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = R.C.parse_with_step_cache(build_parser(), argv)
     R.run_delta_method(
         args, "film_adapter",
         make_wrapper=lambda dit: FiLMAdapterWrapper(dit, num_groups=args.num_groups, hidden_size=dit.config.hidden_size,

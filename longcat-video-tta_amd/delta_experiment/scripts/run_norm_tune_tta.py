@@ -36,7 +36,7 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    return C.parse_with_weight_ema(build_parser(), argv, C.parse_with_decay_to_base)
+    return C.parse_with_step_cache(build_parser(), argv, lambda p, a: C.parse_with_weight_ema(p, a, C.parse_with_decay_to_base))
 
 
 def main(argv=None):

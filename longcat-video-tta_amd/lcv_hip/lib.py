@@ -138,6 +138,14 @@ _SIGNATURES_EMA = {
     "lcv_master_ema_swap": [P, P, P, I64, I64, P],
 }
 
+# include/lcv_hip_stepcache.h (a header of its own: the first-block step cache of the denoise loop); diff takes (x0, x1, prev, r_out,
+# rows, n, float thr, partials, partials_bytes, out), store (xL, x1, R, total), apply (x1, R, out, total); all return int
+_SIGNATURES_STEPCACHE = {
+    "lcv_stepcache_diff": [P, P, P, P, I64, I64, F32, P, I64, P, P],
+    "lcv_stepcache_store": [P, P, P, I64, P],
+    "lcv_stepcache_apply": [P, P, P, I64, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -195,7 +203,8 @@ def load():
     lib.lcv_tn_skinny_dropout_ws_bytes.argtypes = [I64, I64, I64]
     for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
                        + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())
-                       + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())):
+                       + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())
+                       + list(_SIGNATURES_STEPCACHE.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

@@ -372,6 +372,60 @@ def euler_step(v: torch.Tensor, x: torch.Tensor, dt: float, negate: bool = True)
     call("lcv_euler_step", _ptr(v.contiguous()), _ptr(x), x.numel(), float(dt), 1 if negate else 0, _stream())
 
 
+# the first-block step cache of the denoise loop (include/lcv_hip_stepcache.h; the policy lives in longcat_video/step_cache.py)
+_STEPCACHE_CHUNK = 2048
+_STEPCACHE_WS = {}   # (device index, rows, n) -> the partial-sum workspace of lcv_stepcache_diff (kept alive here)
+
+
+def _stepcache_req(name: str, *tensors) -> None:
+    shape = tensors[0].shape
+    for t in tensors:
+        _req(t, BF16, name)
+        if not t.is_contiguous() or t.shape != shape:
+            raise _lib.LcvError(f"{name}: needs contiguous bf16 tensors of one shape, got {tuple(t.shape)} against {tuple(shape)}")
+
+
+def stepcache_workspace(rows: int, n: int, device) -> torch.Tensor:
+    """One (num, den) fp32 pair per 2048-element chunk of a row, cached per (rows, n)."""
+    key = (torch.device(device).index, int(rows), int(n))
+    ws = _STEPCACHE_WS.get(key)
+    if ws is None:
+        chunks = rows * ((n + _STEPCACHE_CHUNK - 1) // _STEPCACHE_CHUNK)
+        ws = _STEPCACHE_WS[key] = torch.empty((2 * chunks,), dtype=F32, device=device)
+    return ws
+
+
+def stepcache_diff(x0: torch.Tensor, x1: torch.Tensor, prev: Optional[torch.Tensor], r_out: torch.Tensor, thr: float,
+                   out: torch.Tensor) -> None:
+    """r_out = bf16(x1 - x0) over [rows, ...] bf16 tensors; with `prev` also out[0:rows] = per-row sum |r - prev|,
+    out[rows:2 rows] = per-row sum |prev| (fixed order) and the 32-bit integer out[2 rows] = all(num < thr * den); without it
+    out[2 rows] = 0.  `out` is an fp32 device tensor of 2 rows + 1 words.  Nothing is synchronised."""
+    _stepcache_req("stepcache_diff", x0, x1, r_out, *(() if prev is None else (prev,)))
+    _req(out, F32, "stepcache_diff.out")
+    rows = x0.shape[0]
+    n = x0.numel() // max(rows, 1)
+    if out.numel() != 2 * rows + 1 or not out.is_contiguous():
+        raise _lib.LcvError(f"stepcache_diff: out needs {2 * rows + 1} contiguous fp32 words, got {out.numel()}")
+    ws = None if prev is None else stepcache_workspace(rows, n, x0.device)
+    call("lcv_stepcache_diff", _ptr(x0), _ptr(x1), _ptr(prev), _ptr(r_out), rows, n, float(thr), _ptr(ws),
+         0 if ws is None else ws.numel() * 4, _ptr(out), _stream())
+
+
+def stepcache_store(xL: torch.Tensor, x1: torch.Tensor, R: torch.Tensor) -> None:
+    """R = bf16(xL - x1): what the blocks after the first added."""
+    _stepcache_req("stepcache_store", xL, x1, R)
+    call("lcv_stepcache_store", _ptr(xL), _ptr(x1), _ptr(R), xL.numel(), _stream())
+
+
+def stepcache_apply(x1: torch.Tensor, R: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = bf16(x1 + R), a skipped step's stand-in for the last block's output; `out` may be x1 (default: a new tensor)."""
+    if out is None:
+        out = torch.empty_like(x1)
+    _stepcache_req("stepcache_apply", x1, R, out)
+    call("lcv_stepcache_apply", _ptr(x1), _ptr(R), _ptr(out), x1.numel(), _stream())
+    return out
+
+
 def fm_noise(x0: torch.Tensor, eps: torch.Tensor, sigma: torch.Tensor) -> torch.Tensor:
     _req(x0, BF16, "fm_noise.x0"); _req(eps, BF16, "fm_noise.eps"); _req(sigma, F32, "fm_noise.sigma")
     B = x0.shape[0]

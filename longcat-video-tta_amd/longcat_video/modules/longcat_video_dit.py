@@ -219,9 +219,34 @@ class LongCatVideoTransformer3DModel(nn.Module):
             full = sp.gather_frames(local)
         return full.reshape(B, full.shape[1], T, H, W)
 
+    # ------------------------------------------------------------------ first-block step cache
+    def _blocks_with_step_cache(self, cache, x0, y, t, y_seqlens, grid, num_cond_latents, kv_cache_dict):
+        """The block stack of a no-grad forward with a `StepCache`: block 0 always runs; the cache then compares its residual
+        with that of the last computed step and either the remaining blocks run and their residual is stored, or the stored
+        one is added.  Module hooks of skipped blocks do not fire: their effect is inside the cached residual."""
+        def run(i, x):
+            if kv_cache_dict is not None:
+                return self.blocks[i](x, y, t, y_seqlens, grid, kv_cache=kv_cache_dict[i], num_cond_latents=num_cond_latents)
+            return self.blocks[i](x, y, t, y_seqlens, grid, num_cond_latents=num_cond_latents)
+        x1 = run(0, x0)
+        if cache.should_skip(x0, x1):
+            return cache.apply(x1)
+        x = x1
+        for i in range(1, len(self.blocks)):
+            x = run(i, x)
+        cache.store(x, x1)
+        return x
+
     # ------------------------------------------------------------------ forward
     def forward(self, hidden_states, timestep, encoder_hidden_states, encoder_attention_mask=None,
-                num_cond_latents=0, return_kv=False, kv_cache_dict=None, skip_crs_attn=False, **kwargs):
+                num_cond_latents=0, return_kv=False, kv_cache_dict=None, skip_crs_attn=False, step_cache=None, **kwargs):
+        if step_cache is not None:      # the first-block step cache (longcat_video/step_cache.py): inference on one GPU only
+            if torch.is_grad_enabled():
+                raise RuntimeError("step_cache is for inference: call the forward under torch.no_grad()")
+            if return_kv:
+                raise RuntimeError("step_cache cannot be combined with return_kv=True (the conditioning-frame pass is never cached)")
+            if getattr(self, "_sp_group", None) is not None:
+                raise RuntimeError("step_cache has no sequence-parallel form (the sums would need a collective)")
         if getattr(self, "_sp_group", None) is not None and not return_kv:  # (the cond-frame cache itself is computed replicated)
             return self._forward_sp(hidden_states, timestep, encoder_hidden_states, encoder_attention_mask,
                                     num_cond_latents, kv_cache_dict)
@@ -242,6 +267,11 @@ class LongCatVideoTransformer3DModel(nn.Module):
             encoder_attention_mask = None        # every (zeroed) token stays in the sequence: the all-ones mask of the reference
         y, y_seqlens = self.pack_text(y, encoder_attention_mask, x.shape[-1])
 
+        if step_cache is not None:
+            x = self._blocks_with_step_cache(step_cache, x, y, t, y_seqlens, (N_t, N_h, N_w), num_cond_latents, kv_cache_dict)
+            x = self.final_layer(x, t, (N_t, N_h, N_w))
+            x = self.unpatchify(x, N_t, N_h, N_w)
+            return x.to(torch.float32)
         kv_out = {} if return_kv else None
         for i, block in enumerate(self.blocks):
             kw = dict(num_cond_latents=num_cond_latents)

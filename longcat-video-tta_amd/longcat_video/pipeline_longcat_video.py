@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from lcv_hip import ops
+from .step_cache import StepCache
 
 RESOLUTIONS = {"480p": (480, 832), "720p": (720, 1280)}
 
@@ -54,6 +55,7 @@ class LongCatVideoPipeline:
         self.negate_pred = True
         self.use_zero_star = True
         self._kv_cache = None
+        self.last_step_cache_stats = None      # StepCache.stats() of the last denoise() that had one
 
     def to(self, device):
         self.device = torch.device(device)
@@ -97,9 +99,19 @@ class LongCatVideoPipeline:
     def denoise(self, latents: torch.Tensor, prompt_embeds: torch.Tensor, prompt_mask: Optional[torch.Tensor],
                 negative_embeds: Optional[torch.Tensor] = None, negative_mask: Optional[torch.Tensor] = None,
                 num_cond_latents: int = 0, num_inference_steps: int = 50, guidance_scale: float = 4.0,
-                use_kv_cache: bool = True, step_callback=None, start_step: int = 0, stop_step: Optional[int] = None):
+                use_kv_cache: bool = True, step_callback=None, start_step: int = 0, stop_step: Optional[int] = None,
+                step_cache=None):
         """latents fp32 [1, C, T, h, w]; the first `num_cond_latents` frames are clean conditioning frames.
-        Returns the fully denoised latents (fp32, conditioning frames untouched)."""
+        Returns the fully denoised latents (fp32, conditioning frames untouched).
+        `step_cache`: a threshold or a `StepCache` (longcat_video/step_cache.py): steps whose first-block residual is within
+        the threshold of the last computed step's reuse that step's residual of the remaining blocks; the first and the last
+        step are always computed, and the statistics are left in `self.last_step_cache_stats`.
+        No hipGraph is captured while a cache is attached: a captured forward cannot branch."""
+        cache = None
+        if step_cache is not None:
+            cache = step_cache if isinstance(step_cache, StepCache) else StepCache(float(step_cache))
+            cache.begin()
+        self.last_step_cache_stats = None
         dit, sched = self.dit, self.scheduler
         dev = latents.device
         do_cfg = guidance_scale > 1.0 and negative_embeds is not None
@@ -131,14 +143,16 @@ class LongCatVideoPipeline:
         graph = None
         n_tok = Bm * T_in * (work.shape[3] // 2) * (work.shape[4] // 2)
         want_graph = (os.environ.get("LCV_DENOISE_GRAPH") == "1" or n_tok <= int(os.environ.get("LCV_DENOISE_GRAPH_TOKENS", "0"))) \
-            and not torch.is_grad_enabled() and getattr(dit, "_sp_group", None) is None and stop - start_step >= 3
+            and not torch.is_grad_enabled() and getattr(dit, "_sp_group", None) is None and stop - start_step >= 3 and cache is None
+
+        extra = {} if cache is None else {"step_cache": cache}
 
         def forward(x_in, ts):
             if kv is not None:
                 return dit(hidden_states=x_in, timestep=ts, encoder_hidden_states=emb, encoder_attention_mask=mask,
-                           num_cond_latents=ncl, kv_cache_dict=kv)
+                           num_cond_latents=ncl, kv_cache_dict=kv, **extra)
             return dit(hidden_states=x_in, timestep=ts, encoder_hidden_states=emb, encoder_attention_mask=mask,
-                       num_cond_latents=ncl)
+                       num_cond_latents=ncl, **extra)
         x_static = ts_static = pred_static = None
         for i in range(start_step, stop):
             t = timesteps[i]
@@ -156,6 +170,8 @@ class LongCatVideoPipeline:
                 ts = torch.full((Bm, T_in), t, device=dev, dtype=torch.bfloat16)
                 if kv is None and ncl > 0:
                     ts[:, :ncl] = 0
+                if cache is not None:
+                    cache.set_step(i, forced=i == start_step or i == stop - 1)
                 pred = forward(x_in, ts)
                 if want_graph and i == start_step:      # the eager step above was the warm-up: capture for the remaining steps
                     x_static = x_in.contiguous().clone()
@@ -177,6 +193,8 @@ class LongCatVideoPipeline:
             if step_callback is not None:
                 step_callback(i, work)
         sched._step_index = stop
+        if cache is not None:
+            self.last_step_cache_stats = cache.stats()
         if cond is not None:
             work = torch.cat([cond, work], dim=2)
         return work
@@ -215,7 +233,8 @@ class LongCatVideoPipeline:
                     resolution: str = "480p", num_frames: int = 93, num_cond_frames: int = 13,
                     num_inference_steps: int = 50, guidance_scale: float = 4.0, generator=None,
                     use_kv_cache: bool = True, offload_kv_cache: bool = False, prompt_embeds=None,
-                    prompt_mask=None, negative_embeds=None, negative_mask=None, output_type: str = "np", **kw):
+                    prompt_mask=None, negative_embeds=None, negative_mask=None, output_type: str = "np",
+                    step_cache=None, **kw):
         """Video continuation: `video` is a list of PIL frames (or a [T,H,W,3] uint8/float array); the last
         `num_cond_frames` are VAE-encoded as clean conditioning latents."""
         H, W = RESOLUTIONS[resolution]
@@ -233,7 +252,8 @@ class LongCatVideoPipeline:
         noise = torch.randn((1, cond.shape[1], T_lat, h, w), generator=generator, device=self.device, dtype=torch.float32)
         noise[:, :, :ncl] = cond
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=ncl, num_inference_steps=num_inference_steps,
-                           guidance_scale=guidance_scale, use_kv_cache=use_kv_cache)
+                           guidance_scale=guidance_scale, use_kv_cache=use_kv_cache,
+                           **({} if step_cache is None else {"step_cache": step_cache}))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]
@@ -242,7 +262,8 @@ class LongCatVideoPipeline:
     def generate_t2v(self, prompt: Optional[str] = None, negative_prompt: Optional[str] = None, height: int = 480,
                      width: int = 832, num_frames: int = 93, num_inference_steps: int = 50,
                      guidance_scale: float = 4.0, generator=None, prompt_embeds=None, prompt_mask=None,
-                     negative_embeds=None, negative_mask=None, output_type: str = "np", **kw):
+                     negative_embeds=None, negative_mask=None, output_type: str = "np", step_cache=None,
+                     **kw):
         do_cfg = guidance_scale > 1.0
         pe, pm, ne, nm = self._prep_text(prompt, negative_prompt, prompt_embeds, prompt_mask, negative_embeds,
                                          negative_mask, do_cfg)
@@ -251,7 +272,7 @@ class LongCatVideoPipeline:
         C = self.dit.config.in_channels
         noise = torch.randn((1, C, T_lat, h, w), generator=generator, device=self.device, dtype=torch.float32)
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=0, num_inference_steps=num_inference_steps,
-                           guidance_scale=guidance_scale)
+                           guidance_scale=guidance_scale, **({} if step_cache is None else {"step_cache": step_cache}))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]

@@ -53,7 +53,7 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    return C.parse_with_weight_ema(build_parser(), argv, C.parse_with_decay_to_base)
+    return C.parse_with_step_cache(build_parser(), argv, lambda p, a: C.parse_with_weight_ema(p, a, C.parse_with_decay_to_base))
 
 
 def main(argv=None):
@@ -94,7 +94,7 @@ def main(argv=None):
                          "total_params": total_params, "trainable_params": trainable_params},
             "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                            "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
-                           "resolution": args.resolution},
+                           "resolution": args.resolution, **C.step_cache_record(args)},
             "seed": args.seed, "max_videos": args.max_videos,
             **{k: v for k, v in gate.items() if k != "clip_gate_stats"},
             "clip_gate": {"enabled": args.clip_gate_enabled, "threshold": args.clip_gate_threshold,
@@ -152,6 +152,7 @@ def main(argv=None):
                     if not args.no_save_videos:
                         result["output_path"] = R.save_frames(pipe, out, os.path.join(videos_dir, f"{e['name']}_full"), frames=frames)
                 result["gen_time"] = gen_time
+                result.update(C.step_cache_result(blob))
             result["total_time"] = tr["train_time"] + gen_time
             print(f"  [{idx}] {e['name']}: train {tr['train_time']:.1f}s loss {result['final_loss']}"
                   + (f" gen {gen_time:.1f}s" if not args.skip_generation else ""))

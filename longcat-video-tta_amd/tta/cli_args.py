@@ -170,6 +170,69 @@ def weight_ema_record(args) -> dict:
     return {} if args.weight_ema is None else {"weight_ema": args.weight_ema, "weight_ema_warmup": args.weight_ema_warmup}
 
 
+def _step_cache_threshold(text: str) -> float:
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not a number: {text!r}")
+    if not v >= 0.0:                             # a NaN fails too
+        raise argparse.ArgumentTypeError(f"THRESH must be >= 0 and not NaN, got {text}")
+    return v
+
+
+def _step_cache_max_skip(text: str) -> int:
+    try:
+        v = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"K must be >= 1, got {text}")
+    return v
+
+
+def add_step_cache_args(parser):
+    parser.add_argument("--step-cache", type=_step_cache_threshold, default=None, metavar="THRESH",
+                        help="first-block step cache of the denoise loop (include/lcv_hip_stepcache.h): a step whose block-0 "
+                             "residual is within THRESH (relative L1) of the last computed step's adds that step's cached "
+                             "residual of the remaining blocks instead of running them; the first and the last step are always "
+                             "computed; 0 computes every step and records the distance trace (calibration); no default is "
+                             "recommended")
+    parser.add_argument("--step-cache-max-skip", type=_step_cache_max_skip, default=None, metavar="K",
+                        help="with --step-cache: compute a step after K skipped steps in a row (default: no cap)")
+
+
+def parse_with_step_cache(parser, argv=None, parse=None):
+    """`parse` (default parser.parse_args), then the refusal of --step-cache-max-skip without --step-cache as the parser's own
+    one-line error (exit status 2); a negative or NaN THRESH and K < 1 are refused by the arguments' types the same way."""
+    args = parse(parser, argv) if parse is not None else parser.parse_args(argv)
+    if args.step_cache_max_skip is not None and args.step_cache is None:
+        parser.error("--step-cache-max-skip needs --step-cache THRESH")
+    return args
+
+
+def step_cache_from_args(args):
+    """A fresh `StepCache` for one continuation, or None when the flag is absent (then nothing is imported or allocated)."""
+    thr = getattr(args, "step_cache", None)
+    if thr is None:
+        return None
+    from longcat_video.step_cache import StepCache
+    return StepCache(thr, max_consecutive=getattr(args, "step_cache_max_skip", None))
+
+
+def step_cache_record(args) -> dict:
+    """What config.json (`generation`) and the flat summary.json of the runners without one record of --step-cache; nothing
+    when the flag is absent."""
+    if getattr(args, "step_cache", None) is None:
+        return {}
+    return {"step_cache": args.step_cache, "step_cache_max_skip": args.step_cache_max_skip}
+
+
+def step_cache_result(blob) -> dict:
+    """The per-video `step_cache` entry (`StepCache.stats()`, left in the blob by generate_continuation); nothing without the
+    flag."""
+    return {"step_cache": blob["_step_cache"]} if "_step_cache" in blob else {}
+
+
 def normalize_tta_frame_args(args):
     """Post-parse normalisation of lora_experiment/scripts/run_lora_tta.py:743-758 (GT-leak clamp included)."""
     if args.tta_total_frames is None:

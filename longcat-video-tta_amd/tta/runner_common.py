@@ -34,6 +34,7 @@ def add_common_args(p):
     p.add_argument("--resolution", type=str, default="480p")
     p.add_argument("--skip-generation", action="store_true")
     p.add_argument("--no-save-videos", action="store_true")
+    C.add_step_cache_args(p)
 
 
 def add_shared_groups(p, clip_gate: bool = True):
@@ -247,7 +248,8 @@ def continuation_cond_latents(pipe, blob, entry, args, device):
 def generate_continuation(pipe, blob, args, idx, device, num_frames=None, entry=None):
     """KV-cached CFG continuation from the clean conditioning latents (`generate_video_continuation`, common.py:566-611).
     The conditioning encode is inside the timed region, as in the reference.  Returns (denoised latents, seconds); the
-    origin of the conditioning latents is left in `blob["_cond_source"]` for the per-video result."""
+    origin of the conditioning latents is left in `blob["_cond_source"]` for the per-video result, and with `--step-cache` the
+    cache's statistics in `blob["_step_cache"]`."""
     torch.cuda.synchronize()
     t0 = time.time()
     n_valid = num_frames_valid(num_frames if num_frames is not None else args.num_frames)
@@ -258,9 +260,12 @@ def generate_continuation(pipe, blob, args, idx, device, num_frames=None, entry=
     g = torch.Generator(device=device).manual_seed(args.seed + idx)
     lat = torch.randn((1, cond.shape[1], T_lat) + tuple(cond.shape[3:]), generator=g, device=device, dtype=torch.float32)
     lat[:, :, :ncl] = cond
+    cache = C.step_cache_from_args(args)               # --step-cache: None when the flag is absent, and the call is the plain one
     out = pipe.denoise(lat, blob["prompt_embeds"], blob["prompt_mask"], blob.get("negative_embeds"), blob.get("negative_mask"),
                        num_cond_latents=ncl, num_inference_steps=args.num_inference_steps,
-                       guidance_scale=args.guidance_scale, use_kv_cache=True)
+                       guidance_scale=args.guidance_scale, use_kv_cache=True, **({} if cache is None else {"step_cache": cache}))
+    if cache is not None:
+        blob["_step_cache"] = pipe.last_step_cache_stats
     torch.cuda.synchronize()
     return out, time.time() - t0
 
@@ -401,6 +406,7 @@ def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Cal
                         result["output_path"] = save_frames(pipe, out, os.path.join(videos_dir, f"{e['name']}_{file_suffix}"),
                                                             frames=frames)
                 result["gen_time"] = gen_time
+                result.update(C.step_cache_result(blob))
             result["total_time"] = train_time + gen_time
             print(f"  [{idx}] {e['name']}: train {train_time:.1f}s loss {result['final_loss']}"
                   + (f" gen {gen_time:.1f}s" if not args.skip_generation else ""))
@@ -436,6 +442,7 @@ def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Cal
                         "avg_total_time": mean("total_time")})
         if hasattr(args, "clip_gate_enabled"):
             summary.update(clip_gate_summary(args))
+        summary.update(C.step_cache_record(args))      # these runners write no config.json: recorded here, when the flag is set
         summary["results"] = merged
         from tta.eval_metrics import aggregate_quality_metrics
         aggregate_quality_metrics(summary)
