@@ -42,6 +42,7 @@ def build_parser():
     p.add_argument("--save-videos", action="store_true")
     p.add_argument("--device", type=str, default="cuda")
     C.add_step_cache_args(p)
+    C.add_solver_arg(p)
     return p
 
 
@@ -127,6 +128,7 @@ def main(argv=None):
             **({"generation": C.step_cache_record(args),
                 "step_cache_per_video": {r["filename"]: r["step_cache"] for r in merged if "step_cache" in r}}
                if C.step_cache_record(args) else {}),
+            **C.solver_record(args),       # --solver: flat, and only when it is not euler
         }
         with open(out_dir / "summary.json", "w") as f:
             json.dump(summary, f, indent=2)

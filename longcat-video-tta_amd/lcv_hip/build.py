@@ -32,7 +32,8 @@ EXTRA = {"attn_fwd.hip": _ATTN_FLAGS, "attn_fwd_pipe.hip": _ATTN_FLAGS, "attn_bw
          # bit-exact against an fp32 restatement: no product may fuse with the sum that takes it (the source says so too)
          "optim_master.hip": ["-ffp-contract=off"], "optim_moments8.hip": ["-ffp-contract=off"],
          "optim_accum.hip": ["-ffp-contract=off"], "optim_anchor.hip": ["-ffp-contract=off"],
-         "optim_ema.hip": ["-ffp-contract=off"], "step_cache.hip": ["-ffp-contract=off"]}
+         "optim_ema.hip": ["-ffp-contract=off"], "step_cache.hip": ["-ffp-contract=off"],
+         "solver_step.hip": ["-ffp-contract=off"]}
 
 
 def _compile(src: Path, hdr_mtime: float) -> Path:

@@ -146,6 +146,12 @@ _SIGNATURES_STEPCACHE = {
     "lcv_stepcache_apply": [P, P, P, I64, P],
 }
 
+# include/lcv_hip_solver.h (a header of its own: the linear multistep update of the denoise loop): (cond, uncond, x, f0, f1, f2, ws,
+# B, n, float guidance, float w0, w1, w2, int terms, negate, use_zero_star); returns int
+_SIGNATURES_SOLVER = {
+    "lcv_cfg_lms_step": [P, P, P, P, P, P, P, I64, I64, F32, F32, F32, F32, I, I, I, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -204,7 +210,7 @@ def load():
     for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
                        + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())
                        + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())
-                       + list(_SIGNATURES_STEPCACHE.items())):
+                       + list(_SIGNATURES_STEPCACHE.items()) + list(_SIGNATURES_SOLVER.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

@@ -372,6 +372,37 @@ def euler_step(v: torch.Tensor, x: torch.Tensor, dt: float, negate: bool = True)
     call("lcv_euler_step", _ptr(v.contiguous()), _ptr(x), x.numel(), float(dt), 1 if negate else 0, _stream())
 
 
+def cfg_lms_step(cond: torch.Tensor, uncond: Optional[torch.Tensor], x: torch.Tensor, f0: torch.Tensor,
+                 f1: Optional[torch.Tensor], f2: Optional[torch.Tensor], guidance: float, weights, negate: bool = True,
+                 zero_star: bool = True) -> None:
+    """The linear multistep step of include/lcv_hip_solver.h: f0 = the guided velocity of (cond, uncond) (`uncond=None`: cond
+    itself), x += weights[0] f0 + weights[1] f1 + weights[2] f2 over as many terms as `weights` has (1 to 3).  x, f0, f1, f2 are
+    contiguous fp32 of one size and updated / written in place; the rule behind the weights lives in longcat_video/solver.py."""
+    terms = len(weights)
+    hist = (f1, f2)[:max(terms - 1, 0)]
+    if terms < 1 or terms > 3 or any(h is None for h in hist):
+        raise _lib.LcvError(f"cfg_lms_step: {terms} weights need {max(terms - 1, 0)} earlier velocities (1 to 3 terms)")
+    _req(cond, F32, "cfg_lms_step.cond"); _req(x, F32, "cfg_lms_step.x"); _req(f0, F32, "cfg_lms_step.f0")
+    if uncond is not None:
+        _req(uncond, F32, "cfg_lms_step.uncond")
+    for name, t in (("x", x), ("f0", f0)) + tuple(zip(("f1", "f2"), hist)):
+        _req(t, F32, "cfg_lms_step." + name)
+        if not t.is_contiguous() or t.numel() != x.numel():
+            raise _lib.LcvError(f"cfg_lms_step.{name}: needs a contiguous tensor of x's size (it is used in place)")
+    if cond.numel() != x.numel() or (uncond is not None and uncond.numel() != x.numel()):
+        raise _lib.LcvError("cfg_lms_step: cond and uncond must have x's size")
+    B = x.shape[0]
+    n = x.numel() // max(B, 1)
+    ws = None
+    if uncond is not None and zero_star:
+        # cfg_euler_step keeps no workspace cache to reuse: like it, take the 2 KiB per sample from the caching allocator
+        ws = torch.empty((B, 256, 2), dtype=F32, device=x.device)
+    w = [float(v) for v in weights] + [0.0] * (3 - terms)
+    call("lcv_cfg_lms_step", _ptr(cond.contiguous()), None if uncond is None else _ptr(uncond.contiguous()), _ptr(x), _ptr(f0),
+         _ptr(hist[0]) if terms >= 2 else None, _ptr(hist[1]) if terms >= 3 else None, _ptr(ws), B, n, float(guidance),
+         w[0], w[1], w[2], terms, 1 if negate else 0, 1 if zero_star else 0, _stream())
+
+
 # the first-block step cache of the denoise loop (include/lcv_hip_stepcache.h; the policy lives in longcat_video/step_cache.py)
 _STEPCACHE_CHUNK = 2048
 _STEPCACHE_WS = {}   # (device index, rows, n) -> the partial-sum workspace of lcv_stepcache_diff (kept alive here)

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from lcv_hip import ops
+from .solver import MultistepSolver
 from .step_cache import StepCache
 
 RESOLUTIONS = {"480p": (480, 832), "720p": (720, 1280)}
@@ -100,13 +101,21 @@ class LongCatVideoPipeline:
                 negative_embeds: Optional[torch.Tensor] = None, negative_mask: Optional[torch.Tensor] = None,
                 num_cond_latents: int = 0, num_inference_steps: int = 50, guidance_scale: float = 4.0,
                 use_kv_cache: bool = True, step_callback=None, start_step: int = 0, stop_step: Optional[int] = None,
-                step_cache=None):
+                step_cache=None, solver=None):
         """latents fp32 [1, C, T, h, w]; the first `num_cond_latents` frames are clean conditioning frames.
         Returns the fully denoised latents (fp32, conditioning frames untouched).
         `step_cache`: a threshold or a `StepCache` (longcat_video/step_cache.py): steps whose first-block residual is within
         the threshold of the last computed step's reuse that step's residual of the remaining blocks; the first and the last
         step are always computed, and the statistics are left in `self.last_step_cache_stats`.
-        No hipGraph is captured while a cache is attached: a captured forward cannot branch."""
+        No hipGraph is captured while a cache is attached: a captured forward cannot branch.
+        `solver`: None or "euler" (the explicit Euler step, the default), "ab2" / "ab2c" or a `MultistepSolver`
+        (longcat_video/solver.py): a second-order multistep rule over the velocities of the one or two previous steps takes the
+        place of the Euler update; no further forward, one latent-sized fp32 buffer per kept velocity.  The history restarts at
+        every call, so a denoise split by `start_step` / `stop_step` is not bit-equal to one call under these rules."""
+        lms = None
+        if solver is not None and solver != "euler":
+            lms = solver if isinstance(solver, MultistepSolver) else MultistepSolver(solver)
+            lms.begin(start_step)
         cache = None
         if step_cache is not None:
             cache = step_cache if isinstance(step_cache, StepCache) else StepCache(float(step_cache))
@@ -185,9 +194,16 @@ class LongCatVideoPipeline:
                 tgt = work[:, :, ncl:]
                 sl = lambda p: p[:, :, ncl:].contiguous()
                 new = tgt.contiguous()
-                self._apply_step(sl(pred[1:2]) if do_cfg else sl(pred), sl(pred[0:1]) if do_cfg else None, new,
-                                 guidance_scale, dt)
+                if lms is not None:                     # the history is shaped like the target slice
+                    lms.step(sl(pred[1:2]) if do_cfg else sl(pred), sl(pred[0:1]) if do_cfg else None, new, i,
+                             sched._sigmas_host, guidance_scale, self.negate_pred, self.use_zero_star)
+                else:
+                    self._apply_step(sl(pred[1:2]) if do_cfg else sl(pred), sl(pred[0:1]) if do_cfg else None, new,
+                                     guidance_scale, dt)
                 tgt.copy_(new)
+            elif lms is not None:
+                lms.step(pred[1:2] if do_cfg else pred, pred[0:1] if do_cfg else None, work, i, sched._sigmas_host,
+                         guidance_scale, self.negate_pred, self.use_zero_star)
             else:
                 self._apply_step(pred[1:2] if do_cfg else pred, pred[0:1] if do_cfg else None, work, guidance_scale, dt)
             if step_callback is not None:
@@ -234,7 +250,7 @@ class LongCatVideoPipeline:
                     num_inference_steps: int = 50, guidance_scale: float = 4.0, generator=None,
                     use_kv_cache: bool = True, offload_kv_cache: bool = False, prompt_embeds=None,
                     prompt_mask=None, negative_embeds=None, negative_mask=None, output_type: str = "np",
-                    step_cache=None, **kw):
+                    step_cache=None, solver=None, **kw):
         """Video continuation: `video` is a list of PIL frames (or a [T,H,W,3] uint8/float array); the last
         `num_cond_frames` are VAE-encoded as clean conditioning latents."""
         H, W = RESOLUTIONS[resolution]
@@ -253,7 +269,8 @@ class LongCatVideoPipeline:
         noise[:, :, :ncl] = cond
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=ncl, num_inference_steps=num_inference_steps,
                            guidance_scale=guidance_scale, use_kv_cache=use_kv_cache,
-                           **({} if step_cache is None else {"step_cache": step_cache}))
+                           **({} if step_cache is None else {"step_cache": step_cache}),
+                           **({} if solver is None else {"solver": solver}))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]
@@ -263,7 +280,7 @@ class LongCatVideoPipeline:
                      width: int = 832, num_frames: int = 93, num_inference_steps: int = 50,
                      guidance_scale: float = 4.0, generator=None, prompt_embeds=None, prompt_mask=None,
                      negative_embeds=None, negative_mask=None, output_type: str = "np", step_cache=None,
-                     **kw):
+                     solver=None, **kw):
         do_cfg = guidance_scale > 1.0
         pe, pm, ne, nm = self._prep_text(prompt, negative_prompt, prompt_embeds, prompt_mask, negative_embeds,
                                          negative_mask, do_cfg)
@@ -272,7 +289,8 @@ class LongCatVideoPipeline:
         C = self.dit.config.in_channels
         noise = torch.randn((1, C, T_lat, h, w), generator=generator, device=self.device, dtype=torch.float32)
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=0, num_inference_steps=num_inference_steps,
-                           guidance_scale=guidance_scale, **({} if step_cache is None else {"step_cache": step_cache}))
+                           guidance_scale=guidance_scale, **({} if step_cache is None else {"step_cache": step_cache}),
+                           **({} if solver is None else {"solver": solver}))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]

@@ -71,6 +71,7 @@ def build_parser():
     C.add_grad_accum_arg(p)
     C.add_weight_ema_args(p)
     C.add_step_cache_args(p)
+    C.add_solver_arg(p)
     p.add_argument("--max-videos", type=int, default=100)
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--device", type=str, default="cuda")
@@ -167,7 +168,8 @@ def main(argv=None):
                          **C.weight_ema_record(args)},
             "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                            "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
-                           "resolution": args.resolution, **C.step_cache_record(args)},
+                           "resolution": args.resolution, **C.step_cache_record(args),
+                           **C.solver_record(args)},
             "seed": args.seed, "max_videos": args.max_videos, "clip_gate_enabled": args.clip_gate_enabled,
             "clip_gate_threshold": args.clip_gate_threshold, "clip_gate_backend": args.clip_gate_backend,
             "clip_gate_model": args.clip_gate_model, "clip_gate_sample_frames": args.clip_gate_sample_frames,

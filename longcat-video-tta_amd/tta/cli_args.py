@@ -233,6 +233,28 @@ def step_cache_result(blob) -> dict:
     return {"step_cache": blob["_step_cache"]} if "_step_cache" in blob else {}
 
 
+def add_solver_arg(parser):
+    from longcat_video.solver import SOLVERS       # the one list of rules (pure host code: no GPU, no torch)
+    parser.add_argument("--solver", choices=SOLVERS, default="euler",
+                        help="the rule of the denoise loop's update (include/lcv_hip_solver.h, longcat_video/solver.py): euler is "
+                             "the explicit Euler step (first order); ab2 is the two-step Adams-Bashforth rule and ab2c its "
+                             "predictor-corrector form, both second order over the velocities the loop has already computed "
+                             "(no further forward; one latent-sized fp32 buffer per kept velocity); no step count is recommended")
+
+
+def solver_from_args(args):
+    """The `solver=` keyword of the denoise loop, or None for euler or an absent flag (then the call is the plain one)."""
+    kind = getattr(args, "solver", None)
+    return None if kind in (None, "euler") else kind
+
+
+def solver_record(args) -> dict:
+    """What config.json (`generation`) and the flat summary.json of the runners without one record of --solver; nothing for
+    euler."""
+    kind = solver_from_args(args)
+    return {} if kind is None else {"solver": kind}
+
+
 def normalize_tta_frame_args(args):
     """Post-parse normalisation of lora_experiment/scripts/run_lora_tta.py:743-758 (GT-leak clamp included)."""
     if args.tta_total_frames is None:

@@ -35,6 +35,7 @@ def add_common_args(p):
     p.add_argument("--skip-generation", action="store_true")
     p.add_argument("--no-save-videos", action="store_true")
     C.add_step_cache_args(p)
+    C.add_solver_arg(p)
 
 
 def add_shared_groups(p, clip_gate: bool = True):
@@ -261,9 +262,11 @@ def generate_continuation(pipe, blob, args, idx, device, num_frames=None, entry=
     lat = torch.randn((1, cond.shape[1], T_lat) + tuple(cond.shape[3:]), generator=g, device=device, dtype=torch.float32)
     lat[:, :, :ncl] = cond
     cache = C.step_cache_from_args(args)               # --step-cache: None when the flag is absent, and the call is the plain one
+    solver = C.solver_from_args(args)                  # --solver: None for euler, likewise
     out = pipe.denoise(lat, blob["prompt_embeds"], blob["prompt_mask"], blob.get("negative_embeds"), blob.get("negative_mask"),
                        num_cond_latents=ncl, num_inference_steps=args.num_inference_steps,
-                       guidance_scale=args.guidance_scale, use_kv_cache=True, **({} if cache is None else {"step_cache": cache}))
+                       guidance_scale=args.guidance_scale, use_kv_cache=True, **({} if cache is None else {"step_cache": cache}),
+                       **({} if solver is None else {"solver": solver}))
     if cache is not None:
         blob["_step_cache"] = pipe.last_step_cache_stats
     torch.cuda.synchronize()
@@ -443,6 +446,7 @@ def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Cal
         if hasattr(args, "clip_gate_enabled"):
             summary.update(clip_gate_summary(args))
         summary.update(C.step_cache_record(args))      # these runners write no config.json: recorded here, when the flag is set
+        summary.update(C.solver_record(args))
         summary["results"] = merged
         from tta.eval_metrics import aggregate_quality_metrics
         aggregate_quality_metrics(summary)
