@@ -15,6 +15,7 @@
 //                  barrier   K(t+2), V(t+1) in LDS for every wave
 //                  phase 2   O += V(t)^T P(t)^T       32 MFMA   ||  elements 24-31, row max of S(t+1), 8 LDS-DMA requests of
 //                                                                   K(t+3) / V(t+2), first fragments of K(t+2)
+//                  (the first PD + 1 fragments of V(t) are read in the last gaps of phase 1: V(t) landed a barrier earlier)
 //                  post      rare: rescale O, l and S(t+1) of a block whose running max grew by more than 2^RESCALE_THR
 // MFMAs are issued from asm with the register class pinned (score sets in arch VGPRs, O in AGPRs, Q fragments as AGPR B
 // operands): left alone hipcc puts every MFMA result of a > 256-register kernel into AGPRs (round 3, scratch/tried/attn_bwd_dkv3_r3_one_wave_per_simd.hip.txt).  asm is opaque
@@ -35,8 +36,10 @@ struct AttnFwdW64Params : AttnFwdLead {
 // with the pair on the read-free (even) gaps, phase 2's exps over gaps 0..21, its DMA pieces on the read-free even gaps 0..14,
 // the row-max chain in gaps 8..23 and its exchange / ballot in the otherwise empty tail.  tools/mfma_gaps.py prices the
 // compiler's output gap by gap; tests/test_attn_fwd_gap_budget.py holds it there.
-// Order inside a gap is the order of the entries: packs / adds of earlier exps first, the gap's own exps last, so that no VALU
-// reads a v_exp result right behind it (hipcc pads that with an s_nop) and every pack is far ahead of the PV MFMA that reads it.
+// Order inside a gap is the order of the entries: packs / adds of earlier exps first, the gap's own exps last, and every pack
+// far ahead of the PV MFMA that reads it.  Every odd gap OPENS with the fragment read that the MFMA after it used to ask for (its
+// ring slot is free: the MFMA in front of the gap was the last to read it) and closes with the wait of an earlier one.  Those
+// two are what keeps hipcc from padding the adds and packs with s_nops: see w64_apart below.
 template <int I, int N, class F>
 __device__ __forceinline__ void w64_static_for(F&& f) {
   if constexpr (I < N) { f(std::integral_constant<int, I>{}); w64_static_for<I + 1, N>(f); }
@@ -81,7 +84,7 @@ constexpr W64Op W64_P1[32][W64_SLOTS] = {
   {{W64_ADD, 1, 20}, {W64_EXP, 0, 21}, {W64_EXP, 1, 21}},   // 28: 20
   {{W64_PACK, 0, 10}, {W64_ADD, 0, 21}, {W64_PACK, 1, 10}, {W64_ADD, 1, 21}, {W64_EXP, 0, 22}},   // 29: 38
   {{W64_ADD, 0, 22}, {W64_EXP, 1, 22}, {W64_EXP, 0, 23}},   // 30: 20
-  {{W64_PACK, 0, 11}, {W64_ADD, 0, 23}, {W64_ADD, 1, 22}, {W64_EXP, 1, 23}},   // 31: 21
+  {{W64_PACK, 0, 11}, {W64_ADD, 0, 23}, {W64_ADD, 1, 22}, {W64_EXP, 1, 23}},   // 31: 29
 };
 constexpr W64Op W64_P2[32][W64_SLOTS] = {
   {{W64_M0, 0, 0}, {W64_PACK, 1, 11}, {W64_ADD, 1, 23}, {W64_EXP, 0, 24}, {W64_DMA, 0, 0}},   //  0: 25
@@ -106,9 +109,9 @@ constexpr W64Op W64_P2[32][W64_SLOTS] = {
   {{W64_ADD, 1, 30}, {W64_MAX, 1, 5}},   // 19: 24
   {{W64_MAX, 0, 6}, {W64_EXP, 0, 31}},   // 20: 16
   {{W64_PACK, 0, 15}, {W64_ADD, 0, 31}, {W64_MAX, 1, 6}, {W64_EXP, 1, 31}},   // 21: 37
-  {{W64_PACK, 1, 15}, {W64_ADD, 1, 31}, {W64_LRUN, 0, 0}, {W64_MAX, 0, 7}},   // 22: 21
-  {{W64_LRUN, 1, 0}, {W64_MAX, 1, 7}},   // 23: 24
-  {{W64_HMAX, 0, 0}},   // 24: 20
+  {{W64_PACK, 1, 15}, {W64_ADD, 1, 31}, {W64_LRUN, 0, 0}, {W64_MAX, 0, 7}},   // 22: 17
+  {{W64_LRUN, 1, 0}, {W64_MAX, 0, 8}, {W64_MAX, 1, 7}},   // 23: 24
+  {{W64_MAX, 1, 8}, {W64_HMAX, 0, 0}},   // 24: 24
   {{W64_HMAX, 1, 0}},   // 25: 32
   {{W64_BALLOT, 0, 0}},   // 26: 4
   {{W64_BALLOT, 1, 0}},   // 27: 12
@@ -117,13 +120,16 @@ constexpr W64Op W64_P2[32][W64_SLOTS] = {
   {},   // 30: 0
   {},   // 31: 0
 };
-// issue-cycle price of a table entry, and of the fragment reads hipcc places at the end of gap i (a read and its wait)
+// issue-cycle price of a table entry, and of the fragment read at the head of an odd gap i and the wait at its end
 constexpr int w64_op_cost(W64Op o) {
-  return o.kind == W64_EXP ? 8 : o.kind == W64_PACK ? 5 : o.kind == W64_MAX ? 8 : o.kind == W64_HMAX ? 20 :
+  return o.kind == W64_EXP ? 8 : o.kind == W64_PACK ? 5 : o.kind == W64_MAX ? (o.e < 7 ? 8 : 4) : o.kind == W64_HMAX ? 20 :
          o.kind == W64_NONE ? 0 : 4;
 }
+constexpr bool w64_read_first(int phase, int i) { return (i & 1) && (phase == 1 || i <= 29); }   // a fragment read opens the gap
+constexpr bool w64_wait_last(int phase, int i) { return (i & 1) && (phase == 1 || i <= 29); }    // a wait (phase 1, gap 31: the barrier's) closes it
 constexpr int w64_read_cost(int phase, int i) {
-  return !(i & 1) || i > 29 ? 0 : ((phase == 1 && i >= 27) || (phase == 2 && i <= 25)) ? 12 : 8;
+  const bool v = phase == 1 ? i >= 27 : i <= 25;   // a V^T fragment is two ds_read_b64_tr_b16, a K fragment one ds_read_b128
+  return (w64_read_first(phase, i) ? (v ? 8 : 4) : 0) + (w64_wait_last(phase, i) && i <= 29 ? 4 : 0);
 }
 constexpr bool w64_table_ok(const W64Op (&t)[32][W64_SLOTS], int phase, int max_cyc, int max_exp) {
   for (int i = 0; i < 32; ++i) {
@@ -133,8 +139,20 @@ constexpr bool w64_table_ok(const W64Op (&t)[32][W64_SLOTS], int phase, int max_
   }
   return true;
 }
-constexpr bool w64_table_complete() {   // every exp, add, pack exactly once; each after what it reads
-  int exp_at[2][32] = {}, add_at[2][32] = {}, pack_at[2][16] = {}, n = 0;
+// hipcc pads a gap statement that reads the result of another one with an s_nop unless an instruction of ITS OWN stands between
+// the two: asm statements, the MFMA included, count for nothing there, however many they are.  The loop's only such instructions
+// are the fragment reads and their waits, so a result is read no sooner than behind the next of those.  Positions are 8 gap + slot.
+constexpr bool w64_apart(int from, int to) {
+  const int gf = from / 8, gt = to / 8;
+  for (int g = gf; g <= gt; ++g) {
+    const int ph = g < 32 ? 1 : 2, i = g & 31;
+    if ((g > gf && w64_read_first(ph, i)) || (g < gt && w64_wait_last(ph, i))) return true;
+  }
+  return false;
+}
+constexpr bool w64_table_complete() {   // every exp, add, pack exactly once; each after what it reads, and no s_nop in front of it
+  int exp_at[2][32] = {}, add_at[2][32] = {}, pack_at[2][16] = {}, max_at[2][9] = {}, n = 0;
+  for (int b = 0; b < 2; ++b) for (int m = 0; m < 9; ++m) max_at[b][m] = -1;
   for (int b = 0; b < 2; ++b) for (int e = 0; e < 32; ++e) { exp_at[b][e] = -1; add_at[b][e] = -1; }
   for (int b = 0; b < 2; ++b) for (int m = 0; m < 16; ++m) pack_at[b][m] = -1;
   for (int g = 0; g < 64; ++g)
@@ -145,13 +163,20 @@ constexpr bool w64_table_complete() {   // every exp, add, pack exactly once; ea
       if (o.kind == W64_ADD) { if (o.e == 0 || exp_at[o.b][o.e] < 0 || (o.e > 1 && add_at[o.b][o.e - 1] < 0)) return false; add_at[o.b][o.e] = at; }
       if (o.kind == W64_PACK) { if (exp_at[o.b][2 * o.e] < 0 || exp_at[o.b][2 * o.e + 1] < 0) return false; pack_at[o.b][o.e] = at; }
       if (o.kind == W64_LRUN && add_at[o.b][31] < 0) return false;
+      if (o.kind == W64_MAX) { if (o.e > 0 && max_at[o.b][o.e - 1] < 0) return false; max_at[o.b][o.e] = at; }
+      if (o.kind == W64_HMAX && max_at[o.b][8] < 0) return false;
+      if (o.kind == W64_ADD && !(w64_apart(exp_at[o.b][o.e], at) && w64_apart(o.e == 1 ? exp_at[o.b][0] : add_at[o.b][o.e - 1], at))) return false;
+      if (o.kind == W64_PACK && !(w64_apart(exp_at[o.b][2 * o.e], at) && w64_apart(exp_at[o.b][2 * o.e + 1], at))) return false;
+      if (o.kind == W64_LRUN && !w64_apart(add_at[o.b][31], at)) return false;
+      if (o.kind == W64_MAX && o.e > 0 && !w64_apart(max_at[o.b][o.e - 1], at)) return false;
+      if (o.kind == W64_HMAX && !w64_apart(max_at[o.b][8], at)) return false;
     }
   for (int b = 0; b < 2; ++b)
     for (int m = 0; m < 16; ++m)   // pack of k-step m / 4 before PV MFMA 8 (m / 4) + b of phase 2 (MFMA j follows gap j - 1)
       if (pack_at[b][m] < 0 || pack_at[b][m] >= 8 * (32 + 8 * (m / 4) + b - 1) + W64_SLOTS) return false;
   return n == 64;
 }
-static_assert(w64_table_complete(), "attn_fwd_w64 gap table: an exp, add or pack is missing, doubled or out of order");
+static_assert(w64_table_complete(), "attn_fwd_w64 gap table: an exp, add or pack is missing, doubled, out of order or right behind what it reads");
 static_assert(w64_table_ok(W64_P1, 1, 38, 2) && w64_table_ok(W64_P2, 2, 37, 1), "attn_fwd_w64 gap table over its budget");
 
 // GUARD: wait states in front of the MFMA wherever hipcc may have placed a register copy of one of its operands right before the
@@ -427,15 +452,16 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
       if constexpr (o.kind == W64_PACK) pw[b_][e] = gap_pack(ex[b_][2 * e], ex[b_][2 * e + 1]);
       if constexpr (o.kind == W64_LRUN) l_run[b_] = gap_add(l_run[b_], psum[b_]);
       if constexpr (o.kind == W64_VOFF) asm volatile("v_add_u32 %0, %1, %0" : "+v"(v_off[b_ >> 2][b_ & 3]) : "s"(v_delta));
-      if constexpr (o.kind == W64_MAX) {   // two chains of 8 max3 per query block; step 7 folds chain a into b: the full maximum
+      if constexpr (o.kind == W64_MAX) {   // two chains of 8 max3 per query block; steps 7 and 8 fold chain b into a and a into b: the full maximum
         if constexpr (e == 0) {
           mxa[b_] = gap_max3(n[0][b_][0], n[0][b_][1], n[0][b_][2]);
           mxb[b_] = gap_max3(n[1][b_][0], n[1][b_][1], n[1][b_][2]);
         } else if constexpr (e < 7) {
           mxa[b_] = gap_max3(mxa[b_], n[0][b_][2 * e + 1], n[0][b_][2 * e + 2]);
           mxb[b_] = gap_max3(mxb[b_], n[1][b_][2 * e + 1], n[1][b_][2 * e + 2]);
-        } else {
+        } else if constexpr (e == 7) {
           mxa[b_] = gap_max3(mxa[b_], n[0][b_][15], mxb[b_]);
+        } else {
           mxb[b_] = gap_max3(mxa[b_], n[1][b_][15], n[1][b_][14]);
         }
       }
@@ -457,10 +483,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
     w64_static_for<0, 32>([&](auto i_c) __attribute__((always_inline)) {
       constexpr int i = decltype(i_c)::value;
       const int f = i >> 1, nb = i & 1;               // fragment f = (k-step f >> 1, key block f & 1) feeds MFMAs 2 f, 2 f + 1
-      if (nb == 0) {
-        if (f + PD < 16) kfr[(f + PD) % RING] = read_k(kb, f + PD);
-        if (f >= 16 - PD) vfr[f - (16 - PD)] = read_v(f - (16 - PD));   // first fragments of V(t) (landed since the last barrier)
-      }
+      if (i == 0) kfr[PD % RING] = read_k(kb, PD);
       if (f < 2) {
         if (STEADY && i >= 1) mfma_s_first<false>(n[f & 1][nb], minit[nb], kfr[f % RING], qf[nb][0]);
         else mfma_s_first<true>(n[f & 1][nb], minit[nb], kfr[f % RING], qf[nb][0]);
@@ -469,6 +492,13 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
         else mfma_s<true>(n[f & 1][nb], kfr[f % RING], qf[nb][f >> 1]);
       }
       SCHED_FENCE();
+      if (nb == 1) {   // the read of fragment f + 1 + PD, into the ring slot MFMA i was the last to read (see above the table)
+        const int fn = f + 1;
+        if (fn + PD < 16) kfr[(fn + PD) % RING] = read_k(kb, fn + PD);
+        else if (fn < 16) vfr[fn - (16 - PD)] = read_v(fn - (16 - PD));   // first fragments of V(t) (landed since the last barrier)
+        else vfr[PD % RING] = read_v(PD);
+        SCHED_FENCE();
+      }
       w64_static_for<0, W64_SLOTS>([&](auto s_c) { run_op(std::integral_constant<int, 1>{}, i_c, s_c); });
       SCHED_FENCE();
     });
@@ -483,15 +513,17 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
     w64_static_for<0, 32>([&](auto j_c) __attribute__((always_inline)) {
       constexpr int j = decltype(j_c)::value;
       const int g = j >> 1, nb = j & 1;               // fragment g = (k-step g >> 2, dim block g & 3) feeds MFMAs 2 g, 2 g + 1
-      if (nb == 0) {
-        if (g + PD < 16) vfr[(g + PD) % RING] = read_v(g + PD);
-        if (g >= 16 - PD) kfr[g - (16 - PD)] = read_k(kb_next, g - (16 - PD));   // first fragments of K(t+2)
-      }
       const int kk = g >> 2;
       const u32x4 pbw = {pw[nb][4 * kk], pw[nb][4 * kk + 1], pw[nb][4 * kk + 2], pw[nb][4 * kk + 3]};
       if (STEADY && j >= 2) mfma_o<false>(oacc[nb][g & 3], vfr[g % RING], __builtin_bit_cast(bf16x8, pbw));
       else mfma_o<true>(oacc[nb][g & 3], vfr[g % RING], __builtin_bit_cast(bf16x8, pbw));
       SCHED_FENCE();
+      if (nb == 1 && g + 1 < 16) {   // (V fragment PD was read behind the last score MFMA)
+        const int gn = g + 1;
+        if (gn + PD < 16) vfr[(gn + PD) % RING] = read_v(gn + PD);
+        else kfr[gn - (16 - PD)] = read_k(kb_next, gn - (16 - PD));   // first fragments of K(t+2)
+        SCHED_FENCE();
+      }
       w64_static_for<0, W64_SLOTS>([&](auto s_c) { run_op(std::integral_constant<int, 2>{}, j_c, s_c); });
       SCHED_FENCE();
     });
