@@ -1,10 +1,9 @@
 // What the master-weight optimizer kernels share (optim_master.hip, optim_moments8.hip, optim_accum.hip, optim_anchor.hip,
 // optim_ema.hip):
-// the (bf16 word, int16 low word) <-> fp32 master format, AdamW's scalars and its per-element op sequences.  All of them are
-// built with -ffp-contract=off.
+// the (bf16 word, int16 low word) <-> fp32 master format, a thread's eight fp32 values, and the per-element op sequences of SGD
+// and AdamW (their scalars are optim_common.h's).  All of them are built with -ffp-contract=off.
 #pragma once
 #include "optim_common.h"
-#include <math.h>
 
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 
@@ -25,28 +24,33 @@ __device__ __forceinline__ void master_split(float w, bf16_t& h, short& l) {
   l = (short)(unsigned short)(m - (hh << 16));
 }
 
-struct MasterAdamScalars {
-  float c_wd, w1, b2, c2, bc2_sqrt, eps, step_size;
-};
+// a thread's 8 consecutive fp32 values (a moment, a gradient, an average): two 16-byte packets
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[e + 4] = b[e]; }
+}
+__device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
+  f32x4 a, b;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { a[e] = v[e]; b[e] = v[e + 4]; }
+  *reinterpret_cast<f32x4*>(p) = a;
+  *reinterpret_cast<f32x4*>(p + 4) = b;
+}
 
-// scalars formed in double exactly as lcv_adamw_step (torch/optim/adamw.py) forms them, then narrowed to fp32
-static inline MasterAdamScalars master_adam_scalars(double lr, double beta1, double beta2, double eps, double weight_decay,
-                                                    int64_t step) {
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  MasterAdamScalars sc;
-  sc.c_wd = (float)(1.0 - lr * weight_decay);
-  sc.w1 = (float)(1.0 - beta1);
-  sc.b2 = (float)beta2;
-  sc.c2 = (float)(1.0 - beta2);
-  sc.bc2_sqrt = (float)sqrt(bc2);
-  sc.eps = (float)eps;
-  sc.step_size = (float)((lr / bc1) * -1.0);
-  return sc;
+// SGD (momentum 0): g is scaled by the clip coefficient, takes the decay, and moves w
+__device__ __forceinline__ float master_sgd_elem(float w, float g, float coef, float lr, float wd) {
+  g = g * coef;
+  if (wd != 0.f) {
+    const float d = wd * w;
+    g = g + d;
+  }
+  const float u = -lr * g;
+  return w + u;
 }
 
 // AdamW after the decay: both moments, then the parameter.  g is already scaled by the clip coefficient.
-__device__ __forceinline__ void master_adamw_moments_update(float& p, float& m, float& v, float g, const MasterAdamScalars& s) {
+__device__ __forceinline__ void master_adamw_moments_update(float& p, float& m, float& v, float g, const AdamScalars& s) {
   const float dm = s.w1 * (g - m);
   m = m + dm;
   v = v * s.b2;
@@ -58,14 +62,14 @@ __device__ __forceinline__ void master_adamw_moments_update(float& p, float& m, 
 }
 
 // the fp32 op sequence of adamw_kernel<true> (optim.hip), each operation correctly rounded; p, m, v in and out
-__device__ __forceinline__ void master_adamw_elem(float& p, float& m, float& v, float g, float coef, const MasterAdamScalars& s) {
+__device__ __forceinline__ void master_adamw_elem(float& p, float& m, float& v, float g, float coef, const AdamScalars& s) {
   g = g * coef;
   p = p * s.c_wd;
   master_adamw_moments_update(p, m, v, g, s);
 }
 
 // ---- decay toward a base weight w0 instead of toward zero (include/lcv_hip_anchor.h) ----
-// master_sgd_elem (optim_master.hip) with wd * (w - w0) in place of wd * w
+// master_sgd_elem with wd * (w - w0) in place of wd * w
 __device__ __forceinline__ float master_sgd_anchor_elem(float w, float w0, float g, float coef, float lr, float wd) {
   g = g * coef;
   if (wd != 0.f) {
@@ -80,7 +84,7 @@ __device__ __forceinline__ float master_sgd_anchor_elem(float w, float w0, float
 // master_adamw_elem with p = p - a * (p - w0) in place of p = p * c_wd; a = (float)(lr * weight_decay).  Always taken: a = 0
 // subtracts a zero.
 __device__ __forceinline__ void master_adamw_anchor_elem(float& p, float& m, float& v, float w0, float g, float coef, float a,
-                                                         const MasterAdamScalars& s) {
+                                                         const AdamScalars& s) {
   g = g * coef;
   const float d = p - w0;
   const float t = a * d;

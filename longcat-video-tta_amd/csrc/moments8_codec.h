@@ -1,5 +1,5 @@
-// The 8-bit block-scaled moment codec (include/lcv_hip_moments8.h) shared by the kernels that keep AdamW moments in it
-// (optim_moments8.hip, optim_anchor.hip): codes, a thread's 8-code packets, a wave's block maxima and scales.
+// The 8-bit block-scaled moment codec (include/lcv_hip_moments8.h) of the kernels that keep AdamW moments in it
+// (optim_moments8.hip): codes, a thread's 8-code packets, a wave's block maxima and scales.
 #pragma once
 #include "master_elem.h"   // contraction off from there on
 #include "lcv_hip_moments8.h"

@@ -61,10 +61,6 @@ void clip_coef_launch(const float* per_tensor, int n, float max_norm, float* out
   else hipLaunchKernelGGL(clip_coef_kernel<false>, dim3(1), dim3(256), 0, s, per_tensor, n, max_norm, out);
 }
 
-struct AdamScalars {
-  float c_wd, w1, b2, c2, bc2_sqrt, eps, step_size;
-};
-
 template <bool F32>
 __global__ __launch_bounds__(256) void adamw_kernel(const lcv_adam_tensor* __restrict__ tensors, int n,
                                                     const float* __restrict__ clip, const AdamScalars s) {
@@ -127,17 +123,7 @@ extern "C" int lcv_adamw_step(const lcv_adam_tensor* tensors, int64_t n_tensors,
                               const float* norm_coef, double lr, double beta1, double beta2, double eps,
                               double weight_decay, int64_t step, void* stream) {
   LCV_CHECK_ARG(tensors && n_tensors > 0 && total_chunks > 0 && step >= 1, "adamw_step: bad arguments");
-  // scalars formed in double exactly as torch/optim/adamw.py does, then narrowed to the kernels' opmath (fp32)
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  AdamScalars sc;
-  sc.c_wd = (float)(1.0 - lr * weight_decay);
-  sc.w1 = (float)(1.0 - beta1);
-  sc.b2 = (float)beta2;
-  sc.c2 = (float)(1.0 - beta2);
-  sc.bc2_sqrt = (float)sqrt(bc2);
-  sc.eps = (float)eps;
-  sc.step_size = (float)((lr / bc1) * -1.0);
+  const AdamScalars sc = adam_scalars(lr, beta1, beta2, eps, weight_decay, step);
   if (param_f32)
     hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, tensors, (int)n_tensors, norm_coef, sc);
   else

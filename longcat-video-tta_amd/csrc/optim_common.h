@@ -1,7 +1,9 @@
 // What the optimizer kernels (optim.hip) and the fixed-order gradient-norm clip (reduce_det.hip) share: the chunking of the
-// descriptor table, one chunk's sum of squares, and the launcher of the clip coefficient.
+// descriptor table, one chunk's sum of squares, and the launcher of the clip coefficient; and what every optimizer entry point
+// over that table shares on the host (the master-weight files too): AdamW's scalars, the table check, a single array's grid.
 #pragma once
 #include "lcv_common.h"
+#include <math.h>
 
 static constexpr int CHUNK = 2048;  // elements per workgroup (256 threads x 8)
 // per-tensor sum-of-squares accumulators: chunk c of a tensor adds into slot c % NORM_SLOTS of that tensor's row, the
@@ -44,6 +46,40 @@ __device__ __forceinline__ float grad_chunk_sumsq(const lcv_adam_tensor& t, int6
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
   __syncthreads();
   return part[0] + part[1] + part[2] + part[3];
+}
+
+// ---- host: what the entry points over a descriptor table share ----
+// AdamW's scalars, formed in double exactly as torch/optim/adamw.py forms them, then narrowed to the kernels' opmath (fp32)
+struct AdamScalars {
+  float c_wd, w1, b2, c2, bc2_sqrt, eps, step_size;
+};
+
+static inline AdamScalars adam_scalars(double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step) {
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  AdamScalars sc;
+  sc.c_wd = (float)(1.0 - lr * weight_decay);
+  sc.w1 = (float)(1.0 - beta1);
+  sc.b2 = (float)beta2;
+  sc.c2 = (float)(1.0 - beta2);
+  sc.bc2_sqrt = (float)sqrt(bc2);
+  sc.eps = (float)eps;
+  sc.step_size = (float)((lr / bc1) * -1.0);
+  return sc;
+}
+
+// a table's counts fit the kernels' int arguments and the grid
+static inline bool optim_table_ok(int64_t n_tensors, int64_t total_chunks) {
+  return n_tensors > 0 && n_tensors <= 0x7fffffff && total_chunks > 0 && total_chunks <= 0x7fffffff;
+}
+
+// one workgroup per CHUNK of a single array of n elements
+static inline bool chunk_grid(int64_t n, unsigned& blocks) {
+  if (n < 1) return false;
+  const int64_t b = (n + CHUNK - 1) / CHUNK;
+  if (b > 0x7fffffff) return false;
+  blocks = (unsigned)b;
+  return true;
 }
 
 // ---- host: internal launcher shared by the two clip entry points (the caller runs LCV_LAUNCH_CHECK under its own name) ----

@@ -65,13 +65,9 @@ __global__ __launch_bounds__(256) void master_ema_kernel(const lcv_adam_tensor* 
   }
 }
 
-static bool ema_table_ok(const void* tensors, const void* low, const void* ema, int64_t n_tensors, int64_t total_chunks) {
-  return tensors && low && ema && n_tensors > 0 && n_tensors <= 0x7fffffff && total_chunks > 0 && total_chunks <= 0x7fffffff;
-}
-
 extern "C" int lcv_master_ema_load(const lcv_adam_tensor* tensors, void* const* low, void* const* ema, int64_t n_tensors,
                                    int64_t total_chunks, void* stream) {
-  LCV_CHECK_ARG(ema_table_ok(tensors, low, ema, n_tensors, total_chunks), "master_ema_load: bad arguments");
+  LCV_CHECK_ARG(tensors && low && ema && optim_table_ok(n_tensors, total_chunks), "master_ema_load: bad arguments");
   hipLaunchKernelGGL(master_ema_kernel<EMA_LOAD>, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, tensors, low,
                      ema, (int)n_tensors, 0.f);
   LCV_LAUNCH_CHECK("master_ema_load");
@@ -80,7 +76,7 @@ extern "C" int lcv_master_ema_load(const lcv_adam_tensor* tensors, void* const* 
 
 extern "C" int lcv_master_ema_update(const lcv_adam_tensor* tensors, void* const* low, void* const* ema, int64_t n_tensors,
                                      int64_t total_chunks, double beta, void* stream) {
-  LCV_CHECK_ARG(ema_table_ok(tensors, low, ema, n_tensors, total_chunks), "master_ema_update: bad arguments");
+  LCV_CHECK_ARG(tensors && low && ema && optim_table_ok(n_tensors, total_chunks), "master_ema_update: bad arguments");
   LCV_CHECK_ARG(beta >= 0.0 && beta < 1.0, "master_ema_update: beta must be in [0, 1), got %g", beta);   // NaN fails both
   hipLaunchKernelGGL(master_ema_kernel<EMA_UPDATE>, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, tensors,
                      low, ema, (int)n_tensors, (float)beta);
@@ -90,7 +86,7 @@ extern "C" int lcv_master_ema_update(const lcv_adam_tensor* tensors, void* const
 
 extern "C" int lcv_master_ema_swap(const lcv_adam_tensor* tensors, void* const* low, void* const* ema, int64_t n_tensors,
                                    int64_t total_chunks, void* stream) {
-  LCV_CHECK_ARG(ema_table_ok(tensors, low, ema, n_tensors, total_chunks), "master_ema_swap: bad arguments");
+  LCV_CHECK_ARG(tensors && low && ema && optim_table_ok(n_tensors, total_chunks), "master_ema_swap: bad arguments");
   hipLaunchKernelGGL(master_ema_kernel<EMA_SWAP>, dim3((unsigned)total_chunks), dim3(256), 0, (hipStream_t)stream, tensors, low,
                      ema, (int)n_tensors, 0.f);
   LCV_LAUNCH_CHECK("master_ema_swap");

@@ -1132,32 +1132,24 @@ class FusedAdamWClip:
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
-        if self._anchor:                 # decay toward the base words (include/lcv_hip_anchor.h)
-            coef = _ptr(self._norm_coef) if self._have_coef else None
-            hyper = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                     self.step_count)
-            if self.moments_8bit:
-                call("lcv_master_adamw8_step_anchor", _ptr(d), _ptr(self._low_desc), _ptr(self._scale_desc),
-                     _ptr(self._anchor_desc), self._n_active, self._total_chunks, coef, *hyper, _stream())
-            else:
-                call("lcv_master_adamw_step_anchor", _ptr(d), _ptr(self._low_desc), _ptr(self._anchor_desc), self._n_active,
-                     self._total_chunks, coef, *hyper, 1 if self.grad_accum > 1 else 0, _stream())
+        hyper = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                 self.step_count)
+        coef = _ptr(self._norm_coef) if self._have_coef else None
+        # the entry point, the pointer tables that follow the descriptors, param_f32 (after the counts), grad_f32 (before the stream)
+        if self._anchor and self.moments_8bit:   # an anchor: decay toward the base words (include/lcv_hip_anchor.h)
+            name, tables, pf32, gf32 = "lcv_master_adamw8_step_anchor", "low scale anchor", (), ()
+        elif self._anchor:
+            name, tables, pf32, gf32 = "lcv_master_adamw_step_anchor", "low anchor", (), (1 if self.grad_accum > 1 else 0,)
         elif self.moments_8bit:
-            call("lcv_master_adamw8_step", _ptr(d), _ptr(self._low_desc), _ptr(self._scale_desc), self._n_active,
-                 self._total_chunks, _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
-                 float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
+            name, tables, pf32, gf32 = "lcv_master_adamw8_step", "low scale", (), ()
         elif self.grad_accum > 1:
-            call("lcv_master_adamw_step_g32", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
-                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
-                 float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
+            name, tables, pf32, gf32 = "lcv_master_adamw_step_g32", "low", (), ()
         elif self.master_weights:
-            call("lcv_master_adamw_step", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
-                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
-                 float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
+            name, tables, pf32, gf32 = "lcv_master_adamw_step", "low", (), ()
         else:
-            call("lcv_adamw_step", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
-                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["betas"][0]),
-                 float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), self.step_count, _stream())
+            name, tables, pf32, gf32 = "lcv_adamw_step", "", (1 if self.f32 else 0,), ()
+        call(name, _ptr(d), *(_ptr(getattr(self, f"_{t}_desc")) for t in tables.split()), self._n_active, self._total_chunks, *pf32,
+             coef, *hyper, *gf32, _stream())
         self._have_coef = False
         if self.weight_ema is not None:  # the average follows the masters this step left (include/lcv_hip_ema.h)
             self._ema_update()
@@ -1514,19 +1506,19 @@ class FusedSGDClip(FusedAdamWClip):
         d = self._descriptors()
         g = self.param_groups[0]
         self.step_count += 1
+        hyper = (float(g["lr"]), float(g["weight_decay"]))
+        coef = _ptr(self._norm_coef) if self._have_coef else None
+        # as in FusedAdamWClip.step: the entry point, its pointer tables, param_f32, grad_f32
         if self._anchor:                 # decay toward the base words (include/lcv_hip_anchor.h)
-            call("lcv_master_sgd_step_anchor", _ptr(d), _ptr(self._low_desc), _ptr(self._anchor_desc), self._n_active,
-                 self._total_chunks, _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]),
-                 float(g["weight_decay"]), 1 if self.grad_accum > 1 else 0, _stream())
+            name, tables, pf32, gf32 = "lcv_master_sgd_step_anchor", "low anchor", (), (1 if self.grad_accum > 1 else 0,)
         elif self.grad_accum > 1:
-            call("lcv_master_sgd_step_g32", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
-                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
+            name, tables, pf32, gf32 = "lcv_master_sgd_step_g32", "low", (), ()
         elif self.master_weights:
-            call("lcv_master_sgd_step", _ptr(d), _ptr(self._low_desc), self._n_active, self._total_chunks,
-                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
+            name, tables, pf32, gf32 = "lcv_master_sgd_step", "low", (), ()
         else:
-            call("lcv_sgd_step", _ptr(d), self._n_active, self._total_chunks, 1 if self.f32 else 0,
-                 _ptr(self._norm_coef) if self._have_coef else None, float(g["lr"]), float(g["weight_decay"]), _stream())
+            name, tables, pf32, gf32 = "lcv_sgd_step", "", (1 if self.f32 else 0,), ()
+        call(name, _ptr(d), *(_ptr(getattr(self, f"_{t}_desc")) for t in tables.split()), self._n_active, self._total_chunks, *pf32,
+             coef, *hyper, *gf32, _stream())
         self._have_coef = False
         if self.weight_ema is not None:  # the average follows the masters this step left (include/lcv_hip_ema.h)
             self._ema_update()

@@ -168,19 +168,34 @@ def test_every_anchor_entry_point_has_a_kernel_level_test():
 
 def test_the_source_uses_no_atomics_and_shares_format_steps_and_codec():
     csrc = ROOT / "longcat-video-tta_amd" / "csrc"
-    src = (csrc / "optim_anchor.hip").read_text()
-    for word in ("atomic", "fmaf", "asm", "getenv", "lcv_knob(", "hipMalloc"):
-        assert word not in src, word
+    src = (csrc / "optim_anchor.hip").read_text()           # what is left here: the drift kernels and their entry point
+    master = (csrc / "optim_master.hip").read_text()        # the SGD and AdamW anchor steps: forms of the master kernels
+    m8 = (csrc / "optim_moments8.hip").read_text()          # the 8-bit anchor step: a form of the 8-bit kernel
+    for txt in (src, master, m8):
+        for word in ("atomic", "fmaf", "asm", "getenv", "lcv_knob(", "hipMalloc"):
+            assert word not in txt, word
+        assert '#include "lcv_hip_anchor.h"' in txt                  # the compiler checks the signatures
+    for word in ("__shared__", "__syncthreads"):                    # the wave-order join of the drift sum is the only LDS
+        assert word in src and word not in master and word not in m8, word
+    assert re.findall(r'extern "C" int (\w+)\(', src) == ["lcv_master_drift_sumsq"]
+    for entry, txt in (("lcv_master_sgd_step_anchor", master), ("lcv_master_adamw_step_anchor", master),
+                       ("lcv_master_adamw8_step_anchor", m8)):
+        assert len(re.findall(rf'extern "C" int {entry}\(', txt)) == 1, entry
     shared = (csrc / "master_elem.h").read_text()
     codec = (csrc / "moments8_codec.h").read_text()
     # one definition each: the element functions in master_elem.h, the codec in moments8_codec.h
-    for fn in ("void master_adamw_elem(", "void master_adamw_anchor_elem(", "float master_sgd_anchor_elem(", "float master_join(",
-               "void master_split("):
-        assert shared.count(fn) == 1 and fn not in src, fn
+    for fn in ("void master_adamw_elem(", "void master_adamw_anchor_elem(", "float master_sgd_anchor_elem(", "float master_sgd_elem(",
+               "float master_join(", "void master_split("):
+        assert shared.count(fn) == 1 and fn not in src and fn not in master and fn not in m8, fn
     for fn in ("m8_encode_m(float", "m8_encode_r(float", "m8_decode_m(unsigned", "m8_decode_v(unsigned", "void m8_encode_store("):
-        assert codec.count(fn) == 1 and fn not in src and fn not in (csrc / "optim_moments8.hip").read_text(), fn
-    assert "master_adamw_anchor_elem(" in src and "master_sgd_anchor_elem(" in src and "m8_encode_store(" in src
-    assert "find_tensor(" in src and "master_adam_scalars(" in src and "c_wd" not in src
+        assert codec.count(fn) == 1 and fn not in src and fn not in master and fn not in m8, fn
+    assert "master_adamw_anchor_elem(" in master and "master_sgd_anchor_elem(" in master
+    assert "master_adamw_anchor_elem(" in m8 and "m8_encode_store(" in m8
+    for txt in (src, master, m8):
+        assert "find_tensor(" in txt and "c_wd" not in txt
+    assert "adam_scalars(" in master and "adam_scalars(" in m8
+    # the anchor and plain decay stay two expressions: p - a * (p - w0) against p * c_wd
+    assert "p = p * s.c_wd;" in shared and "p = p - t;" in shared
     from lcv_hip import build
     assert build.EXTRA["optim_anchor.hip"] == build.EXTRA["optim_master.hip"] == ["-ffp-contract=off"]
 

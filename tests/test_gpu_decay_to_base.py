@@ -6,7 +6,8 @@
    accumulators of grad_accum=3, 8-bit moments; with and without clip; wd in {0, 0.01, 0.5}.  Tensors: a single element, a
    sub-packet tail, one 512-block, one element past it, an exact chunk, one element past a chunk (parameter, low words,
    gradient, anchor and codes as 2-byte / 1-byte offset views: the scalar path), a tail past two chunks, plus a parameter
-   without a gradient.
+   without a gradient.  And, at the C ABI, one 2059-element tensor with exactly one array at a time as an offset view, against
+   the all-aligned run: SGD, AdamW and 8-bit AdamW, with and without an anchor, bf16 and fp32 gradients.
 2. Pins to the existing kernels: zero base words give lcv_master_sgd_step's bits, wd = 0 gives the AdamW steps' bits.
 3. The base is a fixed point, the pull a contraction.
 4. lcv_master_drift_sumsq: a derived error bound against float64, run-to-run bits, low = NULL, zero at the base; refusals.
@@ -225,6 +226,84 @@ def test_adamw_anchor_step_bits(n, clip, wd):
 @pytest.mark.parametrize("clip", [False, True])
 def test_adamw8_anchor_step_bits(clip, wd):
     _run_steps("adamw8", 1, clip, wd)
+
+
+# ------------------------------------------------------------------------------------- 1b. one misaligned array at a time
+ONE = 2059                    # a full chunk, one more whole packet and a 3-element tail
+_ONE = {}
+
+
+def _one():
+    """Host-generated arrays of one tensor, made once and never written: live low words, moments and codes."""
+    if not _ONE:
+        rng = np.random.default_rng(47)
+        h, low = W.weights(rng, ONE)
+        _ONE["A"], low = A.anchors(rng, h, low)
+        _ONE["P"], _ONE["L"] = h, low
+        _ONE["G"] = W.grads(rng, ONE)
+        _ONE["G32"] = G.accumulate(np.zeros(ONE, dtype=np.float32), _ONE["G"], 1.0 / 3.0)
+        _ONE["M"], _ONE["V"] = M8.moments(rng, ONE)
+        _ONE["CM"], _ONE["CR"], _ONE["S"] = M8.encode(_ONE["M"], _ONE["V"])
+    return _ONE
+
+
+def _one_step(kind, anchored, g32, offset):
+    """One step of the entry point for (kind, anchored, g32) over the one tensor, every array 16-byte aligned but `offset`,
+    which starts one element late.  Returns every array the step writes."""
+    t = _one()
+    dev = {"P": _bf16_dev(t["P"]), "L": _i16_dev(t["L"]), "A": _bf16_dev(t["A"]),
+           "G": torch.from_numpy(t["G32"].copy()).to(DEV) if g32 else _bf16_dev(t["G"])}
+    if kind == "adamw":
+        dev["M"], dev["V"] = (torch.from_numpy(t[k].copy()).to(DEV) for k in ("M", "V"))
+    if kind == "adamw8":
+        dev["M"], dev["V"] = (torch.from_numpy(t[k].copy()).to(DEV) for k in ("CM", "CR"))
+        dev["S"] = torch.from_numpy(t["S"].copy()).to(DEV)
+    assert all(x.data_ptr() % 16 == 0 for x in dev.values())
+    if offset is not None:
+        dev[offset] = _offset_view(dev[offset])
+    ptr = lambda k: torch.tensor([dev[k].data_ptr()], dtype=torch.int64).to(DEV)
+    moments = [dev[k].data_ptr() if k in dev else 0 for k in ("M", "V")]
+    table = torch.tensor([[dev["P"].data_ptr(), dev["G"].data_ptr(), *moments, ONE, 0]], dtype=torch.int64).to(DEV)
+    tables = [ptr("L")] + ([ptr("S")] if kind == "adamw8" else []) + ([ptr("A")] if anchored else [])
+    hyper = (LR[kind], 0.01) if kind == "sgd" else (LR[kind], B1, B2, EPS, 0.01, 2)
+    name = {"sgd": "lcv_master_sgd_step", "adamw": "lcv_master_adamw_step", "adamw8": "lcv_master_adamw8_step"}[kind]
+    if anchored:
+        name, flag = name + "_anchor", () if kind == "adamw8" else (1 if g32 else 0,)
+    else:
+        name, flag = name + ("_g32" if g32 else ""), ()
+    _call(name, table.data_ptr(), *(x.data_ptr() for x in tables), 1, (ONE + CHUNK - 1) // CHUNK, None, *hyper, *flag)
+    torch.cuda.synchronize()
+    out = {"h": _h_of(dev["P"]), "l": dev["L"].cpu().numpy()}
+    if kind == "adamw":
+        out["m"], out["v"] = _bits_of(dev["M"]), _bits_of(dev["V"])
+    if kind == "adamw8":
+        out["cm"], out["cr"], out["s"] = dev["M"].cpu().numpy(), dev["V"].cpu().numpy(), _bits_of(dev["S"])
+    # what the step only reads is what it was
+    assert np.array_equal(_h_of(dev["A"]), t["A"])
+    assert np.array_equal(_bits_of(dev["G"]), W.bits(t["G32"])) if g32 else np.array_equal(_h_of(dev["G"]), t["G"])
+    return out
+
+
+@pytest.mark.parametrize("anchored", [False, True])
+@pytest.mark.parametrize("kind", ["sgd", "adamw", "adamw8"])
+def test_one_misaligned_array_takes_the_scalar_path_to_the_same_bits(kind, anchored):
+    """The packet test ORs the pointers of whichever arrays the form reads (parameter, low words, gradient, with an anchor its
+    base words, both moments or both code arrays): any single one of them off a 16-byte (codes: 8-byte) boundary sends every
+    thread down the scalar path, which leaves the bits of the all-aligned run.  The other tests offset all arrays of a tensor
+    together."""
+    t = _one()
+    arrays = ["P", "L", "G"] + (["A"] if anchored else []) + (["M", "V"] if kind != "sgd" else [])
+    for g32 in ([False] if kind == "adamw8" else [False, True]):
+        want = _one_step(kind, anchored, g32, None)
+        assert (want["h"] != t["P"]).any() or (want["l"] != t["L"]).any()           # the step moved the masters
+        if kind != "sgd":
+            assert any((want[k] != ref).any() for k, ref in (("m", W.bits(t["M"])), ("v", W.bits(t["V"])), ("cm", t["CM"]),
+                                                             ("cr", t["CR"])) if k in want)
+        for offset in arrays:
+            got = _one_step(kind, anchored, g32, offset)
+            assert got.keys() == want.keys()
+            for key in want:
+                _report(f"{kind} anchored={anchored} g32={g32}, {offset} offset: {key}", 0, got[key], want[key])
 
 
 # ---------------------------------------------------------------------------------------------------------- 2. the pins

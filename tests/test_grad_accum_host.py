@@ -133,8 +133,21 @@ def test_the_source_uses_no_atomics_no_lds_and_shares_the_step_with_the_master_k
     src = (csrc / "optim_accum.hip").read_text()
     for word in ("atomic", "fmaf", "asm", "getenv", "lcv_knob(", "hipMalloc", "__shared__", "__syncthreads"):
         assert word not in src, word
-    assert '#include "master_elem.h"' in src and "void master_adamw_elem(" not in src and "master_adamw_elem(" in src
-    assert "master_join(" in src and "master_split(" in src and "find_tensor(" in src
+    # what is left here is the accumulate kernel and its entry point
+    assert '#include "lcv_hip_accum.h"' in src and "find_tensor(" in src and "optim_table_ok(" in src
+    assert re.findall(r'extern "C" int (\w+)\(', src) == ["lcv_grad_accumulate"] and "_step" not in src
+    # the fp32-gradient steps are the master kernels themselves (optim_master.hip): the same word list holds there, the header
+    # is included there so that the compiler checks the signatures, and the op sequences are the shared ones
+    master = (csrc / "optim_master.hip").read_text()
+    for word in ("atomic", "fmaf", "asm", "getenv", "lcv_knob(", "hipMalloc", "__shared__", "__syncthreads"):
+        assert word not in master, word
+    assert '#include "lcv_hip_accum.h"' in master and '#include "master_elem.h"' in master
+    for entry in ("lcv_master_sgd_step_g32", "lcv_master_adamw_step_g32"):
+        assert len(re.findall(rf'extern "C" int {entry}\(', master)) == 1, entry
+    assert "void master_adamw_elem(" not in master and "master_adamw_elem(" in master
+    assert "float master_sgd_elem(" not in master and "master_sgd_elem(" in master
+    assert "master_join(" in master and "master_split(" in master and "find_tensor(" in master
+    assert "accum_sgd_elem" not in "".join(p.read_text() for p in csrc.iterdir() if p.suffix in (".hip", ".h"))
     from lcv_hip import build
     assert build.EXTRA["optim_accum.hip"] == build.EXTRA["optim_master.hip"] == ["-ffp-contract=off"]
 

@@ -188,9 +188,52 @@ def test_every_master_entry_point_has_a_kernel_level_test():
 
 
 def test_the_source_uses_no_atomics_and_reads_no_environment():
-    src = (ROOT / "longcat-video-tta_amd" / "csrc" / "optim_master.hip").read_text()
-    assert "atomicAdd" not in src and "atomic_" not in src and "lcv_knob(" not in src and "getenv(" not in src and "asm" not in src
-    assert "hipMalloc" not in src and "fmaf" not in src
+    csrc = ROOT / "longcat-video-tta_amd" / "csrc"
+    src = (csrc / "optim_master.hip").read_text()
+    # the file holds every SGD and AdamW step form (bf16 / fp32 gradient, with / without an anchor): the lists of the files
+    # those kernels came from hold here
+    for word in ("atomic", "fmaf", "asm", "getenv", "lcv_knob(", "hipMalloc", "__shared__", "__syncthreads"):
+        assert word not in src, word
+    for header in ("lcv_hip_master.h", "lcv_hip_accum.h", "lcv_hip_anchor.h"):       # the compiler checks the signatures
+        assert f'#include "{header}"' in src, header
+    for entry in ("lcv_master_sgd_step", "lcv_master_sgd_step_g32", "lcv_master_sgd_step_anchor", "lcv_master_adamw_step",
+                  "lcv_master_adamw_step_g32", "lcv_master_adamw_step_anchor", "lcv_master_split", "lcv_master_join"):
+        assert len(re.findall(rf'extern "C" int {entry}\(', src)) == 1, entry
+    for use in ("master_sgd_elem(", "master_sgd_anchor_elem(", "master_adamw_elem(", "master_adamw_anchor_elem(", "master_join(",
+                "master_split(", "find_tensor(", "adam_scalars(", "optim_table_ok(", "chunk_grid("):
+        assert use in src, use
+
+
+def test_one_definition_of_each_step_kernel_element_function_and_host_helper():
+    csrc = ROOT / "longcat-video-tta_amd" / "csrc"
+    texts = {p.name: p.read_text() for p in sorted(csrc.glob("*.hip")) + sorted(csrc.glob("*.h"))}
+    everything = "\n".join(texts.values())
+
+    def defined_in(pattern):
+        return [name for name, txt in texts.items() for _ in re.findall(pattern, txt)]
+    # three step kernels, each a template defined once, in the file of its optimizer
+    kernels = re.findall(r"__global__[^;{]*?\bvoid\s+(master_\w+_kernel)\s*\(", everything)
+    assert sorted(kernels) == ["master_adamw8_kernel", "master_adamw_kernel", "master_convert_kernel", "master_ema_kernel",
+                               "master_sgd_kernel"], kernels
+    assert defined_in(r"\bvoid\s+master_sgd_kernel\s*\(") == defined_in(r"\bvoid\s+master_adamw_kernel\s*\(") == ["optim_master.hip"]
+    assert defined_in(r"\bvoid\s+master_adamw8_kernel\s*\(") == ["optim_moments8.hip"]
+    assert "template <bool G32, bool ANCHOR>\n__global__" in texts["optim_master.hip"]
+    assert "template <bool ANCHOR>\n__global__" in texts["optim_moments8.hip"]
+    # the element functions, once each, in the shared header
+    for fn in ("float master_sgd_elem(", "float master_sgd_anchor_elem(", "void master_adamw_elem(", "void master_adamw_anchor_elem(",
+               "void load8(", "void store8("):
+        assert everything.count(fn) == 1 and texts["master_elem.h"].count(fn) == 1, fn
+    assert "accum_sgd_elem" not in everything
+    # the host helpers, once each, in optim_common.h; nothing keeps a copy under another name
+    for fn in ("struct AdamScalars", "AdamScalars adam_scalars(", "bool optim_table_ok(", "bool chunk_grid("):
+        assert everything.count(fn) == 1 and texts["optim_common.h"].count(fn) == 1, fn
+    for gone in ("MasterAdamScalars", "master_adam_scalars", "anchor_table_ok", "ema_table_ok", "master_convert_grid", "moments8_grid",
+                 "anchor_grad", "anchor_widen", "anchor_load_grads"):
+        assert gone not in everything, gone
+    # no optimizer entry point spells the table check out
+    for name in ("optim_master.hip", "optim_moments8.hip", "optim_accum.hip", "optim_anchor.hip", "optim_ema.hip"):
+        assert "0x7fffffff" not in texts[name], name
+        assert "pow(" not in texts[name], name
 
 
 # ------------------------------------------------------------------------------------------------------------ the optimizers

@@ -224,8 +224,13 @@ def test_every_moments8_entry_point_has_a_kernel_level_test():
 def test_the_source_uses_no_atomics_no_lds_and_shares_the_step_with_the_fp32_moment_kernel():
     csrc = ROOT / "longcat-video-tta_amd" / "csrc"
     src = (csrc / "optim_moments8.hip").read_text()
-    assert "atomicAdd" not in src and "atomic_" not in src and "lcv_knob(" not in src and "getenv(" not in src and "asm" not in src
-    assert "hipMalloc" not in src and "fmaf" not in src and "__shared__" not in src and "__syncthreads" not in src
+    # the file holds both 8-bit step forms (with and without an anchor): the lists of both kernels' earlier files hold here
+    for word in ("atomic", "fmaf", "asm", "getenv", "lcv_knob(", "hipMalloc", "__shared__", "__syncthreads"):
+        assert word not in src, word
+    for entry in ("lcv_master_adamw8_step", "lcv_master_adamw8_step_anchor", "lcv_moments8_encode", "lcv_moments8_decode"):
+        assert len(re.findall(rf'extern "C" int {entry}\(', src)) == 1, entry
+    assert len(re.findall(r"\bvoid\s+master_adamw8_kernel\s*\(", src)) == 1 and "master_adamw8_anchor_kernel" not in src
+    assert '#include "lcv_hip_anchor.h"' in src and '#include "lcv_hip_moments8.h"' in (csrc / "moments8_codec.h").read_text()
     # one definition of the op sequence, in the shared header, used by both files
     shared = (csrc / "master_elem.h").read_text()
     assert shared.count("void master_adamw_elem(") == 1

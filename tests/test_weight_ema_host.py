@@ -146,7 +146,7 @@ def test_the_source_uses_no_atomics_and_no_lds_and_shares_the_format():
     shared = (csrc / "master_elem.h").read_text()
     for fn in ("float master_ema_elem(", "float master_join(", "void master_split("):
         assert shared.count(fn) == 1 and fn not in src, fn
-    for use in ("master_ema_elem(", "master_join(", "master_split(", "find_tensor(", "CHUNK", "__launch_bounds__(256)"):
+    for use in ("master_ema_elem(", "master_join(", "master_split(", "find_tensor(", "CHUNK", "__launch_bounds__(256)", "optim_table_ok("):
         assert use in src, use
     from lcv_hip import build
     assert build.EXTRA["optim_ema.hip"] == ["-ffp-contract=off"] == build.EXTRA["optim_master.hip"]

@@ -26,10 +26,11 @@ from pathlib import Path
 
 HERE = Path(__file__).resolve().parents[1]
 # kernel name in the trace -> (entry point, bytes read + written per element as the headers state them)
-KERNELS = [("master_sgd_kernel", "lcv_master_sgd_step", 10), ("master_sgd_anchor_kernel<false>", "lcv_master_sgd_step_anchor", 12),
-           ("master_sgd_g32_kernel", "lcv_master_sgd_step_g32", 12), ("master_sgd_anchor_kernel<true>", "lcv_master_sgd_step_anchor, fp32 gradient", 14),
-           ("master_adamw_kernel", "lcv_master_adamw_step", 26), ("master_adamw_anchor_kernel<false>", "lcv_master_adamw_step_anchor", 28),
-           ("master_adamw8_kernel", "lcv_master_adamw8_step", 14), ("master_adamw8_anchor_kernel", "lcv_master_adamw8_step_anchor", 16),
+# (the step kernels' template arguments: <fp32 gradient, anchor>, the 8-bit one's <anchor>)
+KERNELS = [("master_sgd_kernel<false, false>", "lcv_master_sgd_step", 10), ("master_sgd_kernel<false, true>", "lcv_master_sgd_step_anchor", 12),
+           ("master_sgd_kernel<true, false>", "lcv_master_sgd_step_g32", 12), ("master_sgd_kernel<true, true>", "lcv_master_sgd_step_anchor, fp32 gradient", 14),
+           ("master_adamw_kernel<false, false>", "lcv_master_adamw_step", 26), ("master_adamw_kernel<false, true>", "lcv_master_adamw_step_anchor", 28),
+           ("master_adamw8_kernel<false>", "lcv_master_adamw8_step", 14), ("master_adamw8_kernel<true>", "lcv_master_adamw8_step_anchor", 16),
            ("drift_chunk_kernel", "lcv_master_drift_sumsq: one partial per chunk", 6), ("drift_final_kernel", "lcv_master_drift_sumsq: the partials", 0)]
 
 

@@ -29,7 +29,7 @@ from pathlib import Path
 
 HERE = Path(__file__).resolve().parents[1]
 # kernel name in the trace -> (entry point, bytes read + written per element as the headers state them)
-KERNELS = [("master_sgd_kernel", "lcv_master_sgd_step (the counterpart)", 10), ("master_ema_kernel<0>", "lcv_master_ema_load", 8),
+KERNELS = [("master_sgd_kernel<false, false>", "lcv_master_sgd_step (the counterpart)", 10), ("master_ema_kernel<0>", "lcv_master_ema_load", 8),
            ("master_ema_kernel<1>", "lcv_master_ema_update", 12), ("master_ema_kernel<2>", "lcv_master_ema_swap", 16)]
 FORMS = [("flags absent", {}), ("--master-weights", {"master_weights": True}),
          ("--master-weights --weight-ema 0.9", {"master_weights": True, "weight_ema": 0.9})]
