@@ -1376,72 +1376,3 @@ extern "C" int lcv_linear_f32_smallm(const float* a, const void* w, const void* 
   }
   return LCV_OK;
 }
-
-// ---------------------------------------------------------------------------
-// LoRA down-projection: h[M,Rpad] = bf16( s * bf16( x[M,K] A[R,K]^T ) ), zero padded to Rpad columns.
-// Also serves the backward g = s * dy B (x := dy, A := B^T).  HBM-bound on x (rank r flop/B):
-// one wave owns 4 rows so every 16-byte piece of A (L1/L2-resident, <= 800 KB) is reused 4 times.
-// ---------------------------------------------------------------------------
-template <int RMAX>
-__global__ __launch_bounds__(256) void lora_down_kernel(const bf16_t* __restrict__ x,
-                                                        const bf16_t* __restrict__ A,
-                                                        bf16_t* __restrict__ hout, int64_t M, int K, int R,
-                                                        int Rpad, int64_t ldx, float s) {
-  const int lane = threadIdx.x & 63;
-  const int64_t row0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;
-  if (row0 >= M) return;
-  int64_t rows[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) rows[i] = (row0 + i < M) ? row0 + i : M - 1;
-  float acc[4][RMAX];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < RMAX; ++j) acc[i][j] = 0.f;
-  for (int k = lane * 8; k < K; k += 512) {
-    float xf[4][8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) unpack8(*reinterpret_cast<const u16x8*>(x + rows[i] * ldx + k), xf[i]);
-#pragma unroll
-    for (int j = 0; j < RMAX; ++j) {
-      if (j < R) {
-        float af[8];
-        unpack8(*reinterpret_cast<const u16x8*>(A + (int64_t)j * K + k), af);
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc[i][j] += xf[i][e] * af[e];
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float mine = 0.f;  // lane j keeps column j
-#pragma unroll
-    for (int j = 0; j < RMAX; ++j) {
-      if (j < R) {
-        const float t = wave_sum(acc[i][j]);
-        if (lane == j) mine = t;
-      }
-    }
-    if (row0 + i < M && lane < Rpad) hout[(row0 + i) * Rpad + lane] = (lane < R) ? f2bf(s * bfround(mine)) : (bf16_t)0;
-  }
-}
-
-extern "C" int lcv_lora_down(const void* x, const void* A, void* h, int64_t M, int64_t K, int64_t R,
-                             int64_t Rpad, int64_t ldx, float s, void* stream) {
-  LCV_CHECK_ARG(x && A && h, "lora_down: null pointer");
-  LCV_CHECK_ARG(R >= 1 && R <= 32 && Rpad >= R && Rpad <= 64, "lora_down: rank %ld unsupported (1..32, Rpad <= 64)", (long)R);
-  LCV_CHECK_ARG(K % 8 == 0 && ldx % 8 == 0, "lora_down: K and ldx must be multiples of 8");
-  if (M == 0) return LCV_OK;
-  const unsigned blocks = (unsigned)((M + 15) / 16);
-  hipStream_t st = (hipStream_t)stream;
-  if (R <= 8)
-    hipLaunchKernelGGL(lora_down_kernel<8>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)A, (bf16_t*)h, M, (int)K, (int)R, (int)Rpad, ldx, s);
-  else if (R <= 16)
-    hipLaunchKernelGGL(lora_down_kernel<16>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)A, (bf16_t*)h, M, (int)K, (int)R, (int)Rpad, ldx, s);
-  else
-    hipLaunchKernelGGL(lora_down_kernel<32>, dim3(blocks), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)A, (bf16_t*)h, M, (int)K, (int)R, (int)Rpad, ldx, s);
-  LCV_LAUNCH_CHECK("lora_down");
-  return LCV_OK;
-}

@@ -262,13 +262,17 @@ def linear_f32_smallm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Ten
     return out
 
 
+def _lora_down(name: str, x: torch.Tensor, A: torch.Tensor, s: float, rpad: int, draw=()) -> torch.Tensor:
+    """lcv_lora_down (draw empty) or lcv_lora_down_dropout (draw = _draw(...)): the output and the call."""
+    M, K = x.shape
+    h = torch.empty((M, rpad), dtype=BF16, device=x.device)
+    call(name, _ptr(x), _ptr(A.contiguous()), _ptr(h), M, K, A.shape[0], rpad, x.stride(0), float(s), *draw, _stream())
+    return h
+
+
 def lora_down(x: torch.Tensor, A: torch.Tensor, s: float, rpad: int = 64) -> torch.Tensor:
     _req(x, BF16, "lora_down.x"); _req(A, BF16, "lora_down.A")
-    M, K = x.shape
-    R = A.shape[0]
-    h = torch.empty((M, rpad), dtype=BF16, device=x.device)
-    call("lcv_lora_down", _ptr(x), _ptr(A.contiguous()), _ptr(h), M, K, R, rpad, x.stride(0), float(s), _stream())
-    return h
+    return _lora_down("lcv_lora_down", x, A, s, rpad)
 
 
 # ------------------------------------------------------------ LoRA dropout ---
@@ -277,18 +281,18 @@ def lora_down(x: torch.Tensor, A: torch.Tensor, s: float, rpad: int = 64) -> tor
 _U64 = (1 << 64) - 1
 
 
+def _draw(p: float, seed: int, offset: int, row0: int) -> tuple:
+    """The four mask arguments as the C ABI takes them."""
+    return float(p), int(seed) & _U64, int(offset) & _U64, int(row0)
+
+
 def lora_down_dropout(x: torch.Tensor, A: torch.Tensor, s: float, p: float, seed: int, offset: int, rpad: int = 64,
                       row0: int = 0) -> torch.Tensor:
     """h [M, rpad] = bf16(s * bf16(xd A^T)), xd = bf16(x * mask * scale), zero padded."""
     _req(x, BF16, "lora_down_dropout.x"); _req(A, BF16, "lora_down_dropout.A")
     if x.dim() != 2 or x.stride(1) != 1:
         raise _lib.LcvError("lora_down_dropout: x must be 2-D with contiguous rows")
-    M, K = x.shape
-    R = A.shape[0]
-    h = torch.empty((M, rpad), dtype=BF16, device=x.device)
-    call("lcv_lora_down_dropout", _ptr(x), _ptr(A.contiguous()), _ptr(h), M, K, R, rpad, x.stride(0), float(s), float(p),
-         int(seed) & _U64, int(offset) & _U64, int(row0), _stream())
-    return h
+    return _lora_down("lcv_lora_down_dropout", x, A, s, rpad, _draw(p, seed, offset, row0))
 
 
 def tn_skinny_dropout(g: torch.Tensor, x: torch.Tensor, R: int, p: float, seed: int, offset: int, scale: float = 1.0,
@@ -297,13 +301,7 @@ def tn_skinny_dropout(g: torch.Tensor, x: torch.Tensor, R: int, p: float, seed: 
     _req(g, BF16, "tn_skinny_dropout.g"); _req(x, BF16, "tn_skinny_dropout.x")
     if x.dim() != 2 or x.stride(1) != 1 or not g.is_contiguous():
         raise _lib.LcvError("tn_skinny_dropout: x must be 2-D with contiguous rows, g contiguous")
-    M, K = x.shape
-    out = torch.empty((R, K), dtype=F32, device=x.device)
-    ws_bytes = int(_lib.load().lcv_tn_skinny_dropout_ws_bytes(M, K, R))
-    ws = torch.empty((max(ws_bytes, 16) // 4,), dtype=F32, device=x.device)     # per-row-group partial sums (caching allocator)
-    call("lcv_tn_skinny_dropout", _ptr(g), _ptr(x), _ptr(out), M, K, R, g.shape[1], x.stride(0), float(scale), float(p),
-         int(seed) & _U64, int(offset) & _U64, int(row0), _ptr(ws), ws_bytes, _stream())
-    return out
+    return _tn_skinny("lcv_tn_skinny_dropout", g, x, R, scale, _draw(p, seed, offset, row0))
 
 
 def lora_dx_dropout_add(dx: torch.Tensor, g: torch.Tensor, A: torch.Tensor, p: float, seed: int, offset: int,
@@ -315,8 +313,8 @@ def lora_dx_dropout_add(dx: torch.Tensor, g: torch.Tensor, A: torch.Tensor, p: f
         raise _lib.LcvError("lora_dx_dropout_add: dx must be 2-D contiguous, g 2-D with contiguous rows")
     M, K = dx.shape
     R = A.shape[0]
-    call("lcv_lora_dx_dropout_add", _ptr(dx), _ptr(g), _ptr(A.contiguous()), M, K, R, g.shape[1], g.stride(0), float(p),
-         int(seed) & _U64, int(offset) & _U64, int(row0), _stream())
+    call("lcv_lora_dx_dropout_add", _ptr(dx), _ptr(g), _ptr(A.contiguous()), M, K, R, g.shape[1], g.stride(0),
+         *_draw(p, seed, offset, row0), _stream())
     return dx
 
 
@@ -324,7 +322,7 @@ def lora_dropout_mask(M: int, K: int, p: float, seed: int, offset: int, row0: in
     """The 0 / 1 mask of rows [row0, row0 + M) as uint8 [M, K]: what the three kernels above regenerate."""
     out = torch.empty((M, K), dtype=torch.uint8, device=device)
     _req(out, torch.uint8, "lora_dropout_mask.out")
-    call("lcv_lora_dropout_mask", _ptr(out), M, K, float(p), int(seed) & _U64, int(offset) & _U64, int(row0), _stream())
+    call("lcv_lora_dropout_mask", _ptr(out), M, K, *_draw(p, seed, offset, row0), _stream())
     return out
 
 
@@ -664,16 +662,20 @@ def linear_f32_smallm_bwd(dy, w, a, act_in=0):
     return da
 
 
+def _tn_skinny(name, g, x, R, scale, draw=()):
+    """lcv_tn_skinny (draw empty) or lcv_tn_skinny_dropout (draw = _draw(...)): the output, the workspace and the call."""
+    M, K = x.shape
+    out = torch.empty((R, K), dtype=F32, device=x.device)
+    ws_bytes = int(getattr(_lib.load(), name + "_ws_bytes")(M, K, R))
+    ws = torch.empty((max(ws_bytes, 16) // 4,), dtype=F32, device=x.device)     # per-row-group partial sums (caching allocator)
+    call(name, _ptr(g), _ptr(x), _ptr(out), M, K, R, g.shape[1], x.stride(0), float(scale), *draw, _ptr(ws), ws_bytes, _stream())
+    return out
+
+
 def tn_skinny(g, x, R, scale=1.0):
     """out[R, K] fp32 = scale * g[:, :R]^T @ x  (g [M, Rpad] bf16, x [M, K] bf16)."""
     _req(g, BF16, "tn_skinny.g"); _req(x, BF16, "tn_skinny.x")
-    M, K = x.shape
-    out = torch.empty((R, K), dtype=F32, device=x.device)
-    ws_bytes = int(_lib.load().lcv_tn_skinny_ws_bytes(M, K, R))
-    ws = torch.empty((max(ws_bytes, 16) // 4,), dtype=F32, device=x.device)     # per-row-group partial sums (caching allocator)
-    call("lcv_tn_skinny", _ptr(g), _ptr(x), _ptr(out), M, K, R, g.shape[1], x.stride(0), float(scale), _ptr(ws), ws_bytes,
-         _stream())
-    return out
+    return _tn_skinny("lcv_tn_skinny", g, x, R, scale)
 
 
 def ema_beta(beta: float, t: int, warmup: bool = False) -> float:

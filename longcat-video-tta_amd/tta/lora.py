@@ -23,15 +23,19 @@ RPAD = 64  # the rank is zero-padded to one 64-deep K step of the GEMM
 
 
 class _LoRALinearFn(torch.autograd.Function):
+    """`draw` is None, or the (p, seed, offset) of the mask on the adapter's input; g, dB and the forward GEMM are the same
+    calls either way."""
+
     @staticmethod
-    def forward(ctx, x, w, b, lora_a, lora_b, scaling):
+    def forward(ctx, x, w, b, lora_a, lora_b, scaling, draw=None):
         R = lora_a.shape[0]
-        hs = ops.lora_down(x, lora_a, scaling, RPAD)             # [M, 64] = s * bf16(x A^T), zero padded
+        # [M, 64] = s * bf16(x A^T), or s * bf16(xd A^T), zero padded
+        hs = ops.lora_down(x, lora_a, scaling, RPAD) if draw is None else ops.lora_down_dropout(x, lora_a, scaling, *draw, RPAD)
         bpad = torch.zeros((lora_b.shape[0], RPAD), dtype=lora_b.dtype, device=lora_b.device)
         bpad[:, :R].copy_(lora_b.detach())
         y = ops.gemm_nt(x, w, b, a2=hs, w2=bpad)
         ctx.save_for_backward(x, w, lora_a, lora_b, hs)
-        ctx.scaling = scaling
+        ctx.scaling, ctx.draw = scaling, draw
         return y
 
     @staticmethod
@@ -39,52 +43,21 @@ class _LoRALinearFn(torch.autograd.Function):
         x, w, lora_a, lora_b, hs = ctx.saved_tensors
         if w.requires_grad:
             raise LcvError("LoRALinear: the base weight must stay frozen (LoRA-only backward)")
-        s = ctx.scaling
+        s, draw = ctx.scaling, ctx.draw
         R, K = lora_a.shape
-        N = lora_b.shape[0]
         dy = dy.contiguous()
         g = ops.lora_down(dy, lora_b.detach().t().contiguous(), s, RPAD)   # [M, 64] = s * bf16(dy B)
         dx = None
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and draw is None:                           # g A rides in the GEMM's extra K step
             at_pad = torch.zeros((K, RPAD), dtype=lora_a.dtype, device=lora_a.device)
             at_pad[:, :R].copy_(lora_a.detach().t())
             dx = ops.gemm_nt(dy, A.transposed_weight(w), None, a2=g, w2=at_pad)
-        dA = ops.tn_skinny(g, x, R).to(lora_a.dtype)                        # [R, K]
-        dB = ops.tn_skinny(hs, dy, R).t().contiguous().to(lora_b.dtype)     # [N, R]; hs already carries s
-        return dx, None, None, dA, dB, None
-
-
-class _LoRALinearDropoutFn(torch.autograd.Function):
-    """_LoRALinearFn with the mask of (seed, offset) on the adapter's input; g, dB and both GEMMs are the same calls."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, lora_a, lora_b, scaling, p, seed, offset):
-        R = lora_a.shape[0]
-        hs = ops.lora_down_dropout(x, lora_a, scaling, p, seed, offset, RPAD)   # [M, 64] = s * bf16(xd A^T), zero padded
-        bpad = torch.zeros((lora_b.shape[0], RPAD), dtype=lora_b.dtype, device=lora_b.device)
-        bpad[:, :R].copy_(lora_b.detach())
-        y = ops.gemm_nt(x, w, b, a2=hs, w2=bpad)
-        ctx.save_for_backward(x, w, lora_a, lora_b, hs)
-        ctx.scaling, ctx.draw = scaling, (p, seed, offset)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w, lora_a, lora_b, hs = ctx.saved_tensors
-        if w.requires_grad:
-            raise LcvError("LoRALinear: the base weight must stay frozen (LoRA-only backward)")
-        s = ctx.scaling
-        p, seed, offset = ctx.draw
-        R = lora_a.shape[0]
-        dy = dy.contiguous()
-        g = ops.lora_down(dy, lora_b.detach().t().contiguous(), s, RPAD)   # [M, 64] = s * bf16(dy B)
-        dx = None
-        if ctx.needs_input_grad[0]:
+        elif ctx.needs_input_grad[0]:                                          # a mask cannot: plain GEMM, then
             dx = ops.gemm_nt(dy, A.transposed_weight(w), None)
-            ops.lora_dx_dropout_add(dx, g, lora_a.detach(), p, seed, offset)   # dx += mask * scale * (g A), one rounding
-        dA = ops.tn_skinny_dropout(g, x, R, p, seed, offset).to(lora_a.dtype)  # [R, K] = g^T xd
-        dB = ops.tn_skinny(hs, dy, R).t().contiguous().to(lora_b.dtype)        # [N, R]; hs already carries s
-        return dx, None, None, dA, dB, None, None, None, None
+            ops.lora_dx_dropout_add(dx, g, lora_a.detach(), *draw)             # dx += mask * scale * (g A), one rounding
+        dA = ops.tn_skinny(g, x, R) if draw is None else ops.tn_skinny_dropout(g, x, R, *draw)   # [R, K] = g^T x, or g^T xd
+        dB = ops.tn_skinny(hs, dy, R).t().contiguous()                         # [N, R]; hs already carries s
+        return dx, None, None, dA.to(lora_a.dtype), dB.to(lora_b.dtype), None, None
 
 
 # Observer of the dropout draws: when set, called as DRAW_HOOK(module, seed, offset) for every training forward with p > 0
@@ -132,6 +105,7 @@ class LoRALinear(nn.Module):
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
         x2 = x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)
+        draw = None
         if isinstance(self.dropout, nn.Dropout) and self.training and self.dropout.p > 0:
             if self.dropout.p >= 1:
                 raise LcvError("LoRA dropout must be below 1")
@@ -140,11 +114,9 @@ class LoRALinear(nn.Module):
             seed, offset = draw_dropout_offset(x2.device)
             if DRAW_HOOK is not None:
                 DRAW_HOOK(self, seed, offset)
-            y = _LoRALinearDropoutFn.apply(x2.contiguous(), self.original.weight, self.original.bias, self.lora_down.weight,
-                                           self.lora_up.weight, self.scaling, float(self.dropout.p), seed, offset)
-            return y.view(*shp[:-1], self.original.out_features)
+            draw = (float(self.dropout.p), seed, offset)
         y = _LoRALinearFn.apply(x2.contiguous(), self.original.weight, self.original.bias, self.lora_down.weight,
-                                self.lora_up.weight, self.scaling)
+                                self.lora_up.weight, self.scaling, draw)
         return y.view(*shp[:-1], self.original.out_features)
 
 

@@ -235,7 +235,7 @@ def silu_grad_err(x):
 
 # ---- lcv_tn_skinny
 def tn_skinny_rpb(M: int, K: int):
-    """tn_skinny_rpb of csrc/elementwise_bwd.hip: rows per workgroup and the number of row groups (grid.y)."""
+    """tn_skinny_rpb of csrc/lora.hip: rows per workgroup and the number of row groups (grid.y)."""
     groups = 64 if (K + 511) // 512 <= 8 else 32
     rpb = ((M + groups - 1) // groups + 31) // 32 * 32
     rpb = max(64, min(rpb, 1024))

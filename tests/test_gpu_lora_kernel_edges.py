@@ -2,7 +2,8 @@
 against the float64 restatements of tests/kernel_ref.py (`check_tn_skinny`, `check_lora_down`: the bound and its derivation
 sit next to the assert there), at the shapes where they go wrong: one row, partial batches of 8 rows, a single live lane or
 rank, the row-group cap, both row-group counts, a strided x, every template of lora_down at both ends of its rank range and a
-K loop of one, two and three passes.  Conventions of tests/test_gpu_kernel_edges.py: `lib.call` with caller-owned buffers,
+K loop of one, two and three passes.  The masked forms (lcv_tn_skinny_dropout, lcv_lora_down_dropout) are held at the same shapes to
+what they are by definition: the plain kernel on the dropped input, bit for bit.  Conventions of tests/test_gpu_kernel_edges.py: `lib.call` with caller-owned buffers,
 outputs NaN-filled, every input a view into a larger buffer whose guard rows and pad columns hold NaN, so that a read one
 element off shows up as a NaN in the result.
 """
@@ -10,6 +11,7 @@ import pytest
 import torch
 
 import kernel_ref as K
+import lora_dropout_ref as D
 from edge_buffers import BF16, DEV, F32, GUARD, NAN, call as _call, f32, guarded as _guarded, ptr as _p
 
 pytestmark = pytest.mark.gpu
@@ -92,7 +94,7 @@ def test_tn_skinny_rejects_a_small_or_misaligned_workspace():
 # ------------------------------------------------------------------------------------------------------ lcv_lora_down
 # s = 2.0 is a power of two: bf16(2 * bf16(t)) is exact, so those cases cannot tell the outer rounding from its absence; the
 # S037 cases (one per template) are the ones that exercise both roundings of rule 5.
-@pytest.mark.parametrize("M,K_,R,Rpad,s", [
+_DOWN_SHAPES = [
     (1, 8, 1, 8, 2.0),          # <8> at R = 1; one row (three of the wave's four rows clamped), one live lane
     (5, 520, 8, 8, S037),       # <8> at R = 8 = Rpad; the K loop's second pass has one live lane; a wave with one live row
     (18, 1032, 9, 16, 2.0),     # <16> at R = 9; three K passes; two workgroups, the second with two rows
@@ -100,7 +102,10 @@ def test_tn_skinny_rejects_a_small_or_misaligned_workspace():
     (18, 520, 17, 24, 2.0),     # <32> at R = 17
     (1, 1032, 32, 32, S037),    # <32> at R = 32 = Rpad
     (18, 8, 32, 64, 2.0),       # <32> at R = 32, K of one packet, the widest pad
-])
+]
+
+
+@pytest.mark.parametrize("M,K_,R,Rpad,s", _DOWN_SHAPES)
 def test_lora_down_edges(M, K_, R, Rpad, s):
     x = _guarded(M, K_, K_ + 8, seed=111)                                  # ldx > K
     A = _guarded(R, K_, K_, seed=112, scale=0.5)
@@ -120,3 +125,61 @@ def test_lora_down_rejects_rank_33():
     assert e.value.code == -1
     torch.cuda.synchronize()
     assert torch.isnan(h.float()).all()
+
+
+# ------------------------------------------------------------------------- the masked forms are the plain forms on xd
+SEED, OFFSET = (3 << 32) | 1234, (1 << 32) | 8          # both halves of seed and offset in use
+BIG = 1 << 33                                           # a first row whose element index needs 64 bits
+_DRAWS = [(0.5, 0), (0.1, 5), (0.5, BIG), (0.1, BIG)]   # (p, row0), dealt over the shapes in turn
+
+
+def _dropped(x, ld, p, row0, seed):
+    """xd = bf16(x * scale) where lcv_lora_dropout_mask keeps the element and +0 where it drops it, built on the device in a
+    guarded buffer of its own (NaN guard rows and pad columns, as x)."""
+    M, K_ = x.shape
+    mask = torch.empty((M, K_), dtype=torch.uint8, device=DEV)
+    _call("lcv_lora_dropout_mask", _p(mask), M, K_, p, SEED, OFFSET, row0)
+    assert 0 < int(mask.sum()) < mask.numel() or mask.numel() == 8
+    xd = _guarded(M, K_, ld, seed=seed)
+    xd.copy_(torch.where(mask.bool(), (x.float() * float(D.scale(p))).to(BF16), torch.zeros((), dtype=BF16, device=DEV)))
+    return xd
+
+
+@pytest.mark.parametrize("shape,draw", list(zip(_TN_SHAPES, _DRAWS)))
+def test_tn_skinny_dropout_is_tn_skinny_on_the_dropped_input(shape, draw):
+    (M, K_, ldx, R, Rpad), (p, row0) = shape, draw
+    g, x = _tn_inputs(M, K_, ldx, R, Rpad)               # the heavy last row included
+    xd = _dropped(x, ldx, p, row0, seed=103)
+    need = _tn_ws(M, K_, R)
+    from lcv_hip import lib
+    assert lib.load().lcv_tn_skinny_dropout_ws_bytes(M, K_, R) == need
+    ws = torch.full((need // 4,), NAN, dtype=F32, device=DEV)
+    outs = []
+    for name, src, draw_args in (("lcv_tn_skinny_dropout", x, (p, SEED, OFFSET, row0)), ("lcv_tn_skinny", xd, ())):
+        buf = torch.full((R + 2 * GUARD, K_), 7.5, dtype=F32, device=DEV)     # guard rows around `out` hold 7.5
+        out = buf[GUARD: GUARD + R]
+        out.fill_(NAN)
+        ws.fill_(NAN)
+        _call(name, _p(g), _p(src), _p(out), M, K_, R, Rpad, ldx, S037, *draw_args, _p(ws), need)
+        assert (buf[:GUARD] == 7.5).all() and (buf[GUARD + R:] == 7.5).all(), f"{name} wrote outside out[R, K]"
+        outs.append(out.contiguous())
+    assert not torch.isnan(outs[1]).any()
+    K.assert_bits(outs[0], outs[1], what=f"tn_skinny_dropout vs tn_skinny on xd, M={M} K={K_} R={R} p={p} row0={row0}")
+
+
+@pytest.mark.parametrize("shape,draw", list(zip(_DOWN_SHAPES, _DRAWS + _DRAWS)))
+def test_lora_down_dropout_is_lora_down_on_the_dropped_input(shape, draw):
+    (M, K_, R, Rpad, s), (p, row0) = shape, draw
+    x = _guarded(M, K_, K_ + 8, seed=111)                                  # ldx = K + 8
+    A = _guarded(R, K_, K_, seed=112, scale=0.5)
+    xd = _dropped(x, K_ + 8, p, row0, seed=113)
+    outs = []
+    for name, src, draw_args in (("lcv_lora_down_dropout", x, (p, SEED, OFFSET, row0)), ("lcv_lora_down", xd, ())):
+        h = torch.full((M + 2 * GUARD, Rpad), NAN, dtype=BF16, device=DEV)
+        out = h[GUARD: GUARD + M]
+        _call(name, _p(src), _p(A), _p(out), M, K_, R, Rpad, K_ + 8, s, *draw_args)
+        assert torch.isnan(h[:GUARD].float()).all() and torch.isnan(h[GUARD + M:].float()).all(), f"{name} wrote outside h[M, Rpad]"
+        outs.append(out.contiguous())
+    assert not torch.isnan(outs[1].float()).any()
+    K.assert_bits(outs[0], outs[1], what=f"lora_down_dropout vs lora_down on xd, M={M} K={K_} R={R}/{Rpad} p={p} row0={row0}")
+    assert (outs[0][:, R:].view(torch.int16) == 0).all(), "pad columns must be exactly +0"

@@ -58,6 +58,19 @@ def test_a_changed_instruction_register_count_or_kernarg_size_compares_unequal(c
     assert any("DIFFERS" in r for r in report), report
 
 
+def test_a_renamed_kernel_in_another_file_compares_equal_under_its_new_name():
+    """--map: `tn_skinny_dropout_kernel` of one file against `tn_skinny_kernel<8, drop_args>` of another."""
+    old = listing(file="lora_dropout.hip", sym="_Z24tn_skinny_dropout_kernelPKtS1_lli9drop_args", fn=1)
+    plain = listing(file="lora.hip", sym="_Z16tn_skinny_kernelILi8EJEEvPKtS1_PflDpT0_", fn=3, inst="v_pk_fma_f32 v[0:1], v[2:3]")
+    sym = "_Z16tn_skinny_kernelILi8EJ9drop_argsEEvPKtS1_PflDpT0_"
+    rename = {"tn_skinny_dropout_kernel": "tn_skinny_kernelILi8EJ9drop_argsEE"}
+    report = E.compare(old, plain + listing(file="lora.hip", sym=sym, fn=4), rename=rename)
+    assert len(report) == 1 and report[0].startswith("tn_skinny_kernelILi8EJ9drop_argsEE: identical"), report   # the empty pack is another kernel
+    report = E.compare(old, plain + listing(file="lora.hip", sym=sym, fn=4, inst="v_exp_f32_e32 v1, v3"), rename=rename)
+    assert len(report) == 1 and "DIFFERS" in report[0], report
+    assert "only in the new" in E.compare(old, plain, rename={"no_such_kernel": "tn_skinny_kernelILi8EJEE"})[0]
+
+
 def test_another_instantiation_is_another_kernel():
     report = E.compare(listing(), listing(sym="_Z15attn_fwd_kernelILi8ELi0ELb0ELi3EEv13AttnFwdParams"))
     assert sum("only in" in r for r in report) == 2, report

@@ -103,9 +103,29 @@ def test_every_lora_entry_point_has_a_kernel_level_test():
 
 
 def test_the_source_uses_no_atomics_and_reads_no_environment():
-    src = (ROOT / "longcat-video-tta_amd" / "csrc" / "lora_dropout.hip").read_text()
-    src += (ROOT / "longcat-video-tta_amd" / "csrc" / "philox.h").read_text()
-    assert "atomicAdd" not in src and "atomic_" not in src and "lcv_knob(" not in src and "getenv(" not in src and "asm" not in src
+    """csrc/lora.hip holds the plain and the masked adapter kernels.  Atomics: only in the body of the one publish function,
+    which is called from one place, under the compile-time condition "no mask" - so no masked instantiation contains it."""
+    csrc = ROOT / "longcat-video-tta_amd" / "csrc"
+    src = (csrc / "lora.hip").read_text() + (csrc / "philox.h").read_text()
+    assert "lcv_knob(" not in src and "getenv(" not in src and "asm" not in src
+    publish = "tn_skinny_publish_atomic"
+    code = " ".join(re.sub(r"//[^\n]*", "", src).split())          # comments may speak of atomics; code may not
+    define = re.search(r"void %s\([^)]*\) \{[^{}]*\}" % publish, code)
+    assert define and "atomicAdd(" in define.group(0)
+    rest = code.replace(define.group(0), "")
+    assert rest.count(publish) == 1, "the publish function is called from exactly one place"
+    assert re.search(r"if constexpr \(sizeof\.\.\.\(D\) == 0\) \{? ?%s\(" % publish, rest), "not under the no-mask condition"
+    assert "atomic" not in rest.replace(publish, "").lower()
+    # one definition of each shared piece under csrc/, and none of them left in the files they came from
+    everything = {p.name: p.read_text() for p in [*csrc.glob("*.hip"), *csrc.glob("*.h")]}
+    for pattern in (r"void lora_down_kernel\(", r"void tn_skinny_kernel\(", r"void tn_skinny_reduce_kernel\(",
+                    r"int64_t tn_skinny_rpb\(", r"define TN_MAXROWS\b"):
+        homes = {name: len(re.findall(pattern, text)) for name, text in everything.items() if re.search(pattern, text)}
+        assert homes == {"lora.hip": 1}, (pattern, homes)
+    for old_home in ("gemm.hip", "elementwise_bwd.hip"):
+        for word in ("lora_down", "tn_skinny", "TN_MAXROWS"):
+            assert word not in everything[old_home], (old_home, word)
+    assert not (csrc / "lora_dropout.hip").exists()
 
 
 def test_new_ops_refuse_cpu_tensors():

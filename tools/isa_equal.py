@@ -7,7 +7,11 @@ them kernel by kernel: instructions, labels, the .amdhsa_* descriptor (register 
 metadata.  Normalising means: comments, blank lines, `.file` / `.ident` go; a mangled symbol becomes its function name plus
 template arguments (the parameter types - a renamed struct - drop out); basic-block labels lose their function index.
 
-Usage: python tools/isa_equal.py <rev> [file.hip ...]     (default: csrc/attn_*.hip; exit code 1 on any difference)
+A kernel that was renamed or moved to another file is compared with --map: the old kernel's listing, with its name replaced
+by the new one, against the new kernel's.  Kernel names are the normalised ones, as the report prints them.
+
+Usage: python tools/isa_equal.py <rev> [--map old.hip:old_kernel=new.hip:new_kernel ...] [file.hip ...]
+       (default without --map: csrc/attn_*.hip; exit code 1 on any difference)
 """
 import re
 import subprocess
@@ -15,12 +19,13 @@ import sys
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 ROOT = Path(__file__).resolve().parents[1]
 PKG = "longcat-video-tta_amd"
 _MANGLED = re.compile(r"_Z(\d+)(\w+)")
-_TEMPLATE = re.compile(r"I(?:L[a-z]\w*?E)+E")       # literal template arguments only: <8, 0, true, 0> = ILi8ELi0ELb1ELi0EE
+# literal template arguments and parameter packs of named types: <8, 0, true, 0> = ILi8ELi0ELb1ELi0EE, <8, drop_args> = ILi8EJ9drop_argsEE
+_TEMPLATE = re.compile(r"I(?:L[a-z]\w*?E|J\w*?E)+E")
 _LABEL = re.compile(r"\.L(BB|func_end|func_begin)\d+")
 
 
@@ -57,9 +62,13 @@ def normalise(text: str) -> Dict[str, List[str]]:
     return out
 
 
-def compare(old: str, new: str, show: int = 4) -> List[str]:
-    """-> one report line per kernel: `identical`, or where the two listings part."""
+def compare(old: str, new: str, show: int = 4, rename: Optional[Dict[str, str]] = None) -> List[str]:
+    """-> one report line per kernel: `identical`, or where the two listings part.  With `rename` {old kernel: new kernel} only
+    those kernels are compared, the old one under its new name."""
     a, b = normalise(old), normalise(new)
+    if rename:
+        a = {n: [line.replace(o, n) for line in a[o]] for o, n in rename.items() if o in a}
+        b = {k: v for k, v in b.items() if k in rename.values()}
     report = []
     for k in sorted(set(a) | set(b)):
         if k not in a or k not in b:
@@ -88,20 +97,29 @@ def main(argv: List[str]) -> int:
     if not argv:
         print(__doc__)
         return 2
-    rev = argv[0]
-    names = argv[1:] or sorted(p.name for p in (ROOT / PKG / "csrc").glob("attn_*.hip"))
+    rev, argv = argv[0], argv[1:]
+    maps: Dict[tuple, Dict[str, str]] = {}                # (old file, new file) -> {old kernel: new kernel}
+    while "--map" in argv:
+        i = argv.index("--map")
+        (old_file, old_kernel), (new_file, new_kernel) = (side.split(":", 1) for side in argv[i + 1].split("=", 1))
+        maps.setdefault((old_file, new_file), {})[old_kernel] = new_kernel
+        del argv[i:i + 2]
+    names = argv or ([] if maps else sorted(p.name for p in (ROOT / PKG / "csrc").glob("attn_*.hip")))
+    jobs = [(n, n, None) for n in names] + [(o, n, r) for (o, n), r in maps.items()]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         tmp = Path(tmp)
         tar = subprocess.run(["git", "-C", str(ROOT), "archive", rev, f"{PKG}/csrc", "include"], capture_output=True, check=True)
         subprocess.run(["tar", "-x", "-C", str(tmp)], input=tar.stdout, check=True)
 
-        def one(name):
-            old = device_asm(tmp / PKG / "csrc", tmp / "include", Path(name).name, tmp / (Path(name).stem + ".old.s"))
-            new = device_asm(ROOT / PKG / "csrc", ROOT / "include", Path(name).name, tmp / (Path(name).stem + ".new.s"))
-            return name, compare(old, new)
+        def one(job):
+            old_name, name, rename = job
+            stem = f"{Path(old_name).stem}-{Path(name).stem}"
+            old = device_asm(tmp / PKG / "csrc", tmp / "include", Path(old_name).name, tmp / f"{stem}.old.s")
+            new = device_asm(ROOT / PKG / "csrc", ROOT / "include", Path(name).name, tmp / f"{stem}.new.s")
+            return (f"{old_name} -> {name}" if rename else name), compare(old, new, rename=rename)
         with ThreadPoolExecutor(max_workers=6) as ex:
-            for name, report in ex.map(one, names):
+            for name, report in ex.map(one, jobs):
                 print(f"== {name}")
                 print("\n".join("  " + line for line in report))
                 bad += sum("identical" not in line.split("\n")[0] for line in report)
