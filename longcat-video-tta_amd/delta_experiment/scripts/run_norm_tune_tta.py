@@ -25,18 +25,14 @@ def build_parser():
     p.add_argument("--norm-lr", type=float, default=1e-3)
     p.add_argument("--norm-target", type=str, default="all_norm", choices=["cross_attn_norm", "qk_norm", "all_norm"])
     p.add_argument("--also-tune-delta", action="store_true")
-    p.add_argument("--master-weights", action="store_true",
-                   help="fp32 master weights for the bf16 norm weights (include/lcv_hip_master.h)")
-    C.add_adam_8bit_arg(p)
-    C.add_grad_accum_arg(p)
-    C.add_decay_to_base_arg(p)
-    C.add_weight_ema_args(p)
+    C.add_optimizer_args(p, decay_to_base=True,
+                         master_weights_help="fp32 master weights for the bf16 norm weights (include/lcv_hip_master.h)")
     R.add_shared_groups(p, clip_gate=False)
     return p
 
 
 def parse_args(argv=None):
-    return C.parse_with_step_cache(build_parser(), argv, lambda p, a: C.parse_with_weight_ema(p, a, C.parse_with_decay_to_base))
+    return C.parse_with_step_cache(build_parser(), argv, C.parse_optimizer_args)
 
 
 def main(argv=None):
@@ -46,9 +42,7 @@ def main(argv=None):
         make_wrapper=lambda dit: NormTuneForward(dit, args.norm_target, also_tune_delta=args.also_tune_delta),
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_norm_params(
             w, w.tuned_params, cond, train, pe, pm, num_steps=args.norm_steps, lr=args.norm_lr, device=device, dtype=torch.bfloat16,
-            early_stopper=es, train_latents_variants=tv, master_weights=args.master_weights,
-            moments_8bit=args.adam_8bit, grad_accum=args.grad_accum, decay_to_base=args.decay_to_base,
-            **C.weight_ema_kwargs(args)),
+            early_stopper=es, train_latents_variants=tv, **C.optimizer_kwargs(args)),
         params_of=lambda w: w.tuned_params,
         result_extra=lambda opt: {k: opt[k] for k in ("norm_param_drift", "delta_norm", "drift_norm") if k in opt},
         # this runner writes no config.json (as the reference's does not): the flag is recorded here, when it is set

@@ -678,487 +678,6 @@ def tn_skinny(g, x, R, scale=1.0):
     return _tn_skinny("lcv_tn_skinny", g, x, R, scale)
 
 
-def ema_beta(beta: float, t: int, warmup: bool = False) -> float:
-    """The beta of the t-th update (t counts from 1) of the weight average: `beta`, or under `warmup` the smaller of it and
-    (1 + t) / (10 + t) - 0.18, 0.25, ..., 0.55 at t = 10, 0.70 at t = 20 - so that an average started at the base weights does
-    not lag a run of 10-20 steps.  Formed in double."""
-    beta = float(beta)
-    return min(beta, (1.0 + t) / (10.0 + t)) if warmup else beta
-
-
-# ===================================================================== fused clip + AdamW
-class FusedAdamWClip:
-    """clip_grad_norm_ + AdamW.step over a fixed parameter list in two launches (norm, update).
-
-    Mirrors `AdamW(lora_params, lr, betas=(0.9, 0.999), weight_decay, eps=1e-8)` +
-    `clip_grad_norm_(lora_params, max_norm)` of lora_experiment/scripts/run_lora_tta.py:462-468, 513-514,
-    including the bf16 rounding points of the foreach implementation.  `param_groups` is kept so the reference's
-    warm-up loop (`for pg in optimizer.param_groups: pg["lr"] = ...`) works unchanged.
-
-    `master_weights=True` (bf16 parameters only) gives every parameter element an int16 low word (include/lcv_hip_master.h):
-    the step then runs in fp32 on join(bf16 word, low word) with fp32 moments and rounds nothing to bf16 in between, so
-    updates below half a bf16 ulp accumulate instead of vanishing.  The bf16 words stay where every GEMM reads them.
-    Anyone else who writes the parameters (a restore, a reset) calls `resync()` afterwards.
-
-    `moments_8bit=True` (with `master_weights=True` only) keeps each moment in one byte per element plus one fp32 scale per
-    moment per 512 elements (include/lcv_hip_moments8.h): about 2.016 B / parameter of moments instead of 8.  The parameter
-    update still uses the fp32 moments of the step; only what is kept between steps is quantised.
-
-    `grad_accum=N` with N > 1 (with `master_weights=True` and fp32 moments only) makes one step the mean of N micro-steps
-    (include/lcv_hip_accum.h): every parameter element gets a zeroed fp32 accumulator (+4 B / parameter); after each backward
-    `accumulate()` adds `.grad * (1/N)` into it in fp32 and drops the `.grad`s; `clip_grad_norm_` and `step()` then read the
-    accumulators as the (fp32) gradients, over every parameter that received a gradient in at least one micro-step, and refuse
-    to run before N micro-steps are in.  `zero_grad()` zeroes the accumulators and starts the next step.
-
-    `anchor=[...]` (with `master_weights=True` only; contiguous bf16 GPU tensors shaped like `params`, held by reference, not
-    copied) turns the weight decay into a pull toward those base words instead of toward zero (include/lcv_hip_anchor.h): the
-    step reads 2 B / parameter more and allocates nothing.  `drift_norm()` is the distance from them.
-
-    `enable_weight_ema(beta)` (with `master_weights=True` only, once, before the first step) keeps an fp32 average of the masters
-    (include/lcv_hip_ema.h, +4 B / parameter): every `step()` ends with e = w - beta_t * (w - e) in a launch of its own.
-    `ema_swap()` exchanges the average and the masters bit for bit, so the model can be scored or run with the average and
-    training can go on afterwards; while the average is in the parameters (`ema_in_params`) the optimizer refuses to train."""
-    CHUNK = 2048
-    NORM_SLOTS = 64   # partial sums of squares per tensor (csrc/optim.hip)
-    MOMENTS8_BLOCK = 512   # elements per scale (LCV_MOMENTS8_BLOCK)
-    moments_8bit = False
-    grad_accum = 1
-    _anchor = ()
-    _drift = None
-    weight_ema = None        # the beta of enable_weight_ema(), or None: no average is kept
-    ema_in_params = False    # True between an ema_swap() and the next: the parameters hold the average
-    _ema = ()
-    _ema_table_cache = None
-
-    def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-8, master_weights=False,
-                 moments_8bit=False, *, grad_accum: int = 1, anchor=None):
-        self.params = [p for p in params]
-        if not self.params:
-            raise ValueError("optimizer got an empty parameter list")
-        dt = self.params[0].dtype
-        if dt not in (BF16, F32) or any(p.dtype != dt for p in self.params):
-            raise _lib.LcvError("FusedAdamWClip: parameters must be all bf16 or all fp32")
-        self.f32 = dt == F32
-        self.param_groups = [dict(params=self.params, lr=lr, betas=betas, weight_decay=weight_decay, eps=eps)]
-        self._init_master(master_weights)
-        self._init_anchor(anchor)
-        self.moments_8bit = bool(moments_8bit)
-        self._scales = []
-        self._scale_desc = None
-        if self.moments_8bit:        # uint8 codes and fp32 block scales, zeroed: the state "all moments zero"
-            if not self.master_weights:
-                raise _lib.LcvError("FusedAdamWClip: moments_8bit=True needs master_weights=True (the 8-bit moments exist "
-                                    "for the master-weight step only)")
-            self.exp_avg = [torch.zeros(p.shape, dtype=torch.uint8, device=p.device) for p in self.params]
-            self.exp_avg_sq = [torch.zeros(p.shape, dtype=torch.uint8, device=p.device) for p in self.params]
-            self._scales = [torch.zeros((2, (p.numel() + self.MOMENTS8_BLOCK - 1) // self.MOMENTS8_BLOCK), dtype=F32,
-                                        device=p.device) for p in self.params]
-        elif self.master_weights:    # fp32 moments: +8 B / parameter
-            self.exp_avg = [torch.zeros(p.shape, dtype=F32, device=p.device) for p in self.params]
-            self.exp_avg_sq = [torch.zeros(p.shape, dtype=F32, device=p.device) for p in self.params]
-        else:
-            self.exp_avg = [torch.zeros_like(p) for p in self.params]
-            self.exp_avg_sq = [torch.zeros_like(p) for p in self.params]
-        self._init_accum(grad_accum)
-        self.step_count = 0
-        dev = self.params[0].device
-        self._ws = torch.zeros(len(self.params) * self.NORM_SLOTS, dtype=F32, device=dev)
-        self._norm_coef = torch.zeros(2, dtype=F32, device=dev)
-        self._desc = None
-        self._desc_key = None
-        self._have_coef = False
-
-    def _init_master(self, master_weights: bool) -> None:
-        """Zeroed int16 low words (+2 B / parameter) when master weights are on; `f32` stays False for the clip (the
-        gradients are bf16, so a tensor's norm is still a bf16 number)."""
-        self.master_weights = bool(master_weights)
-        self._low = []
-        self._low_desc = None
-        if not self.master_weights:
-            return
-        name = type(self).__name__
-        if self.f32:
-            raise _lib.LcvError(f"{name}: master_weights=True is for bf16 parameters; fp32 parameters are already exact")
-        if any(not p.is_cuda for p in self.params):
-            raise _lib.LcvError(f"{name}: master_weights=True needs parameters on the GPU (no CPU path exists)")
-        if any(not p.is_contiguous() for p in self.params):
-            raise _lib.LcvError(f"{name}: master_weights=True needs contiguous parameters")
-        self._low = [torch.zeros(p.shape, dtype=torch.int16, device=p.device) for p in self.params]
-
-    def _check_anchor(self, anchor):
-        """A list of base words that fits `params`: contiguous bf16 GPU tensors of the parameters' shapes."""
-        name = type(self).__name__
-        anchor = [a for a in anchor]
-        if len(anchor) != len(self.params):
-            raise _lib.LcvError(f"{name}: anchor has {len(anchor)} tensors for {len(self.params)} parameters")
-        for a, p in zip(anchor, self.params):
-            if a.dtype != BF16 or not a.is_cuda or not a.is_contiguous() or a.shape != p.shape or a.device != p.device:
-                raise _lib.LcvError(f"{name}: every anchor must be a contiguous bf16 tensor on the parameter's GPU with its "
-                                    f"shape; got {a.dtype} {tuple(a.shape)} on {a.device} for {tuple(p.shape)}")
-        return anchor
-
-    def _init_anchor(self, anchor) -> None:
-        """The base words the decay pulls toward, held by reference; nothing without them."""
-        self._anchor = []
-        self._anchor_desc = None
-        self._drift = None
-        if anchor is None:
-            return
-        if not self.master_weights:
-            raise _lib.LcvError(f"{type(self).__name__}: anchor needs master_weights=True (a pull of lr * wd * (w - w0) is far "
-                                "below half a bf16 ulp; the anchor steps exist for the master-weight form only)")
-        self._anchor = self._check_anchor(anchor)
-
-    def drift_norm(self, anchor=None) -> torch.Tensor:
-        """|theta - theta0| over ALL parameters (with or without a gradient) as a 0-dim fp32 device tensor, no host sync
-        (lcv_master_drift_sumsq, fixed order): theta is join(bf16 word, low word) under master weights and the bf16 word
-        without them; theta0 the optimizer's anchor, or the list passed in."""
-        name = type(self).__name__
-        if self.f32:
-            raise _lib.LcvError(f"{name}: drift_norm() is for bf16 parameters")
-        if anchor is not None:
-            anchor = self._check_anchor(anchor)
-        elif self._anchor:
-            anchor = self._anchor
-        else:
-            raise _lib.LcvError(f"{name}: drift_norm() needs an anchor (the optimizer holds none)")
-        if any(not p.is_cuda or not p.is_contiguous() for p in self.params):
-            raise _lib.LcvError(f"{name}: drift_norm() needs contiguous parameters on the GPU")
-        dev = self.params[0].device
-        key = tuple(a.data_ptr() for a in anchor) + tuple(p.data_ptr() for p in self.params)
-        if self._drift is None or self._drift[0] != key:
-            rows, ptrs, lows, chunk = [], [], [], 0
-            for i, (p, a) in enumerate(zip(self.params, anchor)):
-                if p.numel() == 0:
-                    continue
-                rows.append([p.data_ptr(), 0, 0, 0, p.numel(), chunk])
-                ptrs.append(a.data_ptr())
-                if self.master_weights:
-                    lows.append(self._low[i].data_ptr())
-                chunk += (p.numel() + self.CHUNK - 1) // self.CHUNK
-            if not rows:
-                raise _lib.LcvError(f"{name}: drift_norm() over no elements")
-            self._drift = (key, torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(ptrs, dtype=torch.int64).to(dev),
-                           torch.tensor(lows, dtype=torch.int64).to(dev) if lows else None, len(rows), chunk,
-                           torch.empty((chunk,), dtype=F32, device=dev))
-        _, d, a_desc, low_desc, n, chunks, part = self._drift
-        out = torch.empty(2, dtype=F32, device=dev)
-        call("lcv_master_drift_sumsq", _ptr(d), _ptr(low_desc), _ptr(a_desc), n, chunks, _ptr(part), chunks * 4, _ptr(out),
-             _stream())
-        return out[1]
-
-    def enable_weight_ema(self, beta: float, warmup: bool = False) -> None:
-        """Start the fp32 average of the masters (+4 B / parameter) at the masters themselves (lcv_master_ema_load).  Once, before
-        the first `step()`.  `warmup`: the t-th update uses `ema_beta(beta, t, True)` instead of `beta`."""
-        name = type(self).__name__
-        if self.weight_ema is not None:
-            raise _lib.LcvError(f"{name}: enable_weight_ema() was already called")
-        beta = float(beta)
-        if not 0.0 <= beta < 1.0:            # a NaN fails both
-            raise ValueError(f"{name}: the beta of the weight average must be in [0, 1), got {beta}")
-        if not self.master_weights:
-            raise _lib.LcvError(f"{name}: enable_weight_ema() needs master_weights=True (an increment (1 - beta) * (w - e) is far "
-                                "below half a bf16 ulp; the average is kept in fp32 beside the master weights only)")
-        if self.step_count:
-            raise _lib.LcvError(f"{name}: enable_weight_ema() comes before the first step(), not after {self.step_count}")
-        self._ema = [torch.empty(p.shape, dtype=F32, device=p.device) for p in self.params]
-        self.weight_ema = beta
-        self._ema_warmup = bool(warmup)
-        self.ema_in_params = False
-        self.ema_reset()
-
-    def _ema_table(self):
-        """The descriptor table over ALL non-empty parameters (with or without a gradient, as drift_norm's) with the low-word
-        and the average pointers beside it, all three under one cache key."""
-        key = tuple(p.data_ptr() for p in self.params)
-        if self._ema_table_cache is None or self._ema_table_cache[0] != key:
-            dev = self.params[0].device
-            rows, lows, emas, chunk = [], [], [], 0
-            for p, low, e in zip(self.params, self._low, self._ema):
-                if p.numel() == 0:
-                    continue
-                rows.append([p.data_ptr(), 0, 0, 0, p.numel(), chunk])
-                lows.append(low.data_ptr())
-                emas.append(e.data_ptr())
-                chunk += (p.numel() + self.CHUNK - 1) // self.CHUNK
-            if not rows:
-                raise _lib.LcvError(f"{type(self).__name__}: a weight average over no elements")
-            self._ema_table_cache = (key, torch.tensor(rows, dtype=torch.int64).to(dev),
-                                     torch.tensor(lows, dtype=torch.int64).to(dev),
-                                     torch.tensor(emas, dtype=torch.int64).to(dev), len(rows), chunk)
-        _, d, low_desc, ema_desc, n, chunks = self._ema_table_cache
-        return _ptr(d), _ptr(low_desc), _ptr(ema_desc), n, chunks
-
-    def _ema_needs(self, what: str) -> None:
-        if self.weight_ema is None:
-            raise _lib.LcvError(f"{type(self).__name__}: {what} needs enable_weight_ema()")
-
-    def _ema_guard(self, what: str) -> None:
-        """Nobody trains the average by accident."""
-        if self.ema_in_params:
-            raise _lib.LcvError(f"{type(self).__name__}: {what} while the parameters hold the weight average (ema_in_params); "
-                                "call ema_swap() to put the masters back first")
-
-    def ema_tensors(self):
-        """The fp32 averages themselves, one per parameter in `params` order (empty without enable_weight_ema()).  While
-        `ema_in_params` they hold the masters."""
-        return list(self._ema)
-
-    def ema_reset(self) -> None:
-        """Load the average again from the masters and start its update count (the t of `ema_beta`) at zero."""
-        self._ema_needs("ema_reset()")
-        self._ema_guard("ema_reset()")
-        call("lcv_master_ema_load", *self._ema_table(), _stream())
-        self._ema_t = 0
-
-    def _ema_update(self) -> None:
-        """What step() ends with when an average is kept: its own launch after whichever step kernel ran."""
-        self._ema_t += 1
-        call("lcv_master_ema_update", *self._ema_table(), ema_beta(self.weight_ema, self._ema_t, self._ema_warmup), _stream())
-
-    def ema_swap(self) -> None:
-        """Exchange the average and the masters (lcv_master_ema_swap) and toggle `ema_in_params`: after one call the parameters
-        are the average in valid master format (bf16 word = its round-to-nearest), after two every bit is back."""
-        self._ema_needs("ema_swap()")
-        call("lcv_master_ema_swap", *self._ema_table(), _stream())
-        self.ema_in_params = not self.ema_in_params
-        global PARAM_EPOCH           # the parameters changed under cached copies of them, as after a step
-        PARAM_EPOCH += 1
-
-    def _init_accum(self, grad_accum: int) -> None:
-        """Zeroed fp32 accumulators (+4 B / parameter) when `grad_accum` > 1; nothing at 1."""
-        self.grad_accum = int(grad_accum)
-        self._acc = []
-        self._acc_live = set()       # indices of the parameters that received a gradient in a micro-step of this step
-        self._micro = 0
-        self._micro_desc = None
-        self._micro_key = None
-        if self.grad_accum < 1:
-            raise ValueError(f"grad_accum must be at least 1, got {grad_accum}")
-        if self.grad_accum == 1:
-            return
-        name = type(self).__name__
-        if not self.master_weights:
-            raise _lib.LcvError(f"{name}: grad_accum > 1 needs master_weights=True (the fp32-gradient steps exist for the "
-                                "master-weight form only)")
-        if self.moments_8bit:
-            raise _lib.LcvError(f"{name}: grad_accum > 1 needs moments_8bit=False (the 8-bit-moment step reads bf16 gradients)")
-        self._acc = [torch.zeros(p.shape, dtype=F32, device=p.device) for p in self.params]
-
-    def accumulated_grads(self):
-        """The fp32 accumulators, one per parameter in `params` order (empty at grad_accum=1)."""
-        return list(self._acc)
-
-    def accumulate(self) -> None:
-        """One micro-step: acc += float(.grad) * (1 / grad_accum) over the parameters that hold a `.grad`
-        (lcv_grad_accumulate), then those `.grad`s are dropped."""
-        name = type(self).__name__
-        self._ema_guard("accumulate()")
-        if self.grad_accum == 1:
-            raise _lib.LcvError(f"{name}: accumulate() needs grad_accum > 1")
-        if self._micro >= self.grad_accum:
-            raise _lib.LcvError(f"{name}: {self._micro} of {self.grad_accum} micro-steps are already accumulated; step() and "
-                                "zero_grad() come next")
-        sel, grads = [], []
-        for i, p in enumerate(self.params):
-            if p.grad is None:
-                continue
-            sel.append(i)
-            grads.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())
-        if not sel:
-            raise _lib.LcvError(f"{name}: no parameter has a gradient")
-        key = tuple(g.data_ptr() for g in grads) + tuple(sel)
-        if self._micro_desc is None or key != self._micro_key:
-            dev = self.params[0].device
-            rows, chunk = [], 0
-            for i, g in zip(sel, grads):
-                p = self.params[i]
-                rows.append([p.data_ptr(), g.data_ptr(), 0, 0, p.numel(), chunk])
-                chunk += (p.numel() + self.CHUNK - 1) // self.CHUNK
-            self._micro_desc = (torch.tensor(rows, dtype=torch.int64).to(dev),
-                                torch.tensor([self._acc[i].data_ptr() for i in sel], dtype=torch.int64).to(dev), len(sel), chunk)
-            self._micro_key = key
-        d, acc, n, chunks = self._micro_desc
-        call("lcv_grad_accumulate", _ptr(d), _ptr(acc), n, chunks, 1.0 / self.grad_accum, _stream())
-        for i in sel:
-            self.params[i].grad = None
-        self._acc_live.update(sel)
-        self._micro += 1
-
-    def _accumulated(self):
-        """The active set and its gradients under grad_accum > 1: the accumulators of every parameter that received a gradient
-        in at least one micro-step.  Refuses before all micro-steps are in."""
-        if self._micro != self.grad_accum:
-            raise _lib.LcvError(f"{type(self).__name__}: {self._micro} of {self.grad_accum} micro-steps accumulated; call "
-                                "accumulate() after every backward before clipping or stepping")
-        sel = sorted(self._acc_live)
-        return sel, [self._acc[i] for i in sel]
-
-    @property
-    def low_words(self):
-        """The int16 low-word tensors, one per parameter in `params` order (empty without master weights)."""
-        return list(self._low)
-
-    def resync(self) -> None:
-        """Zero the low words: the masters become exactly the bf16 words the parameters hold now.  Call it after anyone
-        but this optimizer has written the parameters.  A weight average (enable_weight_ema) is left alone: it neither moves to
-        the new masters nor restarts; `ema_reset()` does that."""
-        for low in self._low:
-            low.zero_()
-
-    def master_tensors(self):
-        """fp32 copies of the masters, one per parameter (lcv_master_join)."""
-        if not self.master_weights:
-            raise _lib.LcvError(f"{type(self).__name__}: master_tensors() needs master_weights=True")
-        out = []
-        for p, low in zip(self.params, self._low):
-            m = torch.empty(p.shape, dtype=F32, device=p.device)
-            if p.numel():
-                call("lcv_master_join", _ptr(p), _ptr(low), _ptr(m), p.numel(), _stream())
-            out.append(m)
-        return out
-
-    def moment_tensors(self):
-        """fp32 copies of the moments, one (exp_avg, exp_avg_sq) pair per parameter; decoded (lcv_moments8_decode) under
-        moments_8bit=True."""
-        out = []
-        for i, p in enumerate(self.params):
-            if not self.moments_8bit:
-                out.append((self.exp_avg[i].to(F32, copy=True), self.exp_avg_sq[i].to(F32, copy=True)))
-                continue
-            m = torch.zeros(p.shape, dtype=F32, device=p.device)
-            v = torch.zeros(p.shape, dtype=F32, device=p.device)
-            if p.numel():
-                call("lcv_moments8_decode", _ptr(self.exp_avg[i]), _ptr(self.exp_avg_sq[i]), _ptr(self._scales[i]), _ptr(m),
-                     _ptr(v), p.numel(), _stream())
-            out.append((m, v))
-        return out
-
-    def state_bytes(self) -> int:
-        """Bytes of optimizer state: both moments and, under moments_8bit=True, their scales.  The low words are not counted."""
-        return sum(t.numel() * t.element_size() for ts in (self.exp_avg, self.exp_avg_sq, self._scales) for t in ts)
-
-    def zero_grad(self, set_to_none: bool = True):
-        for p in self.params:
-            p.grad = None if set_to_none else (p.grad.zero_() if p.grad is not None else None)
-        self._have_coef = False
-        if self._acc:                # grad_accum > 1: the next optimizer step starts from zeroed accumulators
-            torch._foreach_zero_(self._acc)
-            self._acc_live.clear()
-            self._micro = 0
-
-    def _descriptors(self):
-        """Device descriptor table over the parameters that received a gradient (torch's AdamW and
-        clip_grad_norm_ skip `grad is None` the same way).  Under grad_accum > 1 the gradients are the fp32 accumulators."""
-        if self.grad_accum > 1:
-            sel, grads = self._accumulated()
-        else:
-            sel, grads = [], []
-            for i, p in enumerate(self.params):
-                if p.grad is None:
-                    continue
-                sel.append(i)
-                grads.append(p.grad if p.grad.is_contiguous() else p.grad.contiguous())
-        if not sel:
-            raise _lib.LcvError("FusedAdamWClip: no parameter has a gradient")
-        key = tuple(g.data_ptr() for g in grads) + tuple(sel)
-        if self._desc is None or key != self._desc_key:
-            rows, chunk = [], 0
-            for i, g in zip(sel, grads):
-                p, m, v = self.params[i], self.exp_avg[i], self.exp_avg_sq[i]
-                rows.append([p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), chunk])
-                chunk += (p.numel() + self.CHUNK - 1) // self.CHUNK
-            self._desc = torch.tensor(rows, dtype=torch.int64).to(self.params[0].device)
-            if self.master_weights:      # the low-word pointers, parallel to the table
-                self._low_desc = torch.tensor([self._low[i].data_ptr() for i in sel],
-                                              dtype=torch.int64).to(self.params[0].device)
-            if self._anchor:             # the base-word pointers
-                self._anchor_desc = torch.tensor([self._anchor[i].data_ptr() for i in sel],
-                                                 dtype=torch.int64).to(self.params[0].device)
-            if self.moments_8bit:        # and the block-scale pointers
-                self._scale_desc = torch.tensor([self._scales[i].data_ptr() for i in sel],
-                                                dtype=torch.int64).to(self.params[0].device)
-            self._total_chunks = chunk
-            self._n_active = len(sel)
-            self._desc_key = key
-            # one fp32 partial per chunk for the fixed-order clip (deterministic mode), sized with the table
-            self._det_ws = torch.empty((chunk,), dtype=F32, device=self.params[0].device) if _DETERMINISTIC else None
-        self._grads = grads  # keep alive until the launch
-        return self._desc
-
-    @property
-    def _grad_f32(self) -> bool:
-        """Whether the clip reads fp32 gradients: fp32 parameters, or the accumulators of grad_accum > 1 (an fp32 gradient's
-        norm is an fp32 number)."""
-        return self.f32 or self.grad_accum > 1
-
-    def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
-        self._ema_guard("clip_grad_norm_()")
-        d = self._descriptors()
-        if _DETERMINISTIC:
-            if getattr(self, "_det_ws", None) is None:      # the mode was switched on after the table was built
-                self._det_ws = torch.empty((self._total_chunks,), dtype=F32, device=self.params[0].device)
-            call("lcv_det_grad_norm_clip", _ptr(d), self._n_active, self._total_chunks, 1 if self._grad_f32 else 0,
-                 float(max_norm), _ptr(self._ws), _ptr(self._norm_coef), _ptr(self._det_ws), self._total_chunks * 4, _stream())
-        else:
-            call("lcv_grad_norm_clip", _ptr(d), self._n_active, self._total_chunks, 1 if self._grad_f32 else 0,
-                 float(max_norm), _ptr(self._ws), _ptr(self._norm_coef), _stream())
-        self._have_coef = True
-        return self._norm_coef[0]
-
-    @staticmethod
-    def joint_clip_grad_norm_(opts, max_norm: float) -> float:
-        """ONE clip over several optimizers' parameters (a bf16 list and an fp32 list under the same
-        `clip_grad_norm_(all_params, max_norm)`): per-tensor norms in each tensor's own dtype, the total over their fp32
-        stack, coefficient min(max_norm / (total + 1e-6), 1) — torch's rule for mixed dtypes.  Reads the per-tensor
-        squares back (one sync per step); used only by the norm + delta tuning option."""
-        if any(o.grad_accum > 1 for o in opts):
-            raise _lib.LcvError("joint_clip_grad_norm_: an optimizer with grad_accum > 1 cannot take part in a joint clip")
-        total_sq = 0.0
-        live = [o for o in opts if any(p.grad is not None for p in o.params)]
-        for o in live:
-            o.clip_grad_norm_(max_norm)                       # fills o._ws with the per-tensor sums of squares
-            sq = o._ws[:o._n_active * o.NORM_SLOTS].view(o._n_active, o.NORM_SLOTS).sum(1).sqrt()
-            if not o.f32:
-                sq = sq.to(BF16).to(F32)                      # a bf16 tensor's norm is a bf16 number
-            total_sq += float((sq * sq).sum().item())
-        total = total_sq ** 0.5
-        coef = min(max_norm / (total + 1e-6), 1.0)
-        for o in live:
-            o._norm_coef[0] = total
-            o._norm_coef[1] = coef
-        return total
-
-    def step(self):
-        self._ema_guard("step()")
-        d = self._descriptors()
-        g = self.param_groups[0]
-        self.step_count += 1
-        hyper = (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                 self.step_count)
-        coef = _ptr(self._norm_coef) if self._have_coef else None
-        # the entry point, the pointer tables that follow the descriptors, param_f32 (after the counts), grad_f32 (before the stream)
-        if self._anchor and self.moments_8bit:   # an anchor: decay toward the base words (include/lcv_hip_anchor.h)
-            name, tables, pf32, gf32 = "lcv_master_adamw8_step_anchor", "low scale anchor", (), ()
-        elif self._anchor:
-            name, tables, pf32, gf32 = "lcv_master_adamw_step_anchor", "low anchor", (), (1 if self.grad_accum > 1 else 0,)
-        elif self.moments_8bit:
-            name, tables, pf32, gf32 = "lcv_master_adamw8_step", "low scale", (), ()
-        elif self.grad_accum > 1:
-            name, tables, pf32, gf32 = "lcv_master_adamw_step_g32", "low", (), ()
-        elif self.master_weights:
-            name, tables, pf32, gf32 = "lcv_master_adamw_step", "low", (), ()
-        else:
-            name, tables, pf32, gf32 = "lcv_adamw_step", "", (1 if self.f32 else 0,), ()
-        call(name, _ptr(d), *(_ptr(getattr(self, f"_{t}_desc")) for t in tables.split()), self._n_active, self._total_chunks, *pf32,
-             coef, *hyper, *gf32, _stream())
-        self._have_coef = False
-        if self.weight_ema is not None:  # the average follows the masters this step left (include/lcv_hip_ema.h)
-            self._ema_update()
-        global PARAM_EPOCH
-        PARAM_EPOCH += 1
-
-
 # ------------------------------------------------------ frame evaluation ---
 def gaussian_window11(sigma: float = 1.5):
     """The 11 normalised fp32 taps torchmetrics builds for SSIM (`_gaussian(kernel_size=11, sigma=1.5)`): evaluated
@@ -1466,63 +985,10 @@ def gelu_tanh_bwd(x: torch.Tensor, dy: torch.Tensor) -> torch.Tensor:
     return dx
 
 
-class FusedSGDClip(FusedAdamWClip):
-    """clip_grad_norm_ + SGD(momentum=0, weight_decay).step over a parameter list in two launches — the default
-    optimizer of full-model TTA (lora_experiment/scripts/run_full_tta.py:138-144, 179-180).  No optimizer state, unless
-    `master_weights=True` adds the int16 low words of FusedAdamWClip's master-weight form (+2 B / parameter), and with it
-    `grad_accum=N` the fp32 accumulators of FusedAdamWClip's accumulation form (+4 B / parameter), or `anchor=[...]` the
-    decay toward those base words of FusedAdamWClip's anchor form (nothing allocated); `enable_weight_ema(beta)` keeps the fp32
-    average of FusedAdamWClip's form (+4 B / parameter)."""
-
-    def __init__(self, params, lr=1e-5, weight_decay=0.01, master_weights=False, *, grad_accum: int = 1, anchor=None):
-        self.params = [p for p in params]
-        if not self.params:
-            raise ValueError("optimizer got an empty parameter list")
-        dt = self.params[0].dtype
-        if dt not in (BF16, F32) or any(p.dtype != dt for p in self.params):
-            raise _lib.LcvError("FusedSGDClip: parameters must be all bf16 or all fp32")
-        self.f32 = dt == F32
-        self.param_groups = [dict(params=self.params, lr=lr, weight_decay=weight_decay)]
-        self._init_master(master_weights)
-        self._init_anchor(anchor)
-        self.exp_avg = self.params            # the descriptor table has moment slots; SGD never reads them
-        self.exp_avg_sq = self.params
-        self._scales = []
-        self._init_accum(grad_accum)
-        self.step_count = 0
-        dev = self.params[0].device
-        self._ws = torch.zeros(len(self.params) * self.NORM_SLOTS, dtype=F32, device=dev)
-        self._norm_coef = torch.zeros(2, dtype=F32, device=dev)
-        self._desc = None
-        self._desc_key = None
-        self._have_coef = False
-
-    def moment_tensors(self):
-        raise _lib.LcvError("FusedSGDClip: SGD (momentum 0) keeps no moments")
-
-    def state_bytes(self) -> int:
-        return 0
-
-    def step(self):
-        self._ema_guard("step()")
-        d = self._descriptors()
-        g = self.param_groups[0]
-        self.step_count += 1
-        hyper = (float(g["lr"]), float(g["weight_decay"]))
-        coef = _ptr(self._norm_coef) if self._have_coef else None
-        # as in FusedAdamWClip.step: the entry point, its pointer tables, param_f32, grad_f32
-        if self._anchor:                 # decay toward the base words (include/lcv_hip_anchor.h)
-            name, tables, pf32, gf32 = "lcv_master_sgd_step_anchor", "low anchor", (), (1 if self.grad_accum > 1 else 0,)
-        elif self.grad_accum > 1:
-            name, tables, pf32, gf32 = "lcv_master_sgd_step_g32", "low", (), ()
-        elif self.master_weights:
-            name, tables, pf32, gf32 = "lcv_master_sgd_step", "low", (), ()
-        else:
-            name, tables, pf32, gf32 = "lcv_sgd_step", "", (1 if self.f32 else 0,), ()
-        call(name, _ptr(d), *(_ptr(getattr(self, f"_{t}_desc")) for t in tables.split()), self._n_active, self._total_chunks, *pf32,
-             coef, *hyper, *gf32, _stream())
-        self._have_coef = False
-        if self.weight_ema is not None:  # the average follows the masters this step left (include/lcv_hip_ema.h)
-            self._ema_update()
-        global PARAM_EPOCH
-        PARAM_EPOCH += 1
+def __getattr__(name):
+    """`ops.FusedAdamWClip`, `ops.FusedSGDClip` and `ops.ema_beta`: the optimizers live in optim.py, which imports this
+    module, so the three names are looked up there on first use instead of at import (either module may be imported first)."""
+    if name in ("FusedAdamWClip", "FusedSGDClip", "ema_beta"):
+        from . import optim
+        return getattr(optim, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -39,12 +39,8 @@ def build_parser():
     p.add_argument("--weight-decay", type=float, default=0.01)
     p.add_argument("--max-grad-norm", type=float, default=1.0)
     p.add_argument("--optimizer", type=str, default="sgd", choices=["sgd", "adamw"])
-    p.add_argument("--master-weights", action="store_true",
-                   help="fp32 master weights: +2 B / parameter of low words, fp32 moments under adamw (include/lcv_hip_master.h)")
-    C.add_adam_8bit_arg(p)
-    C.add_grad_accum_arg(p)
-    C.add_decay_to_base_arg(p)
-    C.add_weight_ema_args(p)
+    C.add_optimizer_args(p, decay_to_base=True, master_weights_help="fp32 master weights: +2 B / parameter of low words, fp32 "
+                                                                    "moments under adamw (include/lcv_hip_master.h)")
     p.add_argument("--batch-videos", type=int, default=1)
     p.add_argument("--batch-method", type=str, default="similarity", choices=["similarity", "sequential"])
     p.add_argument("--retrieval-pool-dir", type=str, default=None)
@@ -53,7 +49,7 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    return C.parse_with_step_cache(build_parser(), argv, lambda p, a: C.parse_with_weight_ema(p, a, C.parse_with_decay_to_base))
+    return C.parse_with_step_cache(build_parser(), argv, C.parse_optimizer_args)
 
 
 def main(argv=None):
@@ -130,11 +126,9 @@ def main(argv=None):
                                                warmup_steps=args.warmup_steps, weight_decay=args.weight_decay,
                                                max_grad_norm=args.max_grad_norm, device=device, dtype=torch.bfloat16,
                                                early_stopper=es, optimizer_type=args.optimizer, train_latents_variants=variants,
-                                               master_weights=args.master_weights, moments_8bit=args.adam_8bit,
-                                               grad_accum=args.grad_accum,
                                                # the anchors are the reset's base copy: nothing more is allocated
-                                               **(dict(decay_to_base=True, base_state=base_state) if args.decay_to_base else {}),
-                                               **C.weight_ema_kwargs(args))
+                                               **({"base_state": base_state} if args.decay_to_base else {}),
+                                               **C.optimizer_kwargs(args))
             result = {"idx": idx, "video_name": e["name"], "video_path": e["path"], "caption": blob.get("caption", ""),
                       "train_time": tr["train_time"], "es_check_time": tr.get("es_check_time", 0.0),
                       "final_loss": tr["losses"][-1] if tr["losses"] else None, "num_train_steps": len(tr["losses"]),

@@ -65,11 +65,8 @@ def build_parser():
     p.add_argument("--warmup-steps", type=int, default=3)
     p.add_argument("--weight-decay", type=float, default=0.01)
     p.add_argument("--max-grad-norm", type=float, default=1.0)
-    p.add_argument("--master-weights", action="store_true",
-                   help="fp32 master weights for the bf16 adapters (include/lcv_hip_master.h); both LoRA implementations")
-    C.add_adam_8bit_arg(p)
-    C.add_grad_accum_arg(p)
-    C.add_weight_ema_args(p)
+    C.add_optimizer_args(p, master_weights_help="fp32 master weights for the bf16 adapters (include/lcv_hip_master.h); both "
+                                                "LoRA implementations")
     C.add_step_cache_args(p)
     C.add_solver_arg(p)
     p.add_argument("--max-videos", type=int, default=100)
@@ -98,7 +95,7 @@ def build_parser():
 
 
 def parse_args(argv=None):
-    return C.parse_with_step_cache(build_parser(), argv, C.parse_with_weight_ema)
+    return C.parse_with_step_cache(build_parser(), argv, C.parse_optimizer_args)
 
 
 def main(argv=None):
@@ -207,9 +204,7 @@ def main(argv=None):
                                                warmup_steps=args.warmup_steps, weight_decay=args.weight_decay,
                                                max_grad_norm=args.max_grad_norm, device=device, dtype=torch.bfloat16,
                                                early_stopper=es, lora_param_fn=get_params, train_latents_variants=variants,
-                                               master_weights=args.master_weights, moments_8bit=args.adam_8bit,
-                                               grad_accum=args.grad_accum,
-                                               **C.weight_ema_kwargs(args))
+                                               **C.optimizer_kwargs(args))
             result = {"idx": idx, "video_name": e["name"], "video_path": e["path"], "caption": blob.get("caption", ""),
                       "train_time": tr["train_time"], "es_check_time": tr.get("es_check_time", 0.0),
                       "final_loss": tr["losses"][-1] if tr["losses"] else None, "num_train_steps": len(tr["losses"]),

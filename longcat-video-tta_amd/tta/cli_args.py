@@ -79,58 +79,20 @@ def add_clip_gate_args(parser):
     return parser
 
 
-def add_adam_8bit_arg(parser):
+def add_optimizer_args(parser, *, master_weights_help, decay_to_base=False):
+    """The optimizer options of the adapting runners; `--master-weights` with the runner's own help wording, `--decay-to-base`
+    only for the runners whose loop takes it."""
+    parser.add_argument("--master-weights", action="store_true", help=master_weights_help)
     parser.add_argument("--adam-8bit", action="store_true",
                         help="with --master-weights: AdamW moments in 1 B each plus block scales, about 2.016 B / parameter "
                              "instead of 8 (include/lcv_hip_moments8.h)")
-
-
-def parse_with_adam_8bit(parser, argv=None):
-    """parse_args, then the two refusals of --adam-8bit as the parser's own one-line errors (exit status 2)."""
-    args = parser.parse_args(argv)
-    if args.adam_8bit and not args.master_weights:
-        parser.error("--adam-8bit needs --master-weights (the 8-bit moments exist for the master-weight AdamW step only)")
-    if args.adam_8bit and getattr(args, "optimizer", "adamw") != "adamw":
-        parser.error("--adam-8bit needs --optimizer adamw (SGD keeps no moments)")
-    return args
-
-
-def add_grad_accum_arg(parser):
     parser.add_argument("--grad-accum", type=int, default=1, metavar="N",
                         help="with --master-weights: every optimizer step is the mean of N micro-steps (own sigma, noise and "
                              "variant draw each), summed in fp32 accumulators, +4 B / parameter (include/lcv_hip_accum.h)")
-
-
-def parse_with_grad_accum(parser, argv=None):
-    """parse_with_adam_8bit, then the refusals of --grad-accum as the parser's own one-line errors (exit status 2)."""
-    args = parse_with_adam_8bit(parser, argv)
-    if args.grad_accum < 1:
-        parser.error(f"--grad-accum must be at least 1, got {args.grad_accum}")
-    if args.grad_accum > 1 and not args.master_weights:
-        parser.error("--grad-accum above 1 needs --master-weights (the fp32-gradient steps exist for the master-weight form only)")
-    if args.grad_accum > 1 and args.adam_8bit:
-        parser.error("--grad-accum above 1 cannot be combined with --adam-8bit (the 8-bit-moment step reads bf16 gradients)")
-    if args.grad_accum > 1 and getattr(args, "also_tune_delta", False):
-        parser.error("--grad-accum above 1 cannot be combined with --also-tune-delta (the fp32 delta vector has no accumulators)")
-    return args
-
-
-def add_decay_to_base_arg(parser):
-    parser.add_argument("--decay-to-base", action="store_true",
-                        help="with --master-weights: the weight decay pulls toward the base weights instead of toward zero, and "
-                             "every result row carries drift_norm, the distance from them (include/lcv_hip_anchor.h)")
-
-
-def parse_with_decay_to_base(parser, argv=None):
-    """parse_with_grad_accum, then the refusal of --decay-to-base as the parser's own one-line error (exit status 2)."""
-    args = parse_with_grad_accum(parser, argv)
-    if args.decay_to_base and not args.master_weights:
-        parser.error("--decay-to-base needs --master-weights (a pull of lr * wd * (w - w0) is far below half a bf16 ulp; the "
-                     "anchor steps exist for the master-weight form only)")
-    return args
-
-
-def add_weight_ema_args(parser):
+    if decay_to_base:
+        parser.add_argument("--decay-to-base", action="store_true",
+                            help="with --master-weights: the weight decay pulls toward the base weights instead of toward zero, and "
+                                 "every result row carries drift_norm, the distance from them (include/lcv_hip_anchor.h)")
     parser.add_argument("--weight-ema", type=float, default=None, metavar="BETA",
                         help="with --master-weights: keep an fp32 exponential moving average of the weights over the optimizer "
                              "steps (e = BETA * e + (1 - BETA) * w, +4 B / parameter, include/lcv_hip_ema.h); the early stopper "
@@ -141,23 +103,52 @@ def add_weight_ema_args(parser):
                              "at the base weights does not lag a short run")
 
 
-def parse_with_weight_ema(parser, argv=None, parse=None):
-    """`parse` (default parse_with_grad_accum), then the refusals of --weight-ema as the parser's own one-line errors (exit
-    status 2)."""
-    args = (parse or parse_with_grad_accum)(parser, argv)
-    if args.weight_ema_warmup and args.weight_ema is None:
-        parser.error("--weight-ema-warmup needs --weight-ema BETA")
-    if args.weight_ema is None:
-        return args
-    if not args.master_weights:
-        parser.error("--weight-ema needs --master-weights (an increment (1 - BETA) * (w - e) is far below half a bf16 ulp; the "
-                     "average is kept in fp32 beside the master weights only)")
-    if not 0.0 <= args.weight_ema < 1.0:         # a NaN fails both
-        parser.error(f"--weight-ema BETA must be in [0, 1), got {args.weight_ema}")
-    if getattr(args, "also_tune_delta", False):
-        parser.error("--weight-ema cannot be combined with --also-tune-delta (the fp32 delta vector has no master-weight form "
-                     "to average beside)")
+def parse_optimizer_args(parser, argv=None):
+    """parse_args, then the refusals of the optimizer options as the parser's own one-line errors (exit status 2), in this
+    order: --adam-8bit, --grad-accum, --decay-to-base, --weight-ema.  `--optimizer`, `--also-tune-delta` and `--decay-to-base`
+    count as adamw, off and off for a parser without them."""
+    args = parser.parse_args(argv)
+    master, accum, tune_delta = args.master_weights, args.grad_accum, getattr(args, "also_tune_delta", False)
+    refusals = [
+        (args.adam_8bit and not master,
+         "--adam-8bit needs --master-weights (the 8-bit moments exist for the master-weight AdamW step only)"),
+        (args.adam_8bit and getattr(args, "optimizer", "adamw") != "adamw",
+         "--adam-8bit needs --optimizer adamw (SGD keeps no moments)"),
+        (accum < 1, f"--grad-accum must be at least 1, got {accum}"),
+        (accum > 1 and not master,
+         "--grad-accum above 1 needs --master-weights (the fp32-gradient steps exist for the master-weight form only)"),
+        (accum > 1 and args.adam_8bit,
+         "--grad-accum above 1 cannot be combined with --adam-8bit (the 8-bit-moment step reads bf16 gradients)"),
+        (accum > 1 and tune_delta,
+         "--grad-accum above 1 cannot be combined with --also-tune-delta (the fp32 delta vector has no accumulators)"),
+        (getattr(args, "decay_to_base", False) and not master,
+         "--decay-to-base needs --master-weights (a pull of lr * wd * (w - w0) is far below half a bf16 ulp; the "
+         "anchor steps exist for the master-weight form only)"),
+        (args.weight_ema_warmup and args.weight_ema is None, "--weight-ema-warmup needs --weight-ema BETA"),
+    ]
+    if args.weight_ema is not None:
+        refusals += [
+            (not master,
+             "--weight-ema needs --master-weights (an increment (1 - BETA) * (w - e) is far below half a bf16 ulp; the "
+             "average is kept in fp32 beside the master weights only)"),
+            (not 0.0 <= args.weight_ema < 1.0,         # a NaN fails both
+             f"--weight-ema BETA must be in [0, 1), got {args.weight_ema}"),
+            (tune_delta,
+             "--weight-ema cannot be combined with --also-tune-delta (the fp32 delta vector has no master-weight form "
+             "to average beside)"),
+        ]
+    for refused, message in refusals:
+        if refused:
+            parser.error(message)
     return args
+
+
+def optimizer_kwargs(args) -> dict:
+    """The loop functions' keywords for the optimizer options; a flag the parser does not have contributes nothing."""
+    kw = {"master_weights": args.master_weights, "moments_8bit": args.adam_8bit, "grad_accum": args.grad_accum}
+    if hasattr(args, "decay_to_base"):
+        kw["decay_to_base"] = args.decay_to_base
+    return {**kw, **weight_ema_kwargs(args)}
 
 
 def weight_ema_kwargs(args) -> dict:

@@ -75,8 +75,7 @@ def _anchors(dit: nn.Module, base_state: Optional[Dict[str, torch.Tensor]]) -> L
 
 
 def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper, optimizer_type,
-         master_weights=False, moments_8bit=False, grad_accum=1, decay_to_base=False, base_state=None, weight_ema=None,
-         ema_warmup=False):
+         *, master_weights, moments_8bit, grad_accum, decay_to_base, base_state, weight_ema, ema_warmup):
     params = _trainable(dit)
     # `decay_to_base`: the weight decay pulls toward the base words (include/lcv_hip_anchor.h), which are the caller's
     # `base_state` entries or, without one, +2 B / parameter of clones; a `base_state` alone only measures the drift
@@ -109,7 +108,8 @@ def finetune_full_on_conditioning(dit: nn.Module, cond_latents: torch.Tensor, tr
                                   grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
     return _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper,
-                optimizer_type, master_weights, moments_8bit, grad_accum, decay_to_base, base_state, weight_ema, ema_warmup)
+                optimizer_type, master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
+                decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup)
 
 
 def finetune_full_batch(dit: nn.Module, batch_data: List[Dict], num_steps: int = 10, lr: float = 1e-5, warmup_steps: int = 2,
@@ -120,4 +120,5 @@ def finetune_full_batch(dit: nn.Module, batch_data: List[Dict], num_steps: int =
                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Round-robin over the eval video and its retrieved neighbours (run_full_tta.py:230-306); no early stopping."""
     return _run(dit, _RoundRobin(batch_data, device), num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype,
-                None, optimizer_type, master_weights, moments_8bit, grad_accum, decay_to_base, base_state, weight_ema, ema_warmup)
+                None, optimizer_type, master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
+                decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup)

@@ -216,7 +216,7 @@ def test_constructors_take_anchor_keyword_only_and_refuse_it_without_master_weig
     with pytest.raises(LcvError, match="GPU"):                       # the existing refusal fires first, with its message
         make(bf, master_weights=True, anchor=[torch.zeros(8, dtype=torch.bfloat16)])
     opt = make(bf)                                                   # no anchor: today's optimizer, nothing held
-    assert list(opt._anchor) == [] and opt._drift is None and hasattr(opt, "drift_norm")
+    assert list(opt._anchor) == [] and "drift" not in opt._tables and hasattr(opt, "drift_norm")
     with pytest.raises(LcvError, match="needs an anchor"):
         opt.drift_norm()
     with pytest.raises(LcvError, match="anchor has 2 tensors for 1"):

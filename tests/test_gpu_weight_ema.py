@@ -153,8 +153,7 @@ KINDS = [("sgd", 1, None), ("adamw", 1, None), ("adamw8", 1, None), ("adamw", D.
 def _enable(opt, beta, warmup):
     """enable_weight_ema, then the offset tensor's average moved into an offset view like its other arrays."""
     opt.enable_weight_ema(beta, warmup)
-    opt._ema[VIEW] = D._offset_view(opt._ema[VIEW])
-    opt._ema_table_cache = None
+    opt._ema[VIEW] = D._offset_view(opt._ema[VIEW])     # the average table is keyed on these pointers: it is built again
     opt.ema_reset()
     assert opt.ema_tensors()[VIEW].data_ptr() % 16 == 4
 
