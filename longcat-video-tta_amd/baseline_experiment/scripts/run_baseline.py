@@ -43,6 +43,7 @@ def build_parser():
     p.add_argument("--device", type=str, default="cuda")
     C.add_step_cache_args(p)
     C.add_solver_arg(p)
+    C.add_cfg_reuse_args(p)
     return p
 
 
@@ -76,7 +77,7 @@ def main(argv=None):
             out, dt = R.generate_continuation(pipe, blob, args, idx, device, num_frames=num_frames, entry=e)
             row = {"idx": idx, "index": idx, "filename": e["name"], "caption": blob.get("caption", ""), "psnr": None,
                    "ssim": None, "lpips": None, "resolution": args.resolution, "inference_time_s": round(dt, 2),
-                   **C.step_cache_result(blob)}
+                   **C.step_cache_result(blob), **C.cfg_reuse_result(blob)}
             if pipe.vae is not None:
                 t1 = time.time()
                 frames = pipe.decode_to_frames(out)
@@ -129,6 +130,10 @@ def main(argv=None):
                 "step_cache_per_video": {r["filename"]: r["step_cache"] for r in merged if "step_cache" in r}}
                if C.step_cache_record(args) else {}),
             **C.solver_record(args),       # --solver: flat, and only when it is not euler
+            # --cfg-reuse: the flags flat and every video's statistics, when the flag is set
+            **({**C.cfg_reuse_record(args),
+                "cfg_reuse_per_video": {r["filename"]: r["cfg_reuse"] for r in merged if "cfg_reuse" in r}}
+               if C.cfg_reuse_record(args) else {}),
         }
         with open(out_dir / "summary.json", "w") as f:
             json.dump(summary, f, indent=2)

@@ -152,6 +152,13 @@ _SIGNATURES_SOLVER = {
     "lcv_cfg_lms_step": [P, P, P, P, P, P, P, I64, I64, F32, F32, F32, F32, I, I, I, P],
 }
 
+# include/lcv_hip_cfgreuse.h (a header of its own: the guidance reuse of the CFG denoise loop): store takes (cond, uncond, delta, ws,
+# out, B, n, float guidance, int use_zero_star), apply (cond, delta, v, B, n); both return int
+_SIGNATURES_CFGREUSE = {
+    "lcv_cfg_delta_store": [P, P, P, P, P, I64, I64, F32, I, P],
+    "lcv_cfg_delta_apply": [P, P, P, I64, I64, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -210,7 +217,8 @@ def load():
     for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
                        + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())
                        + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())
-                       + list(_SIGNATURES_STEPCACHE.items()) + list(_SIGNATURES_SOLVER.items())):
+                       + list(_SIGNATURES_STEPCACHE.items()) + list(_SIGNATURES_SOLVER.items())
+                       + list(_SIGNATURES_CFGREUSE.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

@@ -401,6 +401,55 @@ def cfg_lms_step(cond: torch.Tensor, uncond: Optional[torch.Tensor], x: torch.Te
          w[0], w[1], w[2], terms, 1 if negate else 0, 1 if zero_star else 0, _stream())
 
 
+# the guidance reuse of the CFG denoise loop (include/lcv_hip_cfgreuse.h; the schedule lives in longcat_video/cfg_reuse.py)
+_CFGREUSE_WS = {}    # (device index, B) -> the [2, B, 256, 2] partial sums of lcv_cfg_delta_store (kept alive here)
+
+
+def cfg_reuse_workspace(B: int, device) -> torch.Tensor:
+    """The zero-star partial pairs, then the drift partial pairs: 256 fp32 pairs per sample each, cached per (device, B)."""
+    key = (torch.device(device).index, int(B))
+    ws = _CFGREUSE_WS.get(key)
+    if ws is None:
+        ws = _CFGREUSE_WS[key] = torch.empty((2, int(B), 256, 2), dtype=F32, device=device)
+    return ws
+
+
+def _cfgreuse_req(name: str, *tensors) -> None:
+    numel = tensors[0].numel()
+    for t in tensors:
+        _req(t, F32, name)
+        if not t.is_contiguous() or t.numel() != numel:
+            raise _lib.LcvError(f"{name}: needs contiguous fp32 tensors of one size, got {tuple(t.shape)} against "
+                                f"{tuple(tensors[0].shape)}")
+
+
+def cfg_delta_store(cond: torch.Tensor, uncond: torch.Tensor, delta: torch.Tensor, guidance: float, zero_star: bool = True,
+                    out: Optional[torch.Tensor] = None) -> None:
+    """delta = v - cond, v the guided output of (cond, uncond) as lcv_cfg_lms_step forms it (before any sign), over [B, ...]
+    fp32 tensors; `delta` is written in place.  With `out` ([B, 2] fp32) the old delta is read first and out[b] = (sum |new -
+    old|, sum |old|) in a fixed order.  Nothing is synchronised."""
+    _cfgreuse_req("cfg_delta_store", cond, uncond, delta)
+    B = delta.shape[0]
+    n = delta.numel() // max(B, 1)
+    if out is not None:
+        _req(out, F32, "cfg_delta_store.out")
+        if out.numel() != 2 * B or not out.is_contiguous():
+            raise _lib.LcvError(f"cfg_delta_store: out needs {2 * B} contiguous fp32 words, got {out.numel()}")
+    ws = cfg_reuse_workspace(B, delta.device) if (zero_star or out is not None) else None
+    call("lcv_cfg_delta_store", _ptr(cond), _ptr(uncond), _ptr(delta), _ptr(ws), _ptr(out), B, n, float(guidance),
+         1 if zero_star else 0, _stream())
+
+
+def cfg_delta_apply(cond: torch.Tensor, delta: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = cond + delta, a reuse step's guided output; `out` may be cond (default: a new tensor)."""
+    if out is None:
+        out = torch.empty_like(cond)
+    _cfgreuse_req("cfg_delta_apply", cond, delta, out)
+    B = cond.shape[0]
+    call("lcv_cfg_delta_apply", _ptr(cond), _ptr(delta), _ptr(out), B, cond.numel() // max(B, 1), _stream())
+    return out
+
+
 # the first-block step cache of the denoise loop (include/lcv_hip_stepcache.h; the policy lives in longcat_video/step_cache.py)
 _STEPCACHE_CHUNK = 2048
 _STEPCACHE_WS = {}   # (device index, rows, n) -> the partial-sum workspace of lcv_stepcache_diff (kept alive here)

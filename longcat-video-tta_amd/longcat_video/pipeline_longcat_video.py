@@ -57,6 +57,7 @@ class LongCatVideoPipeline:
         self.use_zero_star = True
         self._kv_cache = None
         self.last_step_cache_stats = None      # StepCache.stats() of the last denoise() that had one
+        self.last_cfg_reuse_stats = None       # GuidanceReuse.stats() of the last denoise() that had one
 
     def to(self, device):
         self.device = torch.device(device)
@@ -101,7 +102,7 @@ class LongCatVideoPipeline:
                 negative_embeds: Optional[torch.Tensor] = None, negative_mask: Optional[torch.Tensor] = None,
                 num_cond_latents: int = 0, num_inference_steps: int = 50, guidance_scale: float = 4.0,
                 use_kv_cache: bool = True, step_callback=None, start_step: int = 0, stop_step: Optional[int] = None,
-                step_cache=None, solver=None):
+                step_cache=None, solver=None, cfg_reuse=None):
         """latents fp32 [1, C, T, h, w]; the first `num_cond_latents` frames are clean conditioning frames.
         Returns the fully denoised latents (fp32, conditioning frames untouched).
         `step_cache`: a threshold or a `StepCache` (longcat_video/step_cache.py): steps whose first-block residual is within
@@ -111,7 +112,23 @@ class LongCatVideoPipeline:
         `solver`: None or "euler" (the explicit Euler step, the default), "ab2" / "ab2c" or a `MultistepSolver`
         (longcat_video/solver.py): a second-order multistep rule over the velocities of the one or two previous steps takes the
         place of the Euler update; no further forward, one latent-sized fp32 buffer per kept velocity.  The history restarts at
-        every call, so a denoise split by `start_step` / `stop_step` is not bit-equal to one call under these rules."""
+        every call, so a denoise split by `start_step` / `stop_step` is not bit-equal to one call under these rules.
+        `cfg_reuse`: an interval K or a `GuidanceReuse` (longcat_video/cfg_reuse.py): every K-th step, the first and the last
+        run both rows as today and store the guidance correction v - c; the steps between run the prompt row alone at batch 1
+        and add the stored correction back before the unguided update.  Needs guidance; not with a step cache or sequence
+        parallelism; no hipGraph is captured while it is attached (the batch changes); a split denoise restarts the schedule.
+        The statistics are left in `self.last_cfg_reuse_stats`."""
+        reuse = None
+        self.last_cfg_reuse_stats = None
+        if cfg_reuse is not None:
+            from .cfg_reuse import GuidanceReuse
+            reuse = cfg_reuse if isinstance(cfg_reuse, GuidanceReuse) else GuidanceReuse(cfg_reuse)
+            if not (guidance_scale > 1.0 and negative_embeds is not None):
+                raise ValueError("cfg_reuse needs guidance: guidance_scale > 1 and negative embeddings")
+            if step_cache is not None:
+                raise ValueError("cfg_reuse cannot be combined with a step cache: its buffers are per batch shape")
+            if getattr(self.dit, "_sp_group", None) is not None:
+                raise ValueError("cfg_reuse has no sequence-parallel form")
         lms = None
         if solver is not None and solver != "euler":
             lms = solver if isinstance(solver, MultistepSolver) else MultistepSolver(solver)
@@ -152,7 +169,8 @@ class LongCatVideoPipeline:
         graph = None
         n_tok = Bm * T_in * (work.shape[3] // 2) * (work.shape[4] // 2)
         want_graph = (os.environ.get("LCV_DENOISE_GRAPH") == "1" or n_tok <= int(os.environ.get("LCV_DENOISE_GRAPH_TOKENS", "0"))) \
-            and not torch.is_grad_enabled() and getattr(dit, "_sp_group", None) is None and stop - start_step >= 3 and cache is None
+            and not torch.is_grad_enabled() and getattr(dit, "_sp_group", None) is None and stop - start_step >= 3 and cache is None \
+            and reuse is None
 
         extra = {} if cache is None else {"step_cache": cache}
 
@@ -163,8 +181,36 @@ class LongCatVideoPipeline:
             return dit(hidden_states=x_in, timestep=ts, encoder_hidden_states=emb, encoder_attention_mask=mask,
                        num_cond_latents=ncl, **extra)
         x_static = ts_static = pred_static = None
+        if reuse is not None:
+            reuse.begin(start_step, stop)
+
+            def unguided(v, x, i, dt):                  # a reuse step's update: v is already guided
+                if lms is not None:
+                    lms.step(v, None, x, i, sched._sigmas_host, guidance_scale, self.negate_pred, self.use_zero_star)
+                else:
+                    ops.euler_step(v, x, dt, negate=self.negate_pred)
         for i in range(start_step, stop):
             t = timesteps[i]
+            if reuse is not None and not reuse.is_full(i):
+                # a reuse step: the prompt row alone at batch 1 (the conditioning frames' KV cache is built at batch 1 and
+                # shared by the rows), v^ = c + delta over the model output, then the unguided update
+                ts = torch.full((1, T_in), t, device=dev, dtype=torch.bfloat16)
+                if kv is None and ncl > 0:
+                    ts[:, :ncl] = 0
+                more = {} if kv is None else {"kv_cache_dict": kv}
+                pred = dit(hidden_states=work.to(torch.bfloat16), timestep=ts, encoder_hidden_states=prompt_embeds,
+                           encoder_attention_mask=prompt_mask, num_cond_latents=ncl, **more)
+                dt = sched.dt(i)
+                if kv is None and ncl > 0:
+                    tgt = work[:, :, ncl:]
+                    new = tgt.contiguous()
+                    unguided(reuse.apply(pred[:, :, ncl:].contiguous()), new, i, dt)
+                    tgt.copy_(new)
+                else:
+                    unguided(reuse.apply(pred), work, i, dt)
+                if step_callback is not None:
+                    step_callback(i, work)
+                continue
             if graph is not None:
                 x_static.copy_(work.expand_as(x_static) if do_cfg else work)       # fp32 -> bf16 into the captured input
                 ts_static.fill_(t)
@@ -206,9 +252,16 @@ class LongCatVideoPipeline:
                          guidance_scale, self.negate_pred, self.use_zero_star)
             else:
                 self._apply_step(pred[1:2] if do_cfg else pred, pred[0:1] if do_cfg else None, work, guidance_scale, dt)
+            if reuse is not None:                       # a full step: today's step above, then delta = v - c of its two rows
+                if kv is None and ncl > 0:
+                    reuse.store(sl(pred[1:2]), sl(pred[0:1]), guidance_scale, self.use_zero_star, i)
+                else:
+                    reuse.store(pred[1:2], pred[0:1], guidance_scale, self.use_zero_star, i)
             if step_callback is not None:
                 step_callback(i, work)
         sched._step_index = stop
+        if reuse is not None:
+            self.last_cfg_reuse_stats = reuse.stats()
         if cache is not None:
             self.last_step_cache_stats = cache.stats()
         if cond is not None:
@@ -250,7 +303,7 @@ class LongCatVideoPipeline:
                     num_inference_steps: int = 50, guidance_scale: float = 4.0, generator=None,
                     use_kv_cache: bool = True, offload_kv_cache: bool = False, prompt_embeds=None,
                     prompt_mask=None, negative_embeds=None, negative_mask=None, output_type: str = "np",
-                    step_cache=None, solver=None, **kw):
+                    step_cache=None, solver=None, cfg_reuse=None, **kw):
         """Video continuation: `video` is a list of PIL frames (or a [T,H,W,3] uint8/float array); the last
         `num_cond_frames` are VAE-encoded as clean conditioning latents."""
         H, W = RESOLUTIONS[resolution]
@@ -270,7 +323,8 @@ class LongCatVideoPipeline:
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=ncl, num_inference_steps=num_inference_steps,
                            guidance_scale=guidance_scale, use_kv_cache=use_kv_cache,
                            **({} if step_cache is None else {"step_cache": step_cache}),
-                           **({} if solver is None else {"solver": solver}))
+                           **({} if solver is None else {"solver": solver}),
+                           **({} if cfg_reuse is None else {"cfg_reuse": cfg_reuse}))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]
@@ -280,7 +334,7 @@ class LongCatVideoPipeline:
                      width: int = 832, num_frames: int = 93, num_inference_steps: int = 50,
                      guidance_scale: float = 4.0, generator=None, prompt_embeds=None, prompt_mask=None,
                      negative_embeds=None, negative_mask=None, output_type: str = "np", step_cache=None,
-                     solver=None, **kw):
+                     solver=None, cfg_reuse=None, **kw):
         do_cfg = guidance_scale > 1.0
         pe, pm, ne, nm = self._prep_text(prompt, negative_prompt, prompt_embeds, prompt_mask, negative_embeds,
                                          negative_mask, do_cfg)
@@ -290,7 +344,8 @@ class LongCatVideoPipeline:
         noise = torch.randn((1, C, T_lat, h, w), generator=generator, device=self.device, dtype=torch.float32)
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=0, num_inference_steps=num_inference_steps,
                            guidance_scale=guidance_scale, **({} if step_cache is None else {"step_cache": step_cache}),
-                           **({} if solver is None else {"solver": solver}))
+                           **({} if solver is None else {"solver": solver}),
+                           **({} if cfg_reuse is None else {"cfg_reuse": cfg_reuse}))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]

@@ -91,7 +91,7 @@ def main(argv=None):
             "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                            "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
                            "resolution": args.resolution, **C.step_cache_record(args),
-                           **C.solver_record(args)},
+                           **C.solver_record(args), **C.cfg_reuse_record(args)},
             "seed": args.seed, "max_videos": args.max_videos,
             **{k: v for k, v in gate.items() if k != "clip_gate_stats"},
             "clip_gate": {"enabled": args.clip_gate_enabled, "threshold": args.clip_gate_threshold,
@@ -148,6 +148,7 @@ def main(argv=None):
                         result["output_path"] = R.save_frames(pipe, out, os.path.join(videos_dir, f"{e['name']}_full"), frames=frames)
                 result["gen_time"] = gen_time
                 result.update(C.step_cache_result(blob))
+                result.update(C.cfg_reuse_result(blob))
             result["total_time"] = tr["train_time"] + gen_time
             print(f"  [{idx}] {e['name']}: train {tr['train_time']:.1f}s loss {result['final_loss']}"
                   + (f" gen {gen_time:.1f}s" if not args.skip_generation else ""))

@@ -69,6 +69,7 @@ def build_parser():
                                                 "LoRA implementations")
     C.add_step_cache_args(p)
     C.add_solver_arg(p)
+    C.add_cfg_reuse_args(p)
     p.add_argument("--max-videos", type=int, default=100)
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--device", type=str, default="cuda")
@@ -166,7 +167,7 @@ def main(argv=None):
             "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                            "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
                            "resolution": args.resolution, **C.step_cache_record(args),
-                           **C.solver_record(args)},
+                           **C.solver_record(args), **C.cfg_reuse_record(args)},
             "seed": args.seed, "max_videos": args.max_videos, "clip_gate_enabled": args.clip_gate_enabled,
             "clip_gate_threshold": args.clip_gate_threshold, "clip_gate_backend": args.clip_gate_backend,
             "clip_gate_model": args.clip_gate_model, "clip_gate_sample_frames": args.clip_gate_sample_frames,
@@ -218,6 +219,7 @@ def main(argv=None):
                 out, gen_only = generate_continuation(pipe, blob, args, idx, device, entry=e)   # cond encode + denoise
                 result["cond_source"] = blob.get("_cond_source")
                 result.update(C.step_cache_result(blob))
+                result.update(C.cfg_reuse_result(blob))
                 t0 = time.time() - gen_only
                 frames = pipe.decode_to_frames(out) if pipe.vae is not None else None
                 torch.cuda.synchronize()

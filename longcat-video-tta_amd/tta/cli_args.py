@@ -198,6 +198,7 @@ def parse_with_step_cache(parser, argv=None, parse=None):
     args = parse(parser, argv) if parse is not None else parser.parse_args(argv)
     if args.step_cache_max_skip is not None and args.step_cache is None:
         parser.error("--step-cache-max-skip needs --step-cache THRESH")
+    check_cfg_reuse_args(parser, args)
     return args
 
 
@@ -244,6 +245,64 @@ def solver_record(args) -> dict:
     euler."""
     kind = solver_from_args(args)
     return {} if kind is None else {"solver": kind}
+
+
+def _cfg_reuse_int(name: str, least: int):
+    def convert(text: str) -> int:
+        try:
+            v = int(text)
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"not an integer: {text!r}")
+        if v < least:
+            raise argparse.ArgumentTypeError(f"{name} must be >= {least}, got {text}")
+        return v
+    return convert
+
+
+def add_cfg_reuse_args(parser):
+    parser.add_argument("--cfg-reuse", type=_cfg_reuse_int("K", 1), default=None, metavar="K",
+                        help="guidance reuse of the CFG denoise loop (include/lcv_hip_cfgreuse.h, longcat_video/cfg_reuse.py): "
+                             "every K-th step, the first and the last run both rows and store the guidance correction; the "
+                             "steps between run the prompt row alone at batch 1 and add the stored correction back; 1 runs "
+                             "every step in full and records the drift trace (calibration); no interval is recommended")
+    parser.add_argument("--cfg-reuse-warmup", type=_cfg_reuse_int("W", 0), default=None, metavar="W",
+                        help="with --cfg-reuse: the first W steps run in full (default 0)")
+
+
+def check_cfg_reuse_args(parser, args) -> None:
+    """The refusals of --cfg-reuse as the parser's own one-line error (exit status 2); K < 1 and W < 0 are refused by the
+    arguments' types the same way.  Called from `parse_with_step_cache`, which every runner parses through."""
+    if getattr(args, "cfg_reuse_warmup", None) is not None and getattr(args, "cfg_reuse", None) is None:
+        parser.error("--cfg-reuse-warmup needs --cfg-reuse K")
+    if getattr(args, "cfg_reuse", None) is None:
+        return
+    if getattr(args, "step_cache", None) is not None:
+        parser.error("--cfg-reuse cannot be combined with --step-cache (the cache's buffers are per batch shape)")
+    if not args.guidance_scale > 1.0:
+        parser.error(f"--cfg-reuse needs guidance: --guidance-scale must be > 1, got {args.guidance_scale}")
+
+
+def cfg_reuse_from_args(args):
+    """A fresh `GuidanceReuse` for one continuation, or None when the flag is absent (then nothing is imported or allocated)."""
+    K = getattr(args, "cfg_reuse", None)
+    if K is None:
+        return None
+    from longcat_video.cfg_reuse import GuidanceReuse
+    return GuidanceReuse(K, warmup=getattr(args, "cfg_reuse_warmup", None) or 0)
+
+
+def cfg_reuse_record(args) -> dict:
+    """What config.json (`generation`) and the flat summary.json of the runners without one record of --cfg-reuse; nothing
+    when the flag is absent."""
+    if getattr(args, "cfg_reuse", None) is None:
+        return {}
+    return {"cfg_reuse": args.cfg_reuse, "cfg_reuse_warmup": getattr(args, "cfg_reuse_warmup", None) or 0}
+
+
+def cfg_reuse_result(blob) -> dict:
+    """The per-video `cfg_reuse` entry (`GuidanceReuse.stats()`, left in the blob by generate_continuation); nothing without the
+    flag."""
+    return {"cfg_reuse": blob["_cfg_reuse"]} if "_cfg_reuse" in blob else {}
 
 
 def normalize_tta_frame_args(args):

@@ -36,6 +36,7 @@ def add_common_args(p):
     p.add_argument("--no-save-videos", action="store_true")
     C.add_step_cache_args(p)
     C.add_solver_arg(p)
+    C.add_cfg_reuse_args(p)
 
 
 def add_shared_groups(p, clip_gate: bool = True):
@@ -250,7 +251,7 @@ def generate_continuation(pipe, blob, args, idx, device, num_frames=None, entry=
     """KV-cached CFG continuation from the clean conditioning latents (`generate_video_continuation`, common.py:566-611).
     The conditioning encode is inside the timed region, as in the reference.  Returns (denoised latents, seconds); the
     origin of the conditioning latents is left in `blob["_cond_source"]` for the per-video result, and with `--step-cache` the
-    cache's statistics in `blob["_step_cache"]`."""
+    cache's statistics in `blob["_step_cache"]`, with `--cfg-reuse` the reuse's in `blob["_cfg_reuse"]`."""
     torch.cuda.synchronize()
     t0 = time.time()
     n_valid = num_frames_valid(num_frames if num_frames is not None else args.num_frames)
@@ -263,12 +264,15 @@ def generate_continuation(pipe, blob, args, idx, device, num_frames=None, entry=
     lat[:, :, :ncl] = cond
     cache = C.step_cache_from_args(args)               # --step-cache: None when the flag is absent, and the call is the plain one
     solver = C.solver_from_args(args)                  # --solver: None for euler, likewise
+    reuse = C.cfg_reuse_from_args(args)                # --cfg-reuse: one object per continuation; None when absent, likewise
     out = pipe.denoise(lat, blob["prompt_embeds"], blob["prompt_mask"], blob.get("negative_embeds"), blob.get("negative_mask"),
                        num_cond_latents=ncl, num_inference_steps=args.num_inference_steps,
                        guidance_scale=args.guidance_scale, use_kv_cache=True, **({} if cache is None else {"step_cache": cache}),
-                       **({} if solver is None else {"solver": solver}))
+                       **({} if solver is None else {"solver": solver}), **({} if reuse is None else {"cfg_reuse": reuse}))
     if cache is not None:
         blob["_step_cache"] = pipe.last_step_cache_stats
+    if reuse is not None:
+        blob["_cfg_reuse"] = pipe.last_cfg_reuse_stats
     torch.cuda.synchronize()
     return out, time.time() - t0
 
@@ -410,6 +414,7 @@ def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Cal
                                                             frames=frames)
                 result["gen_time"] = gen_time
                 result.update(C.step_cache_result(blob))
+                result.update(C.cfg_reuse_result(blob))
             result["total_time"] = train_time + gen_time
             print(f"  [{idx}] {e['name']}: train {train_time:.1f}s loss {result['final_loss']}"
                   + (f" gen {gen_time:.1f}s" if not args.skip_generation else ""))
@@ -447,6 +452,7 @@ def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Cal
             summary.update(clip_gate_summary(args))
         summary.update(C.step_cache_record(args))      # these runners write no config.json: recorded here, when the flag is set
         summary.update(C.solver_record(args))
+        summary.update(C.cfg_reuse_record(args))
         summary["results"] = merged
         from tta.eval_metrics import aggregate_quality_metrics
         aggregate_quality_metrics(summary)
