@@ -355,12 +355,18 @@ def unpatchify(tok: torch.Tensor, Cout: int, T: int, H: int, W: int) -> torch.Te
 
 
 # ---------------------------------------------------------- denoise glue ---
+def _cfg_partials(pairs: int, B: int, device) -> torch.Tensor:
+    """The [pairs, B, 256, 2] fp32 partial sums of csrc/cfg_guidance.h (256 pairs per sample and pair of sums, every slot written
+    by the launch that reads it), from the caching allocator."""
+    return torch.empty((pairs, int(B), 256, 2), dtype=F32, device=device)
+
+
 def cfg_euler_step(cond: torch.Tensor, uncond: torch.Tensor, x: torch.Tensor, guidance: float, dt: float,
                    negate: bool = True, zero_star: bool = True) -> None:
     _req(cond, F32, "cfg_euler_step.cond"); _req(uncond, F32, "cfg_euler_step.uncond"); _req(x, F32, "cfg_euler_step.x")
     B = x.shape[0]
     n = x.numel() // B
-    ws = torch.empty((B, 256, 2), dtype=F32, device=x.device)      # lcv_hip.h: per-slice partial sums of the zero-star dots
+    ws = _cfg_partials(1, B, x.device)
     call("lcv_cfg_euler_step", _ptr(cond.contiguous()), _ptr(uncond.contiguous()), _ptr(x), _ptr(ws), B, n,
          float(guidance), float(dt), 1 if negate else 0, 1 if zero_star else 0, _stream())
 
@@ -391,10 +397,7 @@ def cfg_lms_step(cond: torch.Tensor, uncond: Optional[torch.Tensor], x: torch.Te
         raise _lib.LcvError("cfg_lms_step: cond and uncond must have x's size")
     B = x.shape[0]
     n = x.numel() // max(B, 1)
-    ws = None
-    if uncond is not None and zero_star:
-        # cfg_euler_step keeps no workspace cache to reuse: like it, take the 2 KiB per sample from the caching allocator
-        ws = torch.empty((B, 256, 2), dtype=F32, device=x.device)
+    ws = _cfg_partials(1, B, x.device) if (uncond is not None and zero_star) else None
     w = [float(v) for v in weights] + [0.0] * (3 - terms)
     call("lcv_cfg_lms_step", _ptr(cond.contiguous()), None if uncond is None else _ptr(uncond.contiguous()), _ptr(x), _ptr(f0),
          _ptr(hist[0]) if terms >= 2 else None, _ptr(hist[1]) if terms >= 3 else None, _ptr(ws), B, n, float(guidance),
@@ -410,7 +413,7 @@ def cfg_reuse_workspace(B: int, device) -> torch.Tensor:
     key = (torch.device(device).index, int(B))
     ws = _CFGREUSE_WS.get(key)
     if ws is None:
-        ws = _CFGREUSE_WS[key] = torch.empty((2, int(B), 256, 2), dtype=F32, device=device)
+        ws = _CFGREUSE_WS[key] = _cfg_partials(2, B, device)
     return ws
 
 

@@ -46,6 +46,12 @@ def retrieve_latents(encoder_output, generator=None, sample_mode: str = "sample"
     raise AttributeError("could not access latents of the provided encoder_output")
 
 
+def _denoise_options(step_cache, solver, cfg_reuse) -> dict:
+    """The optional keywords of `denoise()` that are set: with none of them a `generate_*` call is the plain call."""
+    options = {"step_cache": step_cache, "solver": solver, "cfg_reuse": cfg_reuse}
+    return {k: v for k, v in options.items() if v is not None}
+
+
 class LongCatVideoPipeline:
     vae_scale_factor_temporal = 4
     vae_scale_factor_spatial = 8
@@ -173,58 +179,63 @@ class LongCatVideoPipeline:
             and reuse is None
 
         extra = {} if cache is None else {"step_cache": cache}
+        if kv is not None:
+            extra["kv_cache_dict"] = kv
+        pinned = kv is None and ncl > 0                 # the conditioning frames sit in the sequence and in the state
 
-        def forward(x_in, ts):
-            if kv is not None:
-                return dit(hidden_states=x_in, timestep=ts, encoder_hidden_states=emb, encoder_attention_mask=mask,
-                           num_cond_latents=ncl, kv_cache_dict=kv, **extra)
-            return dit(hidden_states=x_in, timestep=ts, encoder_hidden_states=emb, encoder_attention_mask=mask,
+        def forward(x_in, ts, text=emb, text_mask=mask):
+            return dit(hidden_states=x_in, timestep=ts, encoder_hidden_states=text, encoder_attention_mask=text_mask,
                        num_cond_latents=ncl, **extra)
+
+        def timestep_rows(t, rows=Bm, out=None):
+            """The step's timestep per row and frame, pinned conditioning frames at 0; `out`: the graph's static buffer."""
+            ts = torch.full((rows, T_in), t, device=dev, dtype=torch.bfloat16) if out is None else out.fill_(t)
+            if pinned:
+                ts[:, :ncl] = 0
+            return ts
+
+        def rows(pred):
+            return (pred[1:2], pred[0:1]) if do_cfg else (pred, None)
+
+        def update(c, u, x, i, dt):                     # u = None: unguided, or c is already guided (a reuse step)
+            if lms is not None:                         # the history is shaped like x
+                lms.step(c, u, x, i, sched._sigmas_host, guidance_scale, self.negate_pred, self.use_zero_star)
+            elif u is not None:
+                ops.cfg_euler_step(c, u, x, guidance_scale, dt, negate=self.negate_pred, zero_star=self.use_zero_star)
+            else:
+                ops.euler_step(c, x, dt, negate=self.negate_pred)
+
+        def on_target(body, c, u, state=True):
+            """body(c, u, x) on what a step updates: the rows and `work` as they are, or, with pinned conditioning frames,
+            contiguous copies of the frames past them, the state's copied back.  `state=False`: body takes no x."""
+            if not pinned:
+                return body(c, u, work)
+            tgt = work[:, :, ncl:]
+            new = tgt.contiguous() if state else None
+            body(*(None if p is None else p[:, :, ncl:].contiguous() for p in (c, u)), new)
+            if state:
+                tgt.copy_(new)
         x_static = ts_static = pred_static = None
         if reuse is not None:
             reuse.begin(start_step, stop)
-
-            def unguided(v, x, i, dt):                  # a reuse step's update: v is already guided
-                if lms is not None:
-                    lms.step(v, None, x, i, sched._sigmas_host, guidance_scale, self.negate_pred, self.use_zero_star)
-                else:
-                    ops.euler_step(v, x, dt, negate=self.negate_pred)
         for i in range(start_step, stop):
             t = timesteps[i]
-            if reuse is not None and not reuse.is_full(i):
+            full = reuse is None or reuse.is_full(i)
+            if not full:
                 # a reuse step: the prompt row alone at batch 1 (the conditioning frames' KV cache is built at batch 1 and
                 # shared by the rows), v^ = c + delta over the model output, then the unguided update
-                ts = torch.full((1, T_in), t, device=dev, dtype=torch.bfloat16)
-                if kv is None and ncl > 0:
-                    ts[:, :ncl] = 0
-                more = {} if kv is None else {"kv_cache_dict": kv}
-                pred = dit(hidden_states=work.to(torch.bfloat16), timestep=ts, encoder_hidden_states=prompt_embeds,
-                           encoder_attention_mask=prompt_mask, num_cond_latents=ncl, **more)
-                dt = sched.dt(i)
-                if kv is None and ncl > 0:
-                    tgt = work[:, :, ncl:]
-                    new = tgt.contiguous()
-                    unguided(reuse.apply(pred[:, :, ncl:].contiguous()), new, i, dt)
-                    tgt.copy_(new)
-                else:
-                    unguided(reuse.apply(pred), work, i, dt)
-                if step_callback is not None:
-                    step_callback(i, work)
-                continue
-            if graph is not None:
+                ts = timestep_rows(t, rows=1)
+                pred = forward(work.to(torch.bfloat16), ts, prompt_embeds, prompt_mask)
+            elif graph is not None:
                 x_static.copy_(work.expand_as(x_static) if do_cfg else work)       # fp32 -> bf16 into the captured input
-                ts_static.fill_(t)
-                if kv is None and ncl > 0:
-                    ts_static[:, :ncl] = 0
+                timestep_rows(t, out=ts_static)
                 graph.replay()
                 pred = pred_static
             else:
                 x_in = work.to(torch.bfloat16)
                 if do_cfg:
                     x_in = x_in.expand(2, -1, -1, -1, -1)
-                ts = torch.full((Bm, T_in), t, device=dev, dtype=torch.bfloat16)
-                if kv is None and ncl > 0:
-                    ts[:, :ncl] = 0
+                ts = timestep_rows(t)
                 if cache is not None:
                     cache.set_step(i, forced=i == start_step or i == stop - 1)
                 pred = forward(x_in, ts)
@@ -236,27 +247,12 @@ class LongCatVideoPipeline:
                     with torch.cuda.graph(graph):
                         pred_static = forward(x_static, ts_static)
             dt = sched.dt(i)
-            if kv is None and ncl > 0:
-                tgt = work[:, :, ncl:]
-                sl = lambda p: p[:, :, ncl:].contiguous()
-                new = tgt.contiguous()
-                if lms is not None:                     # the history is shaped like the target slice
-                    lms.step(sl(pred[1:2]) if do_cfg else sl(pred), sl(pred[0:1]) if do_cfg else None, new, i,
-                             sched._sigmas_host, guidance_scale, self.negate_pred, self.use_zero_star)
-                else:
-                    self._apply_step(sl(pred[1:2]) if do_cfg else sl(pred), sl(pred[0:1]) if do_cfg else None, new,
-                                     guidance_scale, dt)
-                tgt.copy_(new)
-            elif lms is not None:
-                lms.step(pred[1:2] if do_cfg else pred, pred[0:1] if do_cfg else None, work, i, sched._sigmas_host,
-                         guidance_scale, self.negate_pred, self.use_zero_star)
+            if not full:
+                on_target(lambda c, _, x: update(reuse.apply(c), None, x, i, dt), pred, None)
             else:
-                self._apply_step(pred[1:2] if do_cfg else pred, pred[0:1] if do_cfg else None, work, guidance_scale, dt)
-            if reuse is not None:                       # a full step: today's step above, then delta = v - c of its two rows
-                if kv is None and ncl > 0:
-                    reuse.store(sl(pred[1:2]), sl(pred[0:1]), guidance_scale, self.use_zero_star, i)
-                else:
-                    reuse.store(pred[1:2], pred[0:1], guidance_scale, self.use_zero_star, i)
+                on_target(lambda c, u, x: update(c, u, x, i, dt), *rows(pred))
+                if reuse is not None:                   # a full step: today's step above, then delta = v - c of its two rows
+                    on_target(lambda c, u, _: reuse.store(c, u, guidance_scale, self.use_zero_star, i), *rows(pred), state=False)
             if step_callback is not None:
                 step_callback(i, work)
         sched._step_index = stop
@@ -267,13 +263,6 @@ class LongCatVideoPipeline:
         if cond is not None:
             work = torch.cat([cond, work], dim=2)
         return work
-
-    def _apply_step(self, cond_pred, uncond_pred, x, guidance, dt):
-        if uncond_pred is not None:
-            ops.cfg_euler_step(cond_pred, uncond_pred, x, guidance, dt, negate=self.negate_pred,
-                               zero_star=self.use_zero_star)
-        else:
-            ops.euler_step(cond_pred, x, dt, negate=self.negate_pred)
 
     # ------------------------------------------------------------------ public generation entry points
     def _prep_text(self, prompt, negative_prompt, prompt_embeds, prompt_mask, negative_embeds, negative_mask, do_cfg):
@@ -322,9 +311,7 @@ class LongCatVideoPipeline:
         noise[:, :, :ncl] = cond
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=ncl, num_inference_steps=num_inference_steps,
                            guidance_scale=guidance_scale, use_kv_cache=use_kv_cache,
-                           **({} if step_cache is None else {"step_cache": step_cache}),
-                           **({} if solver is None else {"solver": solver}),
-                           **({} if cfg_reuse is None else {"cfg_reuse": cfg_reuse}))
+                           **_denoise_options(step_cache, solver, cfg_reuse))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]
@@ -343,9 +330,7 @@ class LongCatVideoPipeline:
         C = self.dit.config.in_channels
         noise = torch.randn((1, C, T_lat, h, w), generator=generator, device=self.device, dtype=torch.float32)
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=0, num_inference_steps=num_inference_steps,
-                           guidance_scale=guidance_scale, **({} if step_cache is None else {"step_cache": step_cache}),
-                           **({} if solver is None else {"solver": solver}),
-                           **({} if cfg_reuse is None else {"cfg_reuse": cfg_reuse}))
+                           guidance_scale=guidance_scale, **_denoise_options(step_cache, solver, cfg_reuse))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]

@@ -58,6 +58,26 @@ def test_a_changed_instruction_register_count_or_kernarg_size_compares_unequal(c
     assert any("DIFFERS" in r for r in report), report
 
 
+def test_a_differing_kernel_is_told_whether_its_arithmetic_differs():
+    """Registers renamed (and an fma spelled as the tied-register fmac): `same fp ops`; an fma split into a mul and an add:
+    `fp ops differ`, with what went and what came.  A changed register count or LDS size is named beside either verdict."""
+    lds = "\n\t\t.amdhsa_group_segment_fixed_size {}"
+    body = "v_mul_f32_e32 v1, v2, v3\n\tv_fma_f32 v4, v1, v5, v6\n\tv_rcp_f32_e32 v7, v4\n\tglobal_store_dword v[8:9], v7, off"
+    old = listing(inst=body, vgpr="10" + lds.format(32))
+    renamed = listing(inst="v_mul_f32_e32 v2, v1, v3\n\tv_fmac_f32_e32 v6, v2, v5\n\tv_rcp_f32_e32 v7, v6\n\tglobal_store_dword v[8:9], v7, off",
+                      vgpr="10" + lds.format(32))
+    report = [r for r in E.compare(old, renamed) if r.startswith("attn_fwd_kernel")]
+    assert len(report) == 1 and "DIFFERS" in report[0] and "same fp ops (3 floating-point VALU instructions)" in report[0], report
+    assert "next_free_vgpr 10, LDS bytes 32 (unchanged)" in report[0], report
+    split = listing(inst=body.replace("v_fma_f32 v4, v1, v5, v6", "v_mul_f32_e32 v4, v1, v5\n\tv_add_f32_e32 v4, v4, v6"),
+                    vgpr="12" + lds.format(48))
+    report = [r for r in E.compare(old, split) if r.startswith("attn_fwd_kernel")]
+    assert len(report) == 1 and "DIFFERS" in report[0] and "same fp ops" not in report[0], report
+    assert "fp ops differ: -1xv_fma_f32 +1xv_add_f32 +1xv_mul_f32" in report[0], report
+    assert "next_free_vgpr 10 -> 12, LDS bytes 32 -> 48 (CHANGED)" in report[0], report
+    assert all("fp ops" not in r for r in E.compare(old, old)), "an identical kernel gets no verdict"
+
+
 def test_a_renamed_kernel_in_another_file_compares_equal_under_its_new_name():
     """--map: `tn_skinny_dropout_kernel` of one file against `tn_skinny_kernel<8, drop_args>` of another."""
     old = listing(file="lora_dropout.hip", sym="_Z24tn_skinny_dropout_kernelPKtS1_lli9drop_args", fn=1)

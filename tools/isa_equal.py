@@ -7,6 +7,11 @@ them kernel by kernel: instructions, labels, the .amdhsa_* descriptor (register 
 metadata.  Normalising means: comments, blank lines, `.file` / `.ident` go; a mangled symbol becomes its function name plus
 template arguments (the parameter types - a renamed struct - drop out); basic-block labels lose their function index.
 
+Where a kernel differs, the report also says whether its arithmetic does: "same fp ops" when the multiset of its floating-point
+VALU mnemonics (v_*_f32, v_pk_*_f32, the v_rcp* and v_div* families; encoding suffixes dropped, v_fmac counted as v_fma) is
+unchanged, "fp ops differ" with the mnemonics gained and lost otherwise; and whether .amdhsa_next_free_vgpr and the LDS size
+(.amdhsa_group_segment_fixed_size) are unchanged.  The exit code does not depend on it.
+
 A kernel that was renamed or moved to another file is compared with --map: the old kernel's listing, with its name replaced
 by the new one, against the new kernel's.  Kernel names are the normalised ones, as the report prints them.
 
@@ -17,6 +22,7 @@ import re
 import subprocess
 import sys
 import tempfile
+from collections import Counter
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 from typing import Dict, List, Optional
@@ -27,6 +33,9 @@ _MANGLED = re.compile(r"_Z(\d+)(\w+)")
 # literal template arguments and parameter packs of named types: <8, 0, true, 0> = ILi8ELi0ELb1ELi0EE, <8, drop_args> = ILi8EJ9drop_argsEE
 _TEMPLATE = re.compile(r"I(?:L[a-z]\w*?E|J\w*?E)+E")
 _LABEL = re.compile(r"\.L(BB|func_end|func_begin)\d+")
+_FP_VALU = re.compile(r"(v_(?:pk_)?\w+_f32|v_rcp\w*|v_div\w*)\b")
+_ENCODING = re.compile(r"_(e32|e64|dpp|sdwa)\b")
+_RESOURCES = {".amdhsa_next_free_vgpr": "next_free_vgpr", ".amdhsa_group_segment_fixed_size": "LDS bytes"}
 
 
 def _plain(m: "re.Match") -> str:
@@ -62,6 +71,31 @@ def normalise(text: str) -> Dict[str, List[str]]:
     return out
 
 
+def fp_ops(lines: List[str]) -> Counter:
+    """The multiset of a kernel's floating-point VALU mnemonics, without encoding suffixes; v_fmac is v_fma with a tied register."""
+    ops = Counter()
+    for line in lines:
+        m = _FP_VALU.match(_ENCODING.sub("", line.split(None, 1)[0]) if line else "")
+        if m:
+            ops[m.group(1).replace("v_fmac_", "v_fma_")] += 1
+    return ops
+
+
+def arithmetic_verdict(a: List[str], b: List[str]) -> str:
+    """One line for a kernel that differs: `same fp ops` or `fp ops differ`, then the register and LDS figures."""
+    fa, fb = fp_ops(a), fp_ops(b)
+    if fa == fb:
+        out = f"same fp ops ({sum(fa.values())} floating-point VALU instructions)"
+    else:
+        out = "fp ops differ: " + " ".join([f"-{n}x{k}" for k, n in sorted((fa - fb).items())] + [f"+{n}x{k}" for k, n in sorted((fb - fa).items())])
+    res = []
+    for key, label in _RESOURCES.items():
+        va, vb = ([line.split()[1] for line in side if line.startswith(key + " ")] for side in (a, b))
+        res.append(f"{label} {'/'.join(va) or '?'}" + ("" if va == vb else f" -> {'/'.join(vb) or '?'}"))
+    same = all("->" not in r for r in res)
+    return f"{out}; {', '.join(res)} ({'unchanged' if same else 'CHANGED'})"
+
+
 def compare(old: str, new: str, show: int = 4, rename: Optional[Dict[str, str]] = None) -> List[str]:
     """-> one report line per kernel: `identical`, or where the two listings part.  With `rename` {old kernel: new kernel} only
     those kernels are compared, the old one under its new name."""
@@ -78,7 +112,8 @@ def compare(old: str, new: str, show: int = 4, rename: Optional[Dict[str, str]] 
         else:
             i = next((i for i, (x, y) in enumerate(zip(a[k], b[k])) if x != y), min(len(a[k]), len(b[k])))
             report.append(f"{k}: DIFFERS at line {i} of {len(a[k])} / {len(b[k])}\n" +
-                          "\n".join(f"    - {x}" for x in a[k][i:i + show]) + "\n" + "\n".join(f"    + {y}" for y in b[k][i:i + show]))
+                          "\n".join(f"    - {x}" for x in a[k][i:i + show]) + "\n" + "\n".join(f"    + {y}" for y in b[k][i:i + show]) +
+                          ("" if k == "(metadata)" else "\n    " + arithmetic_verdict(a[k], b[k])))
     return report
 
 
