@@ -9,7 +9,6 @@ the videos are sharded over ranks (the reference launches it with torchrun too, 
 import argparse
 import csv
 import json
-import os
 import sys
 import time
 from pathlib import Path
@@ -101,8 +100,7 @@ def main(argv=None):
         rows.append(row)
     total_inference_time = time.time() - t_inf
     took = [r.get("inference_time_s", 0.0) for r in rows]
-    merged = (dp.gather_results(rows, output_dir=str(out_dir), wait_s=dp.merge_wait_seconds(max(took) if took else 0.0, len(rows)))
-              if world > 1 else dp.merge_results([rows]))
+    merged = R.merge_job_rows(rows, max(took) if took else 0.0, str(out_dir), world)
     if rank == 0:
         times = [r["inference_time_s"] for r in merged if "inference_time_s" in r]
         with open(out_dir / "per_video_metrics.csv", "w", newline="") as f:
@@ -138,11 +136,7 @@ def main(argv=None):
         with open(out_dir / "summary.json", "w") as f:
             json.dump(summary, f, indent=2)
         print(f"baseline complete: {len(times)}/{len(merged)} videos")
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
-        if rank == 0 and dp.exit_code_after_merge():
-            sys.exit(dp.exit_code_after_merge())      # summary.json is written, but a peer never delivered its final rows
+    R.finish_distributed(rank, world)
 
 
 if __name__ == "__main__":

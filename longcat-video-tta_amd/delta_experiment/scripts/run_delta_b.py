@@ -37,7 +37,6 @@ def main(argv=None):
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_delta_b(
             w, cond, train, pe, pm, num_steps=args.delta_steps, lr=args.delta_lr, device=device, dtype=torch.bfloat16,
             early_stopper=es, train_latents_variants=tv),
-        params_of=lambda w: list(w.deltas) + ([w.delta_final] if w.delta_final is not None else []),
         result_extra=lambda opt: {"delta_norms": opt["delta_norms"]},
         summary_head={"delta_target": args.delta_target, "delta_target_blocks": args.delta_target_blocks,
                       "num_groups": args.num_groups, "delta_steps": args.delta_steps, "delta_lr": args.delta_lr},

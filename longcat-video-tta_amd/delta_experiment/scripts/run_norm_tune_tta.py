@@ -43,7 +43,6 @@ def main(argv=None):
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_norm_params(
             w, w.tuned_params, cond, train, pe, pm, num_steps=args.norm_steps, lr=args.norm_lr, device=device, dtype=torch.bfloat16,
             early_stopper=es, train_latents_variants=tv, **C.optimizer_kwargs(args)),
-        params_of=lambda w: w.tuned_params,
         result_extra=lambda opt: {k: opt[k] for k in ("norm_param_drift", "delta_norm", "drift_norm") if k in opt},
         # this runner writes no config.json (as the reference's does not): the flag is recorded here, when it is set
         summary_head={"norm_target": args.norm_target, "norm_steps": args.norm_steps, "norm_lr": args.norm_lr,

@@ -2,13 +2,18 @@
 checkpoints or `synthetic[:depth[:hidden[:caption]]]`; `latents/*.pt` or `synthetic:N` data), one-process-per-GPU data
 parallelism over videos, the KV-cached CFG continuation, and the reference's `checkpoint.json` / `summary.json` schemas
 (delta_experiment/scripts/run_delta_a.py:763-935, run_delta_b.py:915-960, run_delta_c.py:640-703;
-`save_checkpoint` common.py:2055-2059).  The LoRA runner has its own main (it also writes `config.json`)."""
+`save_checkpoint` common.py:2055-2059), and the per-video job loop itself: `run_tta_job` drives the LoRA, full-model and
+delta-family runners, each of which hands it a `TTAMethod` (the LoRA and full-model ones also write `config.json`); the
+baseline runner keeps its own loop and shares the end-of-job merge and the teardown."""
+import contextlib
 import json
 import os
 import sys
 import time
+import traceback
+from dataclasses import dataclass
 from pathlib import Path
-from typing import Callable, Dict
+from typing import Callable, Dict, Optional
 
 import numpy as np
 import torch
@@ -16,6 +21,8 @@ import torch
 from longcat_video.parallel import data_parallel as dp
 from tta import cli_args as C
 from tta.early_stopping import add_early_stopping_args, build_early_stopper_from_args
+from tta.eval_metrics import aggregate_quality_metrics
+from tta.inner_loop import choose_gradient_checkpointing
 from tta.latent_split import _estimate_latent_len, num_frames_valid, split_tta_latents
 
 
@@ -339,12 +346,55 @@ def clip_gate_summary(args) -> Dict:
             "clip_gate_stats": {"skip_rate": 0.0, "num_skipped": 0, "num_scored": 0}}
 
 
-def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Callable, params_of: Callable,
-                     result_extra: Callable, summary_head: Dict, file_suffix: str, cleanup: Callable = None):
-    """The per-video loop of the delta runners: fresh wrapper -> (anchored early stopping) -> optimise on the conditioning
-    window -> continuation with the wrapper's hooks installed -> checkpoint after every video -> summary."""
+def merge_job_rows(rows, longest_video_s: float, output_dir: str, world: int):
+    """End-of-job merge of the ranks' rows; rank 0 gets them, the others None.  At world size above 1 it is the file rendezvous
+    with a bounded wait (a wedged peer must not park this rank for a day)."""
+    if world == 1:
+        return dp.merge_results([rows])
+    return dp.gather_results(rows, output_dir=output_dir, wait_s=dp.merge_wait_seconds(longest_video_s, len(rows)))
+
+
+def finish_distributed(rank: int, world: int):
+    """Process-group teardown, and the exit code of a job whose merge came up short."""
+    if world > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+        if rank == 0 and dp.exit_code_after_merge():
+            sys.exit(dp.exit_code_after_merge())      # summary.json is written, but a peer never delivered its final rows
+
+
+def failed_and_final_loss(merged, ok) -> Dict:
+    """`num_failed` and `avg_final_loss` of the LoRA and full-model summaries."""
+    losses = [r["final_loss"] for r in ok if r.get("final_loss") is not None]
+    return {"num_failed": len(merged) - len(ok), "avg_final_loss": float(np.mean(losses)) if losses else None}
+
+
+@dataclass
+class TTAMethod:
+    """What one runner hands to `run_tta_job`: the places where the LoRA, full-model and delta-family jobs differ.  Each runner
+    uses one of the three per-video hooks `before_load`, `make_model` and `after_variants`; they sit where its reference resets
+    or builds what it adapts."""
+    name: str                                      # `method` of summary.json, context of the feature-budget check
+    file_suffix: str                               # saved clips are <video>_<file_suffix>
+    prepare: Callable                              # (dit) once per job: freeze / unfreeze / inject; returns config.json or None
+    adapt: Callable                                # (model, cond, train, pe, pm, device, es, variants) -> loop dict with train_time
+    row_extra: Callable                            # (loop dict, variants, blob) -> the method's own keys of a result row
+    summary_extra: Callable                        # (merged, ok) -> the method's own keys of summary.json
+    label: Optional[str] = None                    # "<label> complete: n/m videos"; the name when absent
+    before_load: Optional[Callable] = None         # (dit) before the entry is loaded
+    choose_checkpointing: bool = True              # per-video choice from the token count; off where checkpointing is forced on
+    make_model: Optional[Callable] = None          # (dit) -> what the stopper scores and `adapt` trains; the DiT itself when absent
+    after_variants: Optional[Callable] = None      # () once the training latents are final
+    generating: Callable = lambda model: contextlib.nullcontext()      # (model) -> context the continuation runs in
+    on_success: Optional[Callable] = None          # (entry) after a video's row is complete
+    cleanup: Optional[Callable] = None             # (model) after every video that got as far as make_model, failed or not
+
+
+def run_tta_job(args, m: TTAMethod):
+    """The job of every TTA runner: set-up and resume -> per video: split, variants, (anchored early stopping), adapt on the
+    conditioning window, continuation, decode, score, save -> checkpoint after every video -> merge -> summary."""
     C.normalize_tta_frame_args(args)
-    C.validate_tta_feature_budget(args, context=method)
+    C.validate_tta_feature_budget(args, context=m.name)
     C.reject_out_of_scope(args)
     if getattr(args, "batch_videos", 1) != 1:
         raise NotImplementedError("retrieval-augmented batch TTA needs the sentence-transformer pool (SURVEY §2 #16)")
@@ -354,55 +404,54 @@ def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Cal
     os.makedirs(args.output_dir, exist_ok=True)
     dp.begin_job(args.output_dir, rank)
     videos_dir = os.path.join(args.output_dir, "videos"); os.makedirs(videos_dir, exist_ok=True)
-    prior = dp.load_checkpoint(args.output_dir, rank if world > 1 else None)
+    ck_rank = rank if world > 1 else None              # per-rank checkpoint names at world size above 1
+    prior = None if getattr(args, "restart", False) else dp.load_checkpoint(args.output_dir, ck_rank)
     all_results = prior["results"] if prior else []
     done = {r["idx"] for r in all_results}
     dit, pipe = load_components(args, device)
-    for p in dit.parameters():
-        p.requires_grad = False
+    config = m.prepare(dit)
+    if config is not None and rank == 0:
+        config["runtime"] = {"backend": "mi355x-hip", "world_size": world}
+        with open(os.path.join(args.output_dir, "config.json"), "w") as f:
+            json.dump(config, f, indent=2)
     entries = list_eval_entries(args, dit)
     my_idx = [i for i in dp.shard_indices(len(entries), rank, world) if i not in done]
     early_stopper = build_early_stopper_from_args(args)
     n_ctx_lat = _estimate_latent_len(args.tta_context_frames)
-    from tta.inner_loop import choose_gradient_checkpointing
 
     for idx in my_idx:
         e = entries[idx]
-        wrapper = None
+        model = None
         try:
             torch.manual_seed(dp.seed_for_video(args.seed, idx))
+            if m.before_load is not None:
+                m.before_load(dit)
             blob = load_entry(e, args, dit, device, pipe=pipe)
             cond, train, val = split_tta_latents(blob["latents"], n_ctx_lat, args.es_holdout_fraction)
-            n_tok = (cond.shape[2] + train.shape[2]) * (cond.shape[3] // 2) * (cond.shape[4] // 2)
-            choose_gradient_checkpointing(dit, n_tok)
-            wrapper = make_wrapper(dit).to(device)
+            if m.choose_checkpointing:
+                n_tok = (cond.shape[2] + train.shape[2]) * (cond.shape[3] // 2) * (cond.shape[4] // 2)
+                choose_gradient_checkpointing(dit, n_tok)
+            model = dit if m.make_model is None else m.make_model(dit).to(device)
             pe, pm = blob["prompt_embeds"], blob["prompt_mask"]
-            # variants first (as in the LoRA / full runners): a synthetic entry's cond / train latents are REPLACED by the encode
-            # of its own pixels, and the stopper's resident anchor batch must be built from the clip the loop trains on
-            cond, train, variants = train_latents_variants_for(args, pipe, blob, e, cond, train, device)
+            # variants before the stopper: a synthetic entry's cond / train latents are REPLACED by the encode of its own pixels,
+            # and the stopper's resident anchor batch must be built from the clip the loop trains on
+            cond, train, variants = train_latents_variants_for(args, pipe, blob, e, cond, train, device)   # --aug-enabled
+            if m.after_variants is not None:
+                m.after_variants()
             es = early_stopper if (early_stopper is not None and val is not None) else None
             if es is not None:
-                # the wrapper is called directly, so the stopper scores its whole anchor set in one batched forward
-                es.setup(model=wrapper, cond_latents=cond, val_latents=val, prompt_embeds=pe, prompt_mask=pm, device=device,
+                es.setup(model=model, cond_latents=cond, val_latents=val, prompt_embeds=pe, prompt_mask=pm, device=device,
                          dtype=torch.bfloat16, video_id=e["name"])
-            t0 = time.time()
-            opt = optimize_fn(wrapper, cond, train, pe, pm, device, es, variants)
-            torch.cuda.synchronize()
-            train_time = time.time() - t0
+            tr = m.adapt(model, cond, train, pe, pm, device, es, variants)
+            train_time = tr["train_time"]
             result = {"idx": idx, "video_name": e["name"], "video_path": e["path"], "caption": blob.get("caption", ""),
-                      "train_time": train_time, "es_check_time": opt.get("es_check_time", 0.0),
-                      "final_loss": opt["losses"][-1] if opt["losses"] else None, "batch_size": 1, "num_neighbors": 0,
-                      "early_stopping_info": opt.get("early_stopping_info"), "success": True}
-            if variants is not None:
-                result["aug_variants"] = [v["name"] for v in variants]
-            result.update(result_extra(opt))
+                      "train_time": train_time, "es_check_time": tr.get("es_check_time", 0.0),
+                      "final_loss": tr["losses"][-1] if tr["losses"] else None, "batch_size": 1, "num_neighbors": 0,
+                      "early_stopping_info": tr.get("early_stopping_info"), "success": True}
             gen_time = 0.0
             if not args.skip_generation:
-                wrapper.apply_to_dit()
-                try:
-                    out, gen_time = generate_continuation(pipe, blob, args, idx, device, entry=e)
-                finally:
-                    wrapper.remove_from_dit()
+                with m.generating(model):
+                    out, gen_time = generate_continuation(pipe, blob, args, idx, device, entry=e)   # cond encode + denoise
                 if pipe.vae is not None:
                     t1 = time.time()
                     frames = pipe.decode_to_frames(out)
@@ -410,58 +459,79 @@ def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Cal
                     gen_time += time.time() - t1              # the reference's gen_time includes the decode (generate_vc)
                     result.update(score_generation(frames, blob, e, args))
                     if not args.no_save_videos:
-                        result["output_path"] = save_frames(pipe, out, os.path.join(videos_dir, f"{e['name']}_{file_suffix}"),
+                        result["output_path"] = save_frames(pipe, out, os.path.join(videos_dir, f"{e['name']}_{m.file_suffix}"),
                                                             frames=frames)
                 result["gen_time"] = gen_time
                 result.update(C.step_cache_result(blob))
                 result.update(C.cfg_reuse_result(blob))
+            result.update(m.row_extra(tr, variants, blob))
             result["total_time"] = train_time + gen_time
+            if m.on_success is not None:
+                m.on_success(e)
             print(f"  [{idx}] {e['name']}: train {train_time:.1f}s loss {result['final_loss']}"
                   + (f" gen {gen_time:.1f}s" if not args.skip_generation else ""))
             all_results.append(result)
-        except Exception as ex:  # recorded and skipped, like the reference (run_delta_a.py:881-893)
-            import traceback
+        except Exception as ex:  # recorded and skipped, like the reference (run_lora_tta.py:1264-1271, run_delta_a.py:881-893)
             print(f"  ERROR: {ex}")
             traceback.print_exc()
             all_results.append({"idx": idx, "video_name": e["name"], "video_path": e["path"], "error": str(ex),
                                 "success": False})
             if getattr(ex, "fatal", False):   # a failed launch / device error: the HIP context may be dead — stop here
-                dp.write_checkpoint(args.output_dir, idx, all_results, rank=rank if world > 1 else None)
+                dp.write_checkpoint(args.output_dir, idx, all_results, rank=ck_rank)
                 raise
         finally:
-            if cleanup is not None and wrapper is not None:
-                cleanup(wrapper)   # e.g. norm tuning: put the job's original weights back before the next video
-        dp.write_checkpoint(args.output_dir, idx + world, all_results, rank=rank if world > 1 else None)
+            if m.cleanup is not None and model is not None:
+                m.cleanup(model)   # e.g. norm tuning: put the job's original weights back before the next video
+        dp.write_checkpoint(args.output_dir, idx + world, all_results, rank=ck_rank)
 
-    # end-of-job merge: file rendezvous with a bounded wait (a wedged peer must not park this rank for a day)
     took = [r.get("total_time") or r.get("train_time") or 0.0 for r in all_results if r.get("success")]
-    wait_s = dp.merge_wait_seconds(max(took) if took else 0.0, len(all_results))
-    merged = (dp.gather_results(all_results, output_dir=args.output_dir, wait_s=wait_s) if world > 1
-              else dp.merge_results([all_results]))
+    merged = merge_job_rows(all_results, max(took) if took else 0.0, args.output_dir, world)
     if rank == 0:
         ok = [r for r in merged if r.get("success", False)]
         mean = lambda k: float(np.mean([r.get(k, 0.0) or 0.0 for r in ok])) if ok else 0
-        summary = {"method": method}
-        summary.update(summary_head)
-        summary.update({"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
-                        "gen_start_frame": args.gen_start_frame, "num_videos": len(merged), "num_successful": len(ok),
-                        "avg_train_time": mean("train_time"), "avg_clip_gate_eval_time": 0,
-                        "avg_es_check_time": mean("es_check_time"), "avg_gen_time": mean("gen_time"),
-                        "avg_total_time": mean("total_time")})
-        if hasattr(args, "clip_gate_enabled"):
-            summary.update(clip_gate_summary(args))
-        summary.update(C.step_cache_record(args))      # these runners write no config.json: recorded here, when the flag is set
-        summary.update(C.solver_record(args))
-        summary.update(C.cfg_reuse_record(args))
-        summary["results"] = merged
-        from tta.eval_metrics import aggregate_quality_metrics
-        aggregate_quality_metrics(summary)
+        summary = {"method": m.name, "num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
+                   "gen_start_frame": args.gen_start_frame, "num_videos": len(merged), "num_successful": len(ok),
+                   "avg_train_time": mean("train_time"), "avg_clip_gate_eval_time": 0,
+                   "avg_es_check_time": mean("es_check_time"), "avg_gen_time": mean("gen_time"),
+                   "avg_total_time": mean("total_time"), **m.summary_extra(merged, ok), "results": merged}
+        aggregate_quality_metrics(summary)                                     # run_lora_tta.py:1315 (common.py:2453-2458)
         dp.write_checkpoint(args.output_dir, dp.contiguous_next_idx(merged), merged)
         with open(os.path.join(args.output_dir, "summary.json"), "w") as f:
             json.dump(summary, f, indent=2, default=str)
-        print(f"{method} complete: {len(ok)}/{len(merged)} videos")
-    if world > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
-        if rank == 0 and dp.exit_code_after_merge():
-            sys.exit(dp.exit_code_after_merge())      # summary.json is written, but a peer never delivered its final rows
+        print(f"{m.label or m.name} complete: {len(ok)}/{len(merged)} videos")
+    finish_distributed(rank, world)
+
+
+@contextlib.contextmanager
+def _hooks_installed(wrapper):
+    wrapper.apply_to_dit()
+    try:
+        yield
+    finally:
+        wrapper.remove_from_dit()
+
+
+def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Callable, result_extra: Callable,
+                     summary_head: Dict, file_suffix: str, cleanup: Callable = None):
+    """The delta runners on `run_tta_job`: everything frozen, a fresh wrapper per video, its hooks installed for the
+    continuation, wall time around the optimisation; no config.json, so the generation flags are recorded in the summary."""
+    def freeze(dit):
+        for p in dit.parameters():
+            p.requires_grad = False
+
+    def adapt(wrapper, cond, train, pe, pm, device, es, variants):
+        t0 = time.time()
+        opt = optimize_fn(wrapper, cond, train, pe, pm, device, es, variants)
+        torch.cuda.synchronize()
+        return {**opt, "train_time": time.time() - t0}
+
+    def row_extra(opt, variants, blob):
+        return {**({"aug_variants": [v["name"] for v in variants]} if variants is not None else {}), **result_extra(opt)}
+
+    def summary_extra(merged, ok):
+        return {**summary_head, **(clip_gate_summary(args) if hasattr(args, "clip_gate_enabled") else {}),
+                **C.step_cache_record(args), **C.solver_record(args), **C.cfg_reuse_record(args)}
+
+    run_tta_job(args, TTAMethod(name=method, file_suffix=file_suffix, prepare=freeze, adapt=adapt, row_extra=row_extra,
+                                summary_extra=summary_extra, make_model=make_wrapper, generating=_hooks_installed,
+                                cleanup=cleanup))
