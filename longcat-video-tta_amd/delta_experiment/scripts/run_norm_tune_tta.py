@@ -43,14 +43,15 @@ def main(argv=None):
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_norm_params(
             w, w.tuned_params, cond, train, pe, pm, num_steps=args.norm_steps, lr=args.norm_lr, device=device, dtype=torch.bfloat16,
             early_stopper=es, train_latents_variants=tv, **C.optimizer_kwargs(args)),
-        result_extra=lambda opt: {k: opt[k] for k in ("norm_param_drift", "delta_norm", "drift_norm") if k in opt},
+        result_extra=lambda opt: {**{k: opt[k] for k in ("norm_param_drift", "delta_norm", "drift_norm") if k in opt},
+                                  **C.stochastic_rounding_record(args)},
         # this runner writes no config.json (as the reference's does not): the flag is recorded here, when it is set
         summary_head={"norm_target": args.norm_target, "norm_steps": args.norm_steps, "norm_lr": args.norm_lr,
                       **({"master_weights": True} if args.master_weights else {}),
                       **({"adam_8bit": True} if args.adam_8bit else {}),
                       **({"grad_accum": args.grad_accum} if args.grad_accum > 1 else {}),
                       **({"decay_to_base": True} if args.decay_to_base else {}),
-                      **C.weight_ema_record(args)},
+                      **C.weight_ema_record(args), **C.stochastic_rounding_record(args)},
         file_suffix="norm_tune", cleanup=lambda w: w.restore())
 
 

@@ -159,6 +159,14 @@ _SIGNATURES_CFGREUSE = {
     "lcv_cfg_delta_apply": [P, P, P, I64, I64, P],
 }
 
+# include/lcv_hip_sr.h (a header of its own: stochastic rounding for the bf16 optimizer steps): the steps take lcv_master_*_step's
+# arguments without `low` and with uint64 `seed, offset` in front of the stream; round takes (x fp32, out bf16, n, seed, offset)
+_SIGNATURES_SR = {
+    "lcv_sr_sgd_step": [P, I64, I64, P, F64, F64, U64, U64, P],
+    "lcv_sr_adamw_step": [P, I64, I64, P, F64, F64, F64, F64, F64, I64, U64, U64, P],
+    "lcv_sr_round": [P, P, I64, U64, U64, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -218,7 +226,7 @@ def load():
                        + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())
                        + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())
                        + list(_SIGNATURES_STEPCACHE.items()) + list(_SIGNATURES_SOLVER.items())
-                       + list(_SIGNATURES_CFGREUSE.items())):
+                       + list(_SIGNATURES_CFGREUSE.items()) + list(_SIGNATURES_SR.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

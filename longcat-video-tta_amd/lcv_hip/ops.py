@@ -281,6 +281,33 @@ def lora_down(x: torch.Tensor, A: torch.Tensor, s: float, rpad: int = 64) -> tor
 _U64 = (1 << 64) - 1
 
 
+def draw_philox_offset(device: torch.device) -> Tuple[int, int]:
+    """One (seed, offset) pair for one Philox draw (a LoRA dropout mask, the rounding bits of one optimizer step), from the
+    device's default generator: its seed and its current Philox offset, which is then advanced by 4 (the granularity the
+    generator accepts).  Host-side state only: no device-to-host sync.  It follows torch.manual_seed, and
+    torch.utils.checkpoint's RNG preservation replays it for a recomputed block."""
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    gen = torch.cuda.default_generators[index]
+    seed, offset = gen.initial_seed(), gen.get_offset()
+    gen.set_offset(offset + 4)
+    return seed, offset
+
+
+def sr_round(x: torch.Tensor, seed: int, offset: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 of the fp32 `x`, rounded stochastically with stream 0 and group i >> 3 of (seed, offset) (include/lcv_hip_sr.h): the
+    rounding of the --stochastic-rounding optimizer steps on an array of its own."""
+    _req(x, F32, "sr_round.x")
+    if not x.is_contiguous():
+        raise _lib.LcvError("sr_round: x must be contiguous")
+    out = torch.empty(x.shape, dtype=BF16, device=x.device) if out is None else out
+    _req(out, BF16, "sr_round.out")
+    if out.numel() != x.numel() or not out.is_contiguous():
+        raise _lib.LcvError("sr_round: out must be contiguous with x's element count")
+    if x.numel():
+        call("lcv_sr_round", _ptr(x), _ptr(out), x.numel(), int(seed) & _U64, int(offset) & _U64, _stream())
+    return out
+
+
 def _draw(p: float, seed: int, offset: int, row0: int) -> tuple:
     """The four mask arguments as the C ABI takes them."""
     return float(p), int(seed) & _U64, int(offset) & _U64, int(row0)

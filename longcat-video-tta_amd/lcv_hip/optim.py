@@ -10,7 +10,7 @@ import torch
 
 from . import lib as _lib
 from . import ops
-from .ops import BF16, F32, _ptr, _stream
+from .ops import BF16, F32, _U64, _ptr, _stream
 
 # a device table: `desc` [n, 6] int64 rows of lcv_adam_tensor, `sides` name -> [n] int64 pointers parallel to it
 _Table = namedtuple("_Table", "desc sides n chunks")
@@ -57,6 +57,13 @@ class FusedAdamWClip:
     `ema_swap()` exchanges the average and the masters bit for bit, so the model can be scored or run with the average and
     training can go on afterwards; while the average is in the parameters (`ema_in_params`) the optimizer refuses to train.
 
+    `stochastic_rounding=True` (bf16 parameters only, and none of the master-weight options above) keeps the plain form's
+    storage - bf16 parameters and bf16 moments, nothing beside them - and runs the master-weight form's fp32 step on them,
+    rounding every stored value up or down at random so that it is an unbiased estimate of the fp32 result
+    (include/lcv_hip_sr.h): updates below half a bf16 ulp and the decay of exp_avg_sq survive in expectation.  Every `step()`
+    takes one (seed, offset) pair from the device's default generator (`ops.draw_philox_offset`, the generator moves on by 4),
+    so the steps follow `torch.manual_seed`.
+
     A subclass supplies its `param_groups` entry (through `_init`), its moment storage (`_init_moments`), its hyper-parameter
     tuple (`_hyper`) and its `STEPS`."""
     CHUNK = 2048
@@ -70,6 +77,9 @@ class FusedAdamWClip:
     # lcv_hip_anchor.h).  (anchor, moments_8bit, grad_accum > 1, master_weights) -> the entry point, the pointer tables that
     # follow the descriptors, whether param_f32 is passed (after the counts), whether grad_f32 is (before the stream).
     # A combination that is not here is one the constructor refuses.
+    # Outside the table: the stochastic-rounding step (lcv_hip_sr.h) takes the plain table, no param_f32, and `seed, offset`
+    # in front of the stream.
+    SR_STEP = "lcv_sr_adamw_step"
     STEPS = {
         (False, False, False, False): ("lcv_adamw_step", (), True, False),
         (False, False, False, True): ("lcv_master_adamw_step", ("low",), False, False),
@@ -81,11 +91,11 @@ class FusedAdamWClip:
     }
 
     def __init__(self, params, lr=2e-4, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-8, master_weights=False,
-                 moments_8bit=False, *, grad_accum: int = 1, anchor=None):
+                 moments_8bit=False, stochastic_rounding=False, *, grad_accum: int = 1, anchor=None):
         self._init(params, dict(lr=lr, betas=betas, weight_decay=weight_decay, eps=eps), master_weights, moments_8bit,
-                   grad_accum, anchor)
+                   grad_accum, anchor, stochastic_rounding)
 
-    def _init(self, params, group, master_weights, moments_8bit, grad_accum, anchor) -> None:
+    def _init(self, params, group, master_weights, moments_8bit, grad_accum, anchor, stochastic_rounding=False) -> None:
         """The constructor body of both optimizers; `group` is the `param_groups` entry without its `params`."""
         self.params = [p for p in params]
         if not self.params:
@@ -95,6 +105,7 @@ class FusedAdamWClip:
             raise _lib.LcvError(f"{type(self).__name__}: parameters must be all bf16 or all fp32")
         self.f32 = dt == F32
         self.param_groups = [dict(params=self.params, **group)]
+        self._init_stochastic_rounding(stochastic_rounding, master_weights, moments_8bit, grad_accum, anchor)
         self._init_master(master_weights)
         self._init_anchor(anchor)
         self.moments_8bit = bool(moments_8bit)
@@ -145,6 +156,28 @@ class FusedAdamWClip:
         if any(not p.is_contiguous() for p in self.params):
             raise _lib.LcvError(f"{name}: master_weights=True needs contiguous parameters")
         self._low = [torch.zeros(p.shape, dtype=torch.int16, device=p.device) for p in self.params]
+
+    def _init_stochastic_rounding(self, stochastic_rounding: bool, master_weights, moments_8bit, grad_accum, anchor) -> None:
+        """Nothing is allocated: the storage is the plain form's.  Everything that belongs to the master-weight form is refused
+        here, on the constructor's arguments, before that form's own checks ask for master_weights=True."""
+        self.stochastic_rounding = bool(stochastic_rounding)
+        if not self.stochastic_rounding:
+            return
+        name = type(self).__name__
+        if self.f32:
+            raise _lib.LcvError(f"{name}: stochastic_rounding=True is for bf16 parameters; an fp32 step rounds nothing to bf16")
+        if any(not p.is_cuda for p in self.params):
+            raise _lib.LcvError(f"{name}: stochastic_rounding=True needs parameters on the GPU (no CPU path exists)")
+        if any(not p.is_contiguous() for p in self.params):
+            raise _lib.LcvError(f"{name}: stochastic_rounding=True needs contiguous parameters")
+        if master_weights:
+            raise _lib.LcvError(f"{name}: stochastic_rounding=True cannot be combined with master_weights=True (the master "
+                                "weights are already exact)")
+        for on, what in ((moments_8bit, "moments_8bit=True"), (int(grad_accum) > 1, "grad_accum > 1"),
+                         (anchor is not None, "anchor")):
+            if on:
+                raise _lib.LcvError(f"{name}: stochastic_rounding=True cannot be combined with {what} (it exists for the "
+                                    "master-weight form only)")
 
     def _check_anchor(self, anchor):
         """A list of base words that fits `params`: contiguous bf16 GPU tensors of the parameters' shapes."""
@@ -463,12 +496,17 @@ class FusedAdamWClip:
         self._ema_guard("step()")
         t = self._step_table()
         self.step_count += 1
-        name, sides, param_f32, grad_f32 = self.STEPS[bool(self._anchor), self.moments_8bit, self.grad_accum > 1,
-                                                      self.master_weights]
-        # descriptors, tables..., n_active, total_chunks, [param_f32], coef, hyper..., [grad_f32], stream
-        ops.call(name, _ptr(t.desc), *(_ptr(t.sides[s]) for s in sides), t.n, t.chunks,
-                 *((1 if self.f32 else 0,) if param_f32 else ()), _ptr(self._norm_coef) if self._have_coef else None,
-                 *self._hyper(), *((1 if self.grad_accum > 1 else 0,) if grad_f32 else ()), _stream())
+        coef = _ptr(self._norm_coef) if self._have_coef else None
+        if self.stochastic_rounding:     # descriptors, n_active, total_chunks, coef, hyper..., seed, offset, stream
+            seed, offset = ops.draw_philox_offset(self.params[0].device)
+            ops.call(self.SR_STEP, _ptr(t.desc), t.n, t.chunks, coef, *self._hyper(), seed & _U64, offset & _U64, _stream())
+        else:
+            name, sides, param_f32, grad_f32 = self.STEPS[bool(self._anchor), self.moments_8bit, self.grad_accum > 1,
+                                                          self.master_weights]
+            # descriptors, tables..., n_active, total_chunks, [param_f32], coef, hyper..., [grad_f32], stream
+            ops.call(name, _ptr(t.desc), *(_ptr(t.sides[s]) for s in sides), t.n, t.chunks,
+                     *((1 if self.f32 else 0,) if param_f32 else ()), coef,
+                     *self._hyper(), *((1 if self.grad_accum > 1 else 0,) if grad_f32 else ()), _stream())
         self._have_coef = False
         if self.weight_ema is not None:  # the average follows the masters this step left (include/lcv_hip_ema.h)
             self._ema_update()
@@ -481,7 +519,9 @@ class FusedSGDClip(FusedAdamWClip):
     `master_weights=True` adds the int16 low words of FusedAdamWClip's master-weight form (+2 B / parameter), and with it
     `grad_accum=N` the fp32 accumulators of FusedAdamWClip's accumulation form (+4 B / parameter), or `anchor=[...]` the
     decay toward those base words of FusedAdamWClip's anchor form (nothing allocated); `enable_weight_ema(beta)` keeps the fp32
-    average of FusedAdamWClip's form (+4 B / parameter)."""
+    average of FusedAdamWClip's form (+4 B / parameter).  `stochastic_rounding=True` (without any of those) is FusedAdamWClip's
+    stochastic-rounding form: the fp32 step, a stochastically rounded bf16 store, still no state."""
+    SR_STEP = "lcv_sr_sgd_step"
     STEPS = {     # as FusedAdamWClip.STEPS (lcv_hip.h, lcv_hip_master.h, lcv_hip_accum.h, lcv_hip_anchor.h)
         (False, False, False, False): ("lcv_sgd_step", (), True, False),
         (False, False, False, True): ("lcv_master_sgd_step", ("low",), False, False),
@@ -490,8 +530,9 @@ class FusedSGDClip(FusedAdamWClip):
         (True, False, True, True): ("lcv_master_sgd_step_anchor", ("low", "anchor"), False, True),
     }
 
-    def __init__(self, params, lr=1e-5, weight_decay=0.01, master_weights=False, *, grad_accum: int = 1, anchor=None):
-        self._init(params, dict(lr=lr, weight_decay=weight_decay), master_weights, False, grad_accum, anchor)
+    def __init__(self, params, lr=1e-5, weight_decay=0.01, master_weights=False, stochastic_rounding=False, *,
+                 grad_accum: int = 1, anchor=None):
+        self._init(params, dict(lr=lr, weight_decay=weight_decay), master_weights, False, grad_accum, anchor, stochastic_rounding)
 
     def _init_moments(self) -> None:
         self.exp_avg = self.params            # the descriptor table has moment slots; SGD never reads them

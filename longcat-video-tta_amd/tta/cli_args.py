@@ -101,12 +101,17 @@ def add_optimizer_args(parser, *, master_weights_help, decay_to_base=False):
     parser.add_argument("--weight-ema-warmup", action="store_true",
                         help="with --weight-ema: BETA_t = min(BETA, (1 + t) / (10 + t)) at the t-th step, so an average that starts "
                              "at the base weights does not lag a short run")
+    parser.add_argument("--stochastic-rounding", action="store_true",
+                        help="without --master-weights: the optimizer step runs in fp32 and every bf16 value it stores (weights, "
+                             "AdamW moments) is rounded up or down at random, unbiased, so updates below half a bf16 ulp and the "
+                             "decay of the second moment survive in expectation; no extra state (include/lcv_hip_sr.h); the "
+                             "rounding bits follow --seed")
 
 
 def parse_optimizer_args(parser, argv=None):
     """parse_args, then the refusals of the optimizer options as the parser's own one-line errors (exit status 2), in this
-    order: --adam-8bit, --grad-accum, --decay-to-base, --weight-ema.  `--optimizer`, `--also-tune-delta` and `--decay-to-base`
-    count as adamw, off and off for a parser without them."""
+    order: --adam-8bit, --grad-accum, --decay-to-base, --weight-ema, --stochastic-rounding.  `--optimizer`, `--also-tune-delta`
+    and `--decay-to-base` count as adamw, off and off for a parser without them."""
     args = parser.parse_args(argv)
     master, accum, tune_delta = args.master_weights, args.grad_accum, getattr(args, "also_tune_delta", False)
     refusals = [
@@ -137,6 +142,14 @@ def parse_optimizer_args(parser, argv=None):
              "--weight-ema cannot be combined with --also-tune-delta (the fp32 delta vector has no master-weight form "
              "to average beside)"),
         ]
+    if args.stochastic_rounding:
+        refusals += [
+            (master,
+             "--stochastic-rounding cannot be combined with --master-weights (the master weights are already exact)"),
+            (tune_delta,
+             "--stochastic-rounding cannot be combined with --also-tune-delta (the fp32 delta vector has nothing to round, "
+             "and a joint run would mix the two forms)"),
+        ]
     for refused, message in refusals:
         if refused:
             parser.error(message)
@@ -148,7 +161,7 @@ def optimizer_kwargs(args) -> dict:
     kw = {"master_weights": args.master_weights, "moments_8bit": args.adam_8bit, "grad_accum": args.grad_accum}
     if hasattr(args, "decay_to_base"):
         kw["decay_to_base"] = args.decay_to_base
-    return {**kw, **weight_ema_kwargs(args)}
+    return {**kw, **weight_ema_kwargs(args), **stochastic_rounding_record(args)}
 
 
 def weight_ema_kwargs(args) -> dict:
@@ -159,6 +172,12 @@ def weight_ema_kwargs(args) -> dict:
 def weight_ema_record(args) -> dict:
     """What config.json (`training`) and the norm-tuning summary.json record of --weight-ema; nothing when the flag is absent."""
     return {} if args.weight_ema is None else {"weight_ema": args.weight_ema, "weight_ema_warmup": args.weight_ema_warmup}
+
+
+def stochastic_rounding_record(args) -> dict:
+    """`stochastic_rounding: true` for config.json (`training`), the norm-tuning summary.json, every result row and the loop
+    functions' keywords; nothing when the flag is absent."""
+    return {"stochastic_rounding": True} if getattr(args, "stochastic_rounding", False) else {}
 
 
 def _step_cache_threshold(text: str) -> float:

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from lcv_hip.ops import FusedAdamWClip
 
 from .early_stopping import AnchoredEarlyStopper
-from .inner_loop import _OneVideo, _fm_loss, run_adaptation
+from .inner_loop import _OneVideo, _fm_loss, refuse_stochastic_rounding_under_sp, run_adaptation
 from .lora import _parse_target_blocks
 
 
@@ -220,7 +220,7 @@ class FiLMAdapterWrapper(_HookedWrapper):
 def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bool, cond_latents, train_latents,
               prompt_embeds, prompt_mask, num_steps, lr, device, dtype, early_stopper, train_latents_variants,
               master_weights=False, moments_8bit=False, grad_accum=1, decay_to_base=False, info=None,
-              weight_ema=None, ema_warmup=False):
+              weight_ema=None, ema_warmup=False, stochastic_rounding=False):
     """AdamW(0.9, 0.999, wd 0.01, eps 1e-15), clip at 1.0, no warm-up (run_delta_a.py:224-305 and its siblings) on the
     shared engine.  Clipping comes in the three shapes the reference scripts use: per parameter (delta-B,
     run_delta_b.py:386-388), one global norm, or — bf16 norm weights tuned together with an fp32 delta vector — one fused
@@ -233,7 +233,13 @@ def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bo
     into `info["drift_norm"]` after the loop; an fp32 delta vector keeps its decay toward zero, which is its base.
     `weight_ema` (the norm-tuning path only, needs `master_weights`) keeps the fp32 average of the bf16 parameters over the steps
     (include/lcv_hip_ema.h), which the stopper scores and the parameters end as; like `grad_accum` it needs every parameter
-    bf16."""
+    bf16.  `stochastic_rounding` (the norm-tuning path only) gives the bf16 parameters and moments the fp32 step with
+    stochastically rounded stores (include/lcv_hip_sr.h); it too needs every parameter bf16: an fp32 vector has nothing to round,
+    and a joint run would mix the two forms."""
+    refuse_stochastic_rounding_under_sp(wrapper, stochastic_rounding)
+    if stochastic_rounding and any(p.dtype != torch.bfloat16 for p in params):
+        raise ValueError("stochastic_rounding cannot train fp32 parameters (the delta vector of --also-tune-delta): an fp32 "
+                         "step rounds nothing to bf16")
     if weight_ema is not None and any(p.dtype != torch.bfloat16 for p in params):
         raise ValueError("weight_ema cannot train fp32 parameters (the delta vector of --also-tune-delta): the average is kept "
                          "beside master weights, which their optimizer does not have")
@@ -250,7 +256,8 @@ def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bo
         groups = [params]
     opts = [FusedAdamWClip(g, lr=lr, betas=(0.9, 0.999), weight_decay=0.01, eps=1e-15,
                            master_weights=master_weights and g[0].dtype == torch.bfloat16,
-                           moments_8bit=moments_8bit and g[0].dtype == torch.bfloat16, grad_accum=grad_accum,
+                           moments_8bit=moments_8bit and g[0].dtype == torch.bfloat16,
+                           stochastic_rounding=stochastic_rounding, grad_accum=grad_accum,
                            anchor=[p.detach().clone() for p in g] if decay_to_base and g[0].dtype == torch.bfloat16 else None)
             for g in groups]
     if weight_ema is not None:
@@ -403,7 +410,8 @@ class NormTuneForward(nn.Module):
 def optimize_norm_params(wrapper: NormTuneForward, norm_params: List[nn.Parameter], cond_latents, train_latents, prompt_embeds,
                          prompt_mask, num_steps: int = 20, lr: float = 1e-3, device: str = "cuda",
                          dtype: torch.dtype = torch.bfloat16, early_stopper: Optional[AnchoredEarlyStopper] = None,
-                         train_latents_variants: Optional[List[Dict]] = None, *, weight_ema: Optional[float] = None,
+                         train_latents_variants: Optional[List[Dict]] = None, stochastic_rounding: bool = False,
+                         *, weight_ema: Optional[float] = None,
                          ema_warmup: bool = False, decay_to_base: bool = False, grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """run_norm_tune_tta.py:215-283 (same positional order: the parameter list is the second argument): AdamW(eps 1e-15) over
     `norm_params` (bf16 norm weights, plus the fp32 delta vector of --also-tune-delta), one global clip at 1.0.  Returns the
@@ -412,13 +420,16 @@ def optimize_norm_params(wrapper: NormTuneForward, norm_params: List[nn.Paramete
     vector in the list it raises.  `decay_to_base` (with `master_weights`) decays the bf16 norm weights toward their values at
     entry instead of toward zero and adds `drift_norm`, their distance from those values.  `weight_ema` (with `master_weights`;
     `ema_warmup` as in `lcv_hip.ops.ema_beta`) keeps the fp32 average of the bf16 norm weights over the steps: the stopper
-    scores it and the weights end as it; with the fp32 delta vector in the list it raises, as `grad_accum` does."""
+    scores it and the weights end as it; with the fp32 delta vector in the list it raises, as `grad_accum` does.
+    `stochastic_rounding` (without `master_weights`): the fp32 step with stochastically rounded bf16 stores
+    (include/lcv_hip_sr.h); with the fp32 delta vector in the list it raises too."""
     norm_params = list(norm_params)
     info: Dict = {}
     losses, est, es_state = _optimize(wrapper, norm_params, False, cond_latents, train_latents, prompt_embeds,
                                       prompt_mask, num_steps, lr, device, dtype, early_stopper, train_latents_variants,
                                       master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
-                                      decay_to_base=decay_to_base, info=info, weight_ema=weight_ema, ema_warmup=ema_warmup)
+                                      decay_to_base=decay_to_base, info=info, weight_ema=weight_ema, ema_warmup=ema_warmup,
+                                      stochastic_rounding=stochastic_rounding)
     out = {"losses": losses, "early_stopping_info": es_state, "es_check_time": est}
     out.update(info)
     if getattr(wrapper, "_orig", None) and len(wrapper._orig) == len(wrapper.norm_params):

@@ -21,7 +21,8 @@ import torch.nn as nn
 from lcv_hip.ops import FusedAdamWClip, FusedSGDClip
 
 from .early_stopping import AnchoredEarlyStopper
-from .inner_loop import _OneVideo, _RoundRobin, _fm_loss, _single_optimizer_step, run_adaptation
+from .inner_loop import (_OneVideo, _RoundRobin, _fm_loss, _single_optimizer_step, refuse_stochastic_rounding_under_sp,
+                         run_adaptation)
 
 
 def snapshot_base_state(dit: nn.Module) -> Dict[str, torch.Tensor]:
@@ -62,6 +63,19 @@ def _make_optimizer(kind: str, params, lr: float, weight_decay: float, master_we
     raise ValueError(f"unknown optimizer_type {kind!r} (sgd | adamw)")
 
 
+def _make_sr_optimizer(kind: str, params, lr: float, weight_decay: float, **master_form):
+    """`_make_optimizer` for `stochastic_rounding` (include/lcv_hip_sr.h): same hyper-parameters, the plain form's storage.
+    `master_form` are `_make_optimizer`'s master-weight keywords, passed on so that the constructors refuse them by name."""
+    if kind == "adamw":
+        return FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8, stochastic_rounding=True,
+                              **master_form)
+    if kind == "sgd":
+        if master_form.pop("moments_8bit", False):
+            raise ValueError("moments_8bit is for optimizer_type 'adamw': SGD keeps no moments")
+        return FusedSGDClip(params, lr=lr, weight_decay=weight_decay, stochastic_rounding=True, **master_form)
+    raise ValueError(f"unknown optimizer_type {kind!r} (sgd | adamw)")
+
+
 def _anchors(dit: nn.Module, base_state: Optional[Dict[str, torch.Tensor]]) -> List[torch.Tensor]:
     """The base words of the trainable parameters, in `_trainable` order: the `base_state` entries matched by name (not
     copied), or bf16 clones of the parameters as they are now."""
@@ -75,8 +89,10 @@ def _anchors(dit: nn.Module, base_state: Optional[Dict[str, torch.Tensor]]) -> L
 
 
 def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper, optimizer_type,
-         *, master_weights, moments_8bit, grad_accum, decay_to_base, base_state, weight_ema, ema_warmup):
+         *, master_weights, moments_8bit, grad_accum, decay_to_base, base_state, weight_ema, ema_warmup,
+         stochastic_rounding=False):
     params = _trainable(dit)
+    refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
     # `decay_to_base`: the weight decay pulls toward the base words (include/lcv_hip_anchor.h), which are the caller's
     # `base_state` entries or, without one, +2 B / parameter of clones; a `base_state` alone only measures the drift
     want_drift = bool(decay_to_base) or base_state is not None
@@ -84,8 +100,13 @@ def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, de
     # made per call, so per video: the per-video reset writes the bf16 words, and the low words of `master_weights`
     # (+2 B / parameter; AdamW: +8 B of fp32 moments, or +2.016 B of 8-bit ones under `moments_8bit`) start at zero next to them;
     # `grad_accum` > 1 adds +4 B / parameter of fp32 accumulators (54 GB for the whole model: a memory decision)
-    opt = _make_optimizer(optimizer_type, params, lr, weight_decay, master_weights, moments_8bit, grad_accum,
-                          anchor=anchor if decay_to_base else None)
+    # `stochastic_rounding` allocates nothing: SGD stays at 0 B of state, AdamW at its two bf16 moments
+    if stochastic_rounding:
+        opt = _make_sr_optimizer(optimizer_type, params, lr, weight_decay, master_weights=master_weights,
+                                 moments_8bit=moments_8bit, grad_accum=grad_accum, anchor=anchor if decay_to_base else None)
+    else:
+        opt = _make_optimizer(optimizer_type, params, lr, weight_decay, master_weights, moments_8bit, grad_accum,
+                              anchor=anchor if decay_to_base else None)
     if weight_ema is not None:                 # +4 B / parameter of fp32 average (54 GB for the whole model: a memory decision);
         opt.enable_weight_ema(weight_ema, ema_warmup)   # run_adaptation scores it and leaves it in the parameters
     out = run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
@@ -103,22 +124,25 @@ def finetune_full_on_conditioning(dit: nn.Module, cond_latents: torch.Tensor, tr
                                   max_grad_norm: float = 1.0, device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                                   early_stopper: Optional[AnchoredEarlyStopper] = None,
                                   train_latents_variants: Optional[List[Dict]] = None, optimizer_type: str = "sgd",
+                                  stochastic_rounding: bool = False,
                                   *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                                   decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
                                   grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
     return _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper,
                 optimizer_type, master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
-                decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup)
+                decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup,
+                stochastic_rounding=stochastic_rounding)
 
 
 def finetune_full_batch(dit: nn.Module, batch_data: List[Dict], num_steps: int = 10, lr: float = 1e-5, warmup_steps: int = 2,
                         weight_decay: float = 0.01, max_grad_norm: float = 1.0, device: str = "cuda",
-                        dtype: torch.dtype = torch.bfloat16, optimizer_type: str = "sgd",
+                        dtype: torch.dtype = torch.bfloat16, optimizer_type: str = "sgd", stochastic_rounding: bool = False,
                         *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                         decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Round-robin over the eval video and its retrieved neighbours (run_full_tta.py:230-306); no early stopping."""
     return _run(dit, _RoundRobin(batch_data, device), num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype,
                 None, optimizer_type, master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
-                decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup)
+                decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup,
+                stochastic_rounding=stochastic_rounding)

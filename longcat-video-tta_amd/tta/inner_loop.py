@@ -233,6 +233,14 @@ def _sp_sync(dit, opt) -> Optional[Callable[[], None]]:
     return lambda: dit.sequence_parallel_sync_grads(opt.params)
 
 
+def refuse_stochastic_rounding_under_sp(module, stochastic_rounding: bool) -> None:
+    """Every sequence-parallel rank would have to draw the same (seed, offset) pair for its replica of the parameters; the
+    ranks' generators are not tied, so the combination is refused."""
+    if stochastic_rounding and getattr(getattr(module, "dit", module), "_sp_group", None) is not None:
+        raise ValueError("stochastic_rounding cannot be combined with sequence parallelism (every rank would have to draw "
+                         "the same rounding bits)")
+
+
 # ------------------------------------------------------------------------------------------------ public: LoRA
 def _adapter_params(lora_modules, lora_param_fn) -> List[torch.Tensor]:
     params = lora_param_fn() if lora_param_fn is not None else get_lora_parameters(lora_modules)
@@ -247,13 +255,17 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
                                   warmup_steps: int = 3, weight_decay: float = 0.01, max_grad_norm: float = 1.0,
                                   device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                                   early_stopper: Optional[AnchoredEarlyStopper] = None, lora_param_fn=None,
-                                  train_latents_variants: Optional[List[Dict]] = None,
+                                  train_latents_variants: Optional[List[Dict]] = None, stochastic_rounding: bool = False,
                                   *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                                   grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
+    """`stochastic_rounding`: the bf16 adapters and moments take the fp32 step with stochastically rounded stores
+    (include/lcv_hip_sr.h); no state beside them, so the stopper's snapshot and restore are the plain form's."""
     params = _adapter_params(lora_modules, lora_param_fn)
+    refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
     # made per call, so per video: the low words of `master_weights` start at zero next to freshly reset adapters
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
-                         master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum)
+                         master_weights=master_weights, moments_8bit=moments_8bit, stochastic_rounding=stochastic_rounding,
+                         grad_accum=grad_accum)
     if weight_ema is not None:       # the fp32 average of the adapters (+4 B / parameter): scored by the stopper, left in the
         opt.enable_weight_ema(weight_ema, ema_warmup)    # adapters at the end (see run_adaptation)
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
@@ -264,14 +276,17 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
 def finetune_lora_batch(dit: nn.Module, lora_modules, batch_data: List[Dict], num_steps: int = 20, lr: float = 2e-4,
                         warmup_steps: int = 3, weight_decay: float = 0.01, max_grad_norm: float = 1.0,
                         device: str = "cuda", dtype: torch.dtype = torch.bfloat16, lora_param_fn=None,
+                        stochastic_rounding: bool = False,
                         *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Shared adapters trained round-robin over the eval video and its neighbours; no early stopping (:558-634).  The feed
     receives the micro-step index, so `grad_accum` = number of videos puts every video behind each update.  `weight_ema`: the
-    adapters end as their fp32 average over the steps."""
+    adapters end as their fp32 average over the steps.  `stochastic_rounding`: as in `finetune_lora_on_conditioning`."""
     params = _adapter_params(lora_modules, lora_param_fn)
+    refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
-                         master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum)
+                         master_weights=master_weights, moments_8bit=moments_8bit, stochastic_rounding=stochastic_rounding,
+                         grad_accum=grad_accum)
     if weight_ema is not None:
         opt.enable_weight_ema(weight_ema, ema_warmup)
     feed = _RoundRobin(batch_data, device)

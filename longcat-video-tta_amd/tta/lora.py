@@ -10,7 +10,7 @@ mask is a pure function of (seed, offset, element index) (include/lcv_hip_lora.h
   backward  dx = dy W (plain GEMM) + mask * scale * (g A) by lora_dx_dropout_add;  dA = g^T xd by tn_skinny_dropout
 """
 import math
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional
 
 import torch
 import torch.nn as nn
@@ -65,15 +65,9 @@ class _LoRALinearFn(torch.autograd.Function):
 DRAW_HOOK: Optional[Callable] = None
 
 
-def draw_dropout_offset(device: torch.device) -> Tuple[int, int]:
-    """One (seed, offset) pair for one mask, from the device's default generator: its seed and its current Philox offset,
-    which is then advanced by 4 (the granularity the generator accepts).  Host-side state only: no device-to-host sync.  It
-    follows torch.manual_seed, and torch.utils.checkpoint's RNG preservation replays it for a recomputed block."""
-    index = device.index if device.index is not None else torch.cuda.current_device()
-    gen = torch.cuda.default_generators[index]
-    seed, offset = gen.initial_seed(), gen.get_offset()
-    gen.set_offset(offset + 4)
-    return seed, offset
+# one (seed, offset) pair for one mask, from the device's default generator; the stochastic-rounding optimizer steps draw theirs
+# the same way, so the definition lives beside the kernels' wrappers
+draw_dropout_offset = ops.draw_philox_offset
 
 
 class LoRALinear(nn.Module):
