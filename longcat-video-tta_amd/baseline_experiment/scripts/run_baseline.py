@@ -43,6 +43,7 @@ def build_parser():
     C.add_step_cache_args(p)
     C.add_solver_arg(p)
     C.add_cfg_reuse_args(p)
+    C.add_apg_args(p)
     return p
 
 
@@ -76,7 +77,7 @@ def main(argv=None):
             out, dt = R.generate_continuation(pipe, blob, args, idx, device, num_frames=num_frames, entry=e)
             row = {"idx": idx, "index": idx, "filename": e["name"], "caption": blob.get("caption", ""), "psnr": None,
                    "ssim": None, "lpips": None, "resolution": args.resolution, "inference_time_s": round(dt, 2),
-                   **C.step_cache_result(blob), **C.cfg_reuse_result(blob)}
+                   **C.step_cache_result(blob), **C.cfg_reuse_result(blob), **C.apg_result(blob)}
             if pipe.vae is not None:
                 t1 = time.time()
                 frames = pipe.decode_to_frames(out)
@@ -132,6 +133,9 @@ def main(argv=None):
             **({**C.cfg_reuse_record(args),
                 "cfg_reuse_per_video": {r["filename"]: r["cfg_reuse"] for r in merged if "cfg_reuse" in r}}
                if C.cfg_reuse_record(args) else {}),
+            # --apg: likewise
+            **({**C.apg_record(args), "apg_per_video": {r["filename"]: r["apg"] for r in merged if "apg" in r}}
+               if C.apg_record(args) else {}),
         }
         with open(out_dir / "summary.json", "w") as f:
             json.dump(summary, f, indent=2)

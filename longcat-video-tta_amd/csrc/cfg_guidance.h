@@ -1,5 +1,6 @@
-// The CFG-zero-star guidance math of the denoise step, defined once for the three files that use it: elementwise.hip (the fused
-// Euler step), solver_step.hip (the multistep step) and cfg_reuse.hip (the stored correction).
+// The CFG-zero-star guidance math of the denoise step, defined once for the files that use it: elementwise.hip (the fused
+// Euler step), solver_step.hip (the multistep step), cfg_reuse.hip (the stored correction) and cfg_apg.hip (the projected
+// guidance: the sums, st and the joins; its rule for v is its own).
 //
 //   st = <c, u> / (<u, u> + 1e-8) per sample,   u' = u * st,   v = u' + g * (c - u')
 //
@@ -43,7 +44,9 @@ __device__ __forceinline__ void cfg_pair_join(float& a, float& b, CfgJoinLds& sa
 
 // The body of the partial-sum kernel, launched CFG_PARTS x B workgroups of CFG_THREADS: ws[b][part][2] = the (dot, nrm) of the
 // elements part * 256 + t + k * 65536 of sample b.  The stride is fixed, so every slot is written (an empty slice writes 0).
+// SLOTS: the floats a part owns in ws; the pair sits in the first two (cfg_apg.hip keeps four per part, the others keep the pair).
 // (The pointers carry no __restrict__ here: the kernels' own parameters do, and the inlined copies only add alias scopes.)
+template <int SLOTS = 2>
 __device__ __forceinline__ void cfg_partial_sums(const float* cond, const float* uncond, float* ws, int64_t n, CfgJoinLds& sa,
                                                  CfgJoinLds& sb) {
   const int64_t b = blockIdx.y;
@@ -61,15 +64,16 @@ __device__ __forceinline__ void cfg_partial_sums(const float* cond, const float*
   if (threadIdx.x == 0) {
     float part_dot, part_nrm;
     cfg_pair_total(part_dot, part_nrm, sa, sb);
-    float* o = ws + (b * CFG_PARTS + blockIdx.x) * 2;
+    float* o = ws + (b * CFG_PARTS + blockIdx.x) * SLOTS;
     o[0] = part_dot;
     o[1] = part_nrm;
   }
 }
 
 // st of sample b from its CFG_PARTS partial pairs; all CFG_THREADS threads of the workgroup call it
+template <int SLOTS = 2>
 __device__ __forceinline__ float cfg_star_scale(const float* ws, int64_t b, CfgJoinLds& sa, CfgJoinLds& sb) {
-  const float* o = ws + (b * CFG_PARTS + threadIdx.x) * 2;
+  const float* o = ws + (b * CFG_PARTS + threadIdx.x) * SLOTS;
   float dot = o[0], nrm = o[1];
   cfg_pair_join(dot, nrm, sa, sb);
   const float den = nrm + 1e-8f;

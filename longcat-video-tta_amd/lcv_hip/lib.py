@@ -159,6 +159,12 @@ _SIGNATURES_CFGREUSE = {
     "lcv_cfg_delta_apply": [P, P, P, I64, I64, P],
 }
 
+# include/lcv_hip_apg.h (a header of its own: the adaptive projected guidance of the CFG denoise loop): (cond, uncond, diff, v, ws, out,
+# B, n, float guidance, eta, radius, beta, int use_zero_star, have_momentum); returns int
+_SIGNATURES_APG = {
+    "lcv_cfg_apg": [P, P, P, P, P, P, I64, I64, F32, F32, F32, F32, I, I, P],
+}
+
 # include/lcv_hip_sr.h (a header of its own: stochastic rounding for the bf16 optimizer steps): the steps take lcv_master_*_step's
 # arguments without `low` and with uint64 `seed, offset` in front of the stream; round takes (x fp32, out bf16, n, seed, offset)
 _SIGNATURES_SR = {
@@ -226,7 +232,7 @@ def load():
                        + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())
                        + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())
                        + list(_SIGNATURES_STEPCACHE.items()) + list(_SIGNATURES_SOLVER.items())
-                       + list(_SIGNATURES_CFGREUSE.items()) + list(_SIGNATURES_SR.items())):
+                       + list(_SIGNATURES_CFGREUSE.items()) + list(_SIGNATURES_SR.items()) + list(_SIGNATURES_APG.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

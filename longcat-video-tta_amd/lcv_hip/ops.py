@@ -480,6 +480,42 @@ def cfg_delta_apply(cond: torch.Tensor, delta: torch.Tensor, out: Optional[torch
     return out
 
 
+# the adaptive projected guidance of the CFG denoise loop (include/lcv_hip_apg.h; the settings live in longcat_video/apg.py)
+_APG_WS = {}         # (device index, B) -> the [2, B, 256, 4] partial sums of lcv_cfg_apg (kept alive here)
+
+
+def cfg_apg_workspace(B: int, device) -> torch.Tensor:
+    """The zero-star partial pairs (dot, nrm, 0, 0), then the correction's partial sums (dd, dc, cc, 0): 256 per sample each,
+    every slot written by the call that reads it, cached per (device, B)."""
+    key = (torch.device(device).index, int(B))
+    ws = _APG_WS.get(key)
+    if ws is None:
+        ws = _APG_WS[key] = torch.empty((2, int(B), 256, 4), dtype=F32, device=device)
+    return ws
+
+
+def cfg_apg(cond: torch.Tensor, uncond: torch.Tensor, diff: torch.Tensor, guidance: float, eta: float, radius: Optional[float],
+            beta: float, zero_star: bool, have_momentum: bool, out: Optional[torch.Tensor] = None,
+            v: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The projected-guidance output of (cond, uncond) over [B, ...] fp32 tensors: diff = (cond - uncond') [+ beta * diff when
+    `have_momentum`], written in place, then v = cond + (guidance - 1) ((s diff - p) + eta p) with p the part of s diff along
+    cond and s = min(1, radius / ||diff||) (`radius` None or <= 0: no cap).  `v` may be cond (default: a new tensor); with `out`
+    ([B, 4] fp32) out[b] = (<d, d>, <d, c>, <c, c>, s) in a fixed order.  Nothing is synchronised."""
+    if v is None:
+        v = torch.empty_like(cond)
+    _cfgreuse_req("cfg_apg", cond, uncond, diff, v)
+    B = diff.shape[0]
+    n = diff.numel() // max(B, 1)
+    if out is not None:
+        _req(out, F32, "cfg_apg.out")
+        if out.numel() != 4 * B or not out.is_contiguous():
+            raise _lib.LcvError(f"cfg_apg: out needs {4 * B} contiguous fp32 words, got {out.numel()}")
+    ws = cfg_apg_workspace(B, diff.device)
+    call("lcv_cfg_apg", _ptr(cond), _ptr(uncond), _ptr(diff), _ptr(v), _ptr(ws), _ptr(out), B, n, float(guidance), float(eta),
+         0.0 if radius is None else float(radius), float(beta), 1 if zero_star else 0, 1 if have_momentum else 0, _stream())
+    return v
+
+
 # the first-block step cache of the denoise loop (include/lcv_hip_stepcache.h; the policy lives in longcat_video/step_cache.py)
 _STEPCACHE_CHUNK = 2048
 _STEPCACHE_WS = {}   # (device index, rows, n) -> the partial-sum workspace of lcv_stepcache_diff (kept alive here)

@@ -46,9 +46,9 @@ def retrieve_latents(encoder_output, generator=None, sample_mode: str = "sample"
     raise AttributeError("could not access latents of the provided encoder_output")
 
 
-def _denoise_options(step_cache, solver, cfg_reuse) -> dict:
+def _denoise_options(step_cache, solver, cfg_reuse, apg=None) -> dict:
     """The optional keywords of `denoise()` that are set: with none of them a `generate_*` call is the plain call."""
-    options = {"step_cache": step_cache, "solver": solver, "cfg_reuse": cfg_reuse}
+    options = {"step_cache": step_cache, "solver": solver, "cfg_reuse": cfg_reuse, "apg": apg}
     return {k: v for k, v in options.items() if v is not None}
 
 
@@ -64,6 +64,7 @@ class LongCatVideoPipeline:
         self._kv_cache = None
         self.last_step_cache_stats = None      # StepCache.stats() of the last denoise() that had one
         self.last_cfg_reuse_stats = None       # GuidanceReuse.stats() of the last denoise() that had one
+        self.last_apg_stats = None             # ProjectedGuidance.stats() of the last denoise() that had one
 
     def to(self, device):
         self.device = torch.device(device)
@@ -108,7 +109,7 @@ class LongCatVideoPipeline:
                 negative_embeds: Optional[torch.Tensor] = None, negative_mask: Optional[torch.Tensor] = None,
                 num_cond_latents: int = 0, num_inference_steps: int = 50, guidance_scale: float = 4.0,
                 use_kv_cache: bool = True, step_callback=None, start_step: int = 0, stop_step: Optional[int] = None,
-                step_cache=None, solver=None, cfg_reuse=None):
+                step_cache=None, solver=None, cfg_reuse=None, apg=None):
         """latents fp32 [1, C, T, h, w]; the first `num_cond_latents` frames are clean conditioning frames.
         Returns the fully denoised latents (fp32, conditioning frames untouched).
         `step_cache`: a threshold or a `StepCache` (longcat_video/step_cache.py): steps whose first-block residual is within
@@ -123,7 +124,20 @@ class LongCatVideoPipeline:
         run both rows as today and store the guidance correction v - c; the steps between run the prompt row alone at batch 1
         and add the stored correction back before the unguided update.  Needs guidance; not with a step cache or sequence
         parallelism; no hipGraph is captured while it is attached (the batch changes); a split denoise restarts the schedule.
-        The statistics are left in `self.last_cfg_reuse_stats`."""
+        The statistics are left in `self.last_cfg_reuse_stats`.
+        `apg`: a `ProjectedGuidance` (longcat_video/apg.py): every guided step forms its guided output by adaptive projected
+        guidance (the correction's part along the prompt row's output scaled by eta, its norm capped, an optional momentum) in
+        launches of its own (include/lcv_hip_apg.h) and hands it to the unguided update, under either solver and with a step
+        cache.  Needs guidance; not with `cfg_reuse` (its stored correction is the plain rule's) or sequence parallelism; a
+        split denoise restarts the momentum.  The statistics are left in `self.last_apg_stats`."""
+        self.last_apg_stats = None
+        if apg is not None:
+            if not (guidance_scale > 1.0 and negative_embeds is not None):
+                raise ValueError("apg needs guidance: guidance_scale > 1 and negative embeddings")
+            if cfg_reuse is not None:
+                raise ValueError("apg cannot be combined with cfg_reuse: the stored correction is the plain rule's")
+            if getattr(self.dit, "_sp_group", None) is not None:
+                raise ValueError("apg has no sequence-parallel form")
         reuse = None
         self.last_cfg_reuse_stats = None
         if cfg_reuse is not None:
@@ -218,6 +232,8 @@ class LongCatVideoPipeline:
         x_static = ts_static = pred_static = None
         if reuse is not None:
             reuse.begin(start_step, stop)
+        if apg is not None:
+            apg.begin(start_step, stop)
         for i in range(start_step, stop):
             t = timesteps[i]
             full = reuse is None or reuse.is_full(i)
@@ -249,6 +265,9 @@ class LongCatVideoPipeline:
             dt = sched.dt(i)
             if not full:
                 on_target(lambda c, _, x: update(reuse.apply(c), None, x, i, dt), pred, None)
+            elif apg is not None:                       # the guided output in launches of its own, then the unguided update
+                on_target(lambda c, u, x: update(apg.guide(c, u, guidance_scale, self.use_zero_star, i), None, x, i, dt),
+                          *rows(pred))
             else:
                 on_target(lambda c, u, x: update(c, u, x, i, dt), *rows(pred))
                 if reuse is not None:                   # a full step: today's step above, then delta = v - c of its two rows
@@ -258,6 +277,8 @@ class LongCatVideoPipeline:
         sched._step_index = stop
         if reuse is not None:
             self.last_cfg_reuse_stats = reuse.stats()
+        if apg is not None:
+            self.last_apg_stats = apg.stats()
         if cache is not None:
             self.last_step_cache_stats = cache.stats()
         if cond is not None:
@@ -292,7 +313,7 @@ class LongCatVideoPipeline:
                     num_inference_steps: int = 50, guidance_scale: float = 4.0, generator=None,
                     use_kv_cache: bool = True, offload_kv_cache: bool = False, prompt_embeds=None,
                     prompt_mask=None, negative_embeds=None, negative_mask=None, output_type: str = "np",
-                    step_cache=None, solver=None, cfg_reuse=None, **kw):
+                    step_cache=None, solver=None, cfg_reuse=None, apg=None, **kw):
         """Video continuation: `video` is a list of PIL frames (or a [T,H,W,3] uint8/float array); the last
         `num_cond_frames` are VAE-encoded as clean conditioning latents."""
         H, W = RESOLUTIONS[resolution]
@@ -311,7 +332,7 @@ class LongCatVideoPipeline:
         noise[:, :, :ncl] = cond
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=ncl, num_inference_steps=num_inference_steps,
                            guidance_scale=guidance_scale, use_kv_cache=use_kv_cache,
-                           **_denoise_options(step_cache, solver, cfg_reuse))
+                           **_denoise_options(step_cache, solver, cfg_reuse, apg))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]
@@ -321,7 +342,7 @@ class LongCatVideoPipeline:
                      width: int = 832, num_frames: int = 93, num_inference_steps: int = 50,
                      guidance_scale: float = 4.0, generator=None, prompt_embeds=None, prompt_mask=None,
                      negative_embeds=None, negative_mask=None, output_type: str = "np", step_cache=None,
-                     solver=None, cfg_reuse=None, **kw):
+                     solver=None, cfg_reuse=None, apg=None, **kw):
         do_cfg = guidance_scale > 1.0
         pe, pm, ne, nm = self._prep_text(prompt, negative_prompt, prompt_embeds, prompt_mask, negative_embeds,
                                          negative_mask, do_cfg)
@@ -330,7 +351,7 @@ class LongCatVideoPipeline:
         C = self.dit.config.in_channels
         noise = torch.randn((1, C, T_lat, h, w), generator=generator, device=self.device, dtype=torch.float32)
         lat = self.denoise(noise, pe, pm, ne, nm, num_cond_latents=0, num_inference_steps=num_inference_steps,
-                           guidance_scale=guidance_scale, **_denoise_options(step_cache, solver, cfg_reuse))
+                           guidance_scale=guidance_scale, **_denoise_options(step_cache, solver, cfg_reuse, apg))
         if output_type == "latent":
             return [lat]
         return [self._decode_to_numpy(lat)]

@@ -70,7 +70,8 @@ def full_method(args) -> R.TTAMethod:
                 "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                                "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
                                "resolution": args.resolution, **C.step_cache_record(args),
-                               **C.solver_record(args), **C.cfg_reuse_record(args)},
+                               **C.solver_record(args), **C.cfg_reuse_record(args),
+                               **C.apg_record(args)},
                 "seed": args.seed, "max_videos": args.max_videos,
                 **{k: v for k, v in gate.items() if k != "clip_gate_stats"},
                 "clip_gate": {"enabled": args.clip_gate_enabled, "threshold": args.clip_gate_threshold,

@@ -218,6 +218,7 @@ def parse_with_step_cache(parser, argv=None, parse=None):
     if args.step_cache_max_skip is not None and args.step_cache is None:
         parser.error("--step-cache-max-skip needs --step-cache THRESH")
     check_cfg_reuse_args(parser, args)
+    check_apg_args(parser, args)
     return args
 
 
@@ -322,6 +323,77 @@ def cfg_reuse_result(blob) -> dict:
     """The per-video `cfg_reuse` entry (`GuidanceReuse.stats()`, left in the blob by generate_continuation); nothing without the
     flag."""
     return {"cfg_reuse": blob["_cfg_reuse"]} if "_cfg_reuse" in blob else {}
+
+
+class _ApgValue(argparse.Action):
+    """Stores the value and notes on the namespace that the flag was given, so that a value equal to the default is still refused
+    without --apg."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        namespace.apg_flags_given = getattr(namespace, "apg_flags_given", ()) + (option_string,)
+
+
+def add_apg_args(parser):
+    parser.add_argument("--apg", action="store_true",
+                        help="adaptive projected guidance of the CFG denoise loop (include/lcv_hip_apg.h, longcat_video/apg.py): "
+                             "the guidance correction is split into its part along the prompt row's output, which inflates the "
+                             "magnitude at a large --guidance-scale, and the part orthogonal to it; no further forward pass; no "
+                             "setting is recommended")
+    parser.add_argument("--apg-eta", type=float, default=0.0, metavar="ETA", action=_ApgValue,
+                        help="with --apg: the weight of the parallel part (default 0.0: dropped; 1 with no threshold and no "
+                             "momentum is plain guidance in value)")
+    parser.add_argument("--apg-norm-threshold", type=float, default=None, metavar="R", action=_ApgValue,
+                        help="with --apg: cap the correction's norm at R per element (RMS), so one value serves every resolution "
+                             "(default: no cap)")
+    parser.add_argument("--apg-momentum", type=float, default=0.0, metavar="BETA", action=_ApgValue,
+                        help="with --apg: add BETA times the previous step's correction, BETA in (-1, 1); a negative value damps "
+                             "what the last steps already pushed (default 0.0)")
+
+
+def check_apg_args(parser, args) -> None:
+    """The refusals of --apg as the parser's own one-line error (exit status 2).  Called from `parse_with_step_cache`, which
+    every runner parses through."""
+    import math
+    if not getattr(args, "apg", False):
+        for flag in getattr(args, "apg_flags_given", ()):
+            parser.error(f"{flag} needs --apg")
+        return
+    eta, thr, beta = args.apg_eta, args.apg_norm_threshold, args.apg_momentum
+    if getattr(args, "cfg_reuse", None) is not None:
+        parser.error("--apg cannot be combined with --cfg-reuse (the stored correction is the plain rule's)")
+    if not args.guidance_scale > 1.0:
+        parser.error(f"--apg needs guidance: --guidance-scale must be > 1, got {args.guidance_scale}")
+    if not math.isfinite(eta):
+        parser.error(f"--apg-eta ETA must be a finite number, got {eta}")
+    if thr is not None and not (thr > 0.0 and math.isfinite(thr)):        # a NaN fails too
+        parser.error(f"--apg-norm-threshold R must be a finite number > 0, got {thr}")
+    if not -1.0 < beta < 1.0:                                               # likewise
+        parser.error(f"--apg-momentum BETA must be in (-1, 1), got {beta}")
+
+
+def apg_from_args(args):
+    """A fresh `ProjectedGuidance` for one continuation, or None when the flag is absent (then nothing is imported or
+    allocated)."""
+    if not getattr(args, "apg", False):
+        return None
+    from longcat_video.apg import ProjectedGuidance
+    return ProjectedGuidance(eta=args.apg_eta, norm_threshold=args.apg_norm_threshold, momentum=args.apg_momentum)
+
+
+def apg_record(args) -> dict:
+    """What config.json (`generation`) and the flat summary.json of the runners without one record of --apg; nothing when the
+    flag is absent."""
+    if not getattr(args, "apg", False):
+        return {}
+    return {"apg": True, "apg_eta": args.apg_eta, "apg_norm_threshold": args.apg_norm_threshold,
+            "apg_momentum": args.apg_momentum}
+
+
+def apg_result(blob) -> dict:
+    """The per-video `apg` entry (`ProjectedGuidance.stats()`, left in the blob by generate_continuation); nothing without the
+    flag."""
+    return {"apg": blob["_apg"]} if "_apg" in blob else {}
 
 
 def normalize_tta_frame_args(args):

@@ -100,7 +100,7 @@ def encode_prompt(tokenizer, text_encoder, prompt: str, device: str = "cuda", dt
 def generate_video_continuation(pipe, video_frames: list, prompt: str, num_cond_frames: int = 13, num_frames: int = 93,
                                 num_inference_steps: int = 50, guidance_scale: float = 4.0, seed: int = 42,
                                 resolution: str = "480p", device: str = "cuda", use_kv_cache: bool = True, step_cache=None,
-                                solver=None, cfg_reuse=None, **embeds) -> np.ndarray:
+                                solver=None, cfg_reuse=None, apg=None, **embeds) -> np.ndarray:
     """list of PIL frames (or a [T,H,W,3] array) + prompt -> np.ndarray [N, H, W, 3] in [0, 1]; `**embeds` may carry
     precomputed prompt_embeds / prompt_mask / negative_embeds / negative_mask when no text encoder is attached.  The frame
     count is rounded up to 1 + 4k (what the causal VAE can decode) and the noise comes from a generator seeded per call.
@@ -111,6 +111,8 @@ def generate_video_continuation(pipe, video_frames: list, prompt: str, num_cond_
         embeds = dict(embeds, solver=solver)
     if cfg_reuse is not None:               # an interval or a `GuidanceReuse` (longcat_video/cfg_reuse.py); None makes the plain call
         embeds = dict(embeds, cfg_reuse=cfg_reuse)
+    if apg is not None:                     # a `ProjectedGuidance` (longcat_video/apg.py); None makes the plain call
+        embeds = dict(embeds, apg=apg)
     from .latent_split import num_frames_valid
     rng = torch.Generator(device=device).manual_seed(seed)
     clips = pipe.generate_vc(video=video_frames, prompt=prompt, resolution=resolution, num_frames=num_frames_valid(num_frames),

@@ -44,6 +44,7 @@ def add_common_args(p):
     C.add_step_cache_args(p)
     C.add_solver_arg(p)
     C.add_cfg_reuse_args(p)
+    C.add_apg_args(p)
 
 
 def add_shared_groups(p, clip_gate: bool = True):
@@ -258,7 +259,8 @@ def generate_continuation(pipe, blob, args, idx, device, num_frames=None, entry=
     """KV-cached CFG continuation from the clean conditioning latents (`generate_video_continuation`, common.py:566-611).
     The conditioning encode is inside the timed region, as in the reference.  Returns (denoised latents, seconds); the
     origin of the conditioning latents is left in `blob["_cond_source"]` for the per-video result, and with `--step-cache` the
-    cache's statistics in `blob["_step_cache"]`, with `--cfg-reuse` the reuse's in `blob["_cfg_reuse"]`."""
+    cache's statistics in `blob["_step_cache"]`, with `--cfg-reuse` the reuse's in `blob["_cfg_reuse"]`, with `--apg` the
+    projected guidance's in `blob["_apg"]`."""
     torch.cuda.synchronize()
     t0 = time.time()
     n_valid = num_frames_valid(num_frames if num_frames is not None else args.num_frames)
@@ -272,14 +274,18 @@ def generate_continuation(pipe, blob, args, idx, device, num_frames=None, entry=
     cache = C.step_cache_from_args(args)               # --step-cache: None when the flag is absent, and the call is the plain one
     solver = C.solver_from_args(args)                  # --solver: None for euler, likewise
     reuse = C.cfg_reuse_from_args(args)                # --cfg-reuse: one object per continuation; None when absent, likewise
+    apg = C.apg_from_args(args)                        # --apg: likewise
     out = pipe.denoise(lat, blob["prompt_embeds"], blob["prompt_mask"], blob.get("negative_embeds"), blob.get("negative_mask"),
                        num_cond_latents=ncl, num_inference_steps=args.num_inference_steps,
                        guidance_scale=args.guidance_scale, use_kv_cache=True, **({} if cache is None else {"step_cache": cache}),
-                       **({} if solver is None else {"solver": solver}), **({} if reuse is None else {"cfg_reuse": reuse}))
+                       **({} if solver is None else {"solver": solver}), **({} if reuse is None else {"cfg_reuse": reuse}),
+                       **({} if apg is None else {"apg": apg}))
     if cache is not None:
         blob["_step_cache"] = pipe.last_step_cache_stats
     if reuse is not None:
         blob["_cfg_reuse"] = pipe.last_cfg_reuse_stats
+    if apg is not None:
+        blob["_apg"] = pipe.last_apg_stats
     torch.cuda.synchronize()
     return out, time.time() - t0
 
@@ -464,6 +470,7 @@ def run_tta_job(args, m: TTAMethod):
                 result["gen_time"] = gen_time
                 result.update(C.step_cache_result(blob))
                 result.update(C.cfg_reuse_result(blob))
+                result.update(C.apg_result(blob))
             result.update(m.row_extra(tr, variants, blob))
             result["total_time"] = train_time + gen_time
             if m.on_success is not None:
@@ -530,7 +537,8 @@ def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Cal
 
     def summary_extra(merged, ok):
         return {**summary_head, **(clip_gate_summary(args) if hasattr(args, "clip_gate_enabled") else {}),
-                **C.step_cache_record(args), **C.solver_record(args), **C.cfg_reuse_record(args)}
+                **C.step_cache_record(args), **C.solver_record(args), **C.cfg_reuse_record(args),
+                **C.apg_record(args)}
 
     run_tta_job(args, TTAMethod(name=method, file_suffix=file_suffix, prepare=freeze, adapt=adapt, row_extra=row_extra,
                                 summary_extra=summary_extra, make_model=make_wrapper, generating=_hooks_installed,
