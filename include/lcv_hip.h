@@ -172,7 +172,9 @@ const char* lcv_attn_fwd_last_kernel(void);
  * plus qsplit*B*H*Nk*256 when the query sweep of a short-key call (Nk <= 128: the 77-key text cross-attention) is split over
  * workgroups - one fp32 dK / dV slice per split, added in split order by a finishing kernel (the size is an UPPER bound: the
  * slices are counted for every call of such sizes, also the unit-scale ones whose pass A does not use them).  accumulate_kv != 0 adds into the
- * existing dk/dv (second region of the conditioning split).  dq/dk/dv are addressed like q/k/v with their own strides. */
+ * existing dk/dv (second region of the conditioning split).  dq/dk/dv are addressed like q/k/v with their own strides.
+ * Refused (LCV_EINVAL, nothing launched): input strides that are no multiples of 8 elements, gradient strides no multiples of 4,
+ * q / k / v / o / d_o not 16-byte aligned (packet loads, as lcv_attn_fwd), dq / dk / dv not 8-byte aligned (their stores). */
 int64_t lcv_attn_bwd_ws_floats(int64_t B, int64_t H, int64_t Nq, int64_t Nk);   /* host-only; a size, not a status */
 int lcv_attn_bwd(const void* q, const void* k, const void* v, const void* o,
                  const void* d_o, const float* lse,

@@ -521,6 +521,13 @@ extern "C" int lcv_attn_bwd(const void* q, const void* k, const void* v, const v
   LCV_CHECK_ARG(dq_sn % 4 == 0 && dk_sn % 4 == 0 && dv_sn % 4 == 0 && dq_sh % 4 == 0 && dk_sh % 4 == 0 && dv_sh % 4 == 0 &&
                     dq_sb % 4 == 0 && dk_sb % 4 == 0 && dv_sb % 4 == 0,
                 "attn_bwd: gradient strides must be multiples of 4 elements");
+  // 16-byte packet loads of q / k / v / o / dO (as lcv_attn_fwd), 8-byte gradient stores (and loads, accumulate_kv), fp32 rows
+  LCV_CHECK_ARG(((uintptr_t)q % 16 == 0) && ((uintptr_t)k % 16 == 0) && ((uintptr_t)v % 16 == 0) && ((uintptr_t)o % 16 == 0) &&
+                    ((uintptr_t)d_o % 16 == 0),
+                "attn_bwd: q, k, v, o, d_o must be 16-byte aligned");
+  LCV_CHECK_ARG(((uintptr_t)dq % 8 == 0) && ((uintptr_t)dk % 8 == 0) && ((uintptr_t)dv % 8 == 0),
+                "attn_bwd: dq, dk, dv must be 8-byte aligned");
+  LCV_CHECK_ARG(((uintptr_t)lse % 4 == 0) && ((uintptr_t)delta_ws % 4 == 0), "attn_bwd: lse, delta_ws must be 4-byte aligned");
   if (Nq == 0) return LCV_OK;
   hipStream_t s = (hipStream_t)stream;
   AttnArgs a = {};

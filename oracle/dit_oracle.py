@@ -143,13 +143,14 @@ def sdpa(q, k, v, scale, rnd=_id):
     return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
 
 
-def sdpa_at_kernel_rounding(q, k, v, scale, tile=64, group=32, thr=6.0, row0=0):
+def sdpa_at_kernel_rounding(q, k, v, scale, tile=64, group=32, thr=6.0, row0=0, return_lse=False):
     """The forward attention kernels' arithmetic restated tile by tile (checker for tests/test_gpu_kernels.py and
     test_gpu_fullsize.py, not a second definition of the op; csrc/attn_fwd.hip:284-345, attn_fwd_pipe.hip, attn_fwd_w64.hip:233-256):
     keys in tiles of 64; scores in log2 units; the running max of a query row is raised only when SOME row of its 32-row group sees a
     tile maximum more than 2^6 above its own running max (and on the first tile), then O and l are rescaled; P = exp2(s - m_run) is
     rounded to bf16 as the MFMA operand of P V while the row sum takes the unrounded fp32 P; O / l is stored in bf16.
     `row0`: index of q's first row inside the launch (groups are aligned to the launch's row 0), for checks on a slice of rows.
+    `return_lse`: also the kernels' second output, lse = m scale + log(l) (natural log, fp32) [B, H, Nq].
     Against this the kernels differ only by fp32 summation order and the bf16 flips that follow from it."""
     c = scale * 1.4426950408889634
     B, H, Nq, D = q.shape
@@ -176,7 +177,8 @@ def sdpa_at_kernel_rounding(q, k, v, scale, tile=64, group=32, thr=6.0, row0=0):
         pt = torch.exp2(s - m.unsqueeze(-1))
         l = l * alpha + pt.sum(dim=-1)
         o = o * alpha.unsqueeze(-1) + bf16_round(pt) @ vf[:, :, k0:k0 + tile]
-    return bf16_round(o / l.unsqueeze(-1))
+    out = bf16_round(o / l.unsqueeze(-1))
+    return (out, m * (scale / c) + torch.log(l)) if return_lse else out
 
 
 def sdpa_backward_at_kernel_rounding(q, k, v, d_o, scale, scale_inside=True, o=None, lse=None):

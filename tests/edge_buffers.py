@@ -1,4 +1,4 @@
-"""What the GPU edge tests of the LoRA, backward and UMT5 kernels share (tests/test_gpu_{lora,bwd,umt5}_kernel_edges.py): the call
+"""What the GPU edge tests of the LoRA, backward, UMT5 and attention kernels share (tests/test_gpu_{lora,bwd,umt5,attn}_kernel_edges.py): the call
 through the C ABI and the guard convention.  Every input is a view into a larger buffer whose guard rows and pad columns hold
 NaN, every output a NaN-filled view of the same kind, so that a read or a write one element off shows up in the result instead
 of as a fault.  A plain helper module (compare tests/kernel_ref.py)."""

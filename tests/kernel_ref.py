@@ -1,6 +1,6 @@
 """float64 restatements of the HBM-bound kernels of the C ABI (norms, glue, VAE helpers, dense-gradient helpers; the LoRA,
-SwiGLU-backward, q/k-norm and UMT5 kernels) and the per-element check they are held to in tests/test_gpu_kernel_edges.py and
-tests/test_gpu_{lora,bwd,umt5}_kernel_edges.py.  A plain helper module (compare tests/delta_cases.py):
+SwiGLU-backward, q/k-norm and UMT5 kernels; the flash-attention forward and backward) and the per-element check they are held to in
+tests/test_gpu_kernel_edges.py and tests/test_gpu_{lora,bwd,umt5,attn}_kernel_edges.py.  A plain helper module (compare tests/delta_cases.py):
 nothing here calls the product's ops; every restatement is the formula of the kernel's header comment (include/lcv_hip.h)
 evaluated in float64 with torch, on whatever device its inputs live on.
 
@@ -37,6 +37,19 @@ Tolerance rule.  Every bound below is derived from this rule, never tuned to pas
      depth the kernel's own summation tree, stated next to each check.  Where the fp32 error in front of the inner rounding is
      purely relative (no cancellation), the tighter statement of rule 1 is used instead: the other neighbour is admissible
      only near a midpoint (`bf16_neighbours` / `alt`: swiglu_bwd's dup, the attention's probabilities).
+
+The flash-attention kernels (lcv_attn_fwd, lcv_attn_bwd: `check_attn_fwd`, `check_attn_bwd`; tests/test_gpu_attn_kernel_edges.py on
+the inputs of tests/attn_cases.py) are held to rules 1, 3 and 5 together: the float64 formula of the header, 1 bf16 ulp for the
+stored result, half a bf16 ulp per bf16 MFMA operand (P; dS) carried linearly to the output, depth * u * sum|terms| per
+accumulation, the cancellation floor of dP - delta, and the fp32 error of the exponent of P.  No tile schedule is restated: P is
+rounded relative to whatever running max is in force, and half an ulp is at most BF16_U = 2^-8 relative wherever that puts it.
+How large these bounds are: the output's own ulp is 0.4 - 0.8 % of an element, but an element of o is a weighted MEAN of v rows
+and much smaller than the |v| its operand terms scale with; on random v the median bound is 1.4 % (5 keys) to 9 % (641 keys)
+of the median |o|, for dq 1.4 - 4 %, for dk and dv 2 - 13 % (the largest at 2 017 queries); lse is bounded by 5e-6 to 5e-5
+absolutely.  A key that carries 1 / Nk of a row's probability therefore hides inside the bound: the cases plant HEAVY keys (a
+quarter to a half of a designated row's probability) exactly where the kernels' edges are - the last key, the first key of the
+last tile, the last query row - so that counting one twice, dropping it or losing a tile moves an element by many bounds
+(tests/test_kernel_ref.py walks these corruptions through the very checks).
 
 The `check_*` functions below hold the restatement, the derived bound and the assert of one entry point each, so that the GPU
 tests (the kernel's result) and the CPU tests of tests/test_kernel_ref.py (deliberately wrong float64 "results") go through
@@ -448,3 +461,131 @@ def check_t5_attention(got, q, k, v, bias, mask, what: str):
     # sum is one fma chain over the Spad staged keys (rule 3, depth Spad); the output's rounding is assert_within's 1 ulp
     floor = (((pb_alt - pb).abs() + Spad * U * pb) @ vf.abs()).permute(0, 2, 1, 3)
     return assert_within(got, ref, 1.0, floor, what=what)
+
+
+# ---- lcv_attn_fwd / lcv_attn_bwd
+LOG2E = 1.4426950408889634
+BF16_U = 2.0 ** -8        # unit roundoff of bf16 (8 significant bits): half an ulp is between 2^-9 |v| (just below a power of
+                          # two) and 2^-8 |v| (just above one).  With 2^-9 in its place the float64-exact tile restatement of the
+                          # documented arithmetic (oracle/dit_oracle.py) fails these checks on exact-grid inputs by up to 1.4.
+
+
+def _bhnd(t):
+    """[B, N, H, D] as the header addresses it -> float64 [B, H, N, D]."""
+    return f64(t).permute(0, 2, 1, 3)
+
+
+def _f32(v: float) -> float:
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def attn_fwd(q, k, v, scale: float):
+    """o = softmax(q k^T scale) v, lse = logsumexp(q k^T scale) in float64.  q [B, Nq, H, D], k, v [B, Nk, H, D] ->
+    o [B, H, Nq, D], lse [B, H, Nq], p [B, H, Nq, Nk], x [B, H, Nq, Nk] (the scores in log2 units)."""
+    qf, kf, vf = _bhnd(q), _bhnd(k), _bhnd(v)
+    s = (qf @ kf.transpose(-1, -2)) * scale
+    lse = torch.logsumexp(s, dim=-1)
+    p = torch.exp(s - lse.unsqueeze(-1))
+    return p @ vf, lse, p, s * LOG2E
+
+
+def attn_score_err(x, q, k, scale: float, exact_scores: bool, offset=None):
+    """sigma_ij, a bound on the fp32 error of the exponent of P_ij in log2 units (which is also a bound on P's relative error:
+    d exp2(x) / exp2(x) = ln 2 dx < dx).  x_ij c - m c (c = scale log2(e); m the running max in force, itself one of the row's
+    scores; the backward has lse in m's place: `offset`, [B, H, Nq] in log2 units) is two rounded products, or one fma, and a
+    difference: (|x_ij| + |m c|) u with |m c| <= max_j |x_ij|; exp2 and the difference itself: 2 u.  The unit-scale bodies start
+    their score accumulators at -m instead: the same magnitudes.  The 128-term dot product in front of it: 128 u scale
+    sum_d |q_id k_jd| (rule 3; with `offset` the accumulators of the unit-scale backward start at -lse and every partial sum
+    is rounded at that magnitude: 128 u |lse| on top) - unless every partial sum of q . k is exactly representable
+    (`exact_scores`: the grids of tests/attn_cases.py), where this part vanishes for the forward."""
+    ax = x.abs()
+    off = ax.amax(-1, keepdim=True) if offset is None else offset.abs().unsqueeze(-1)
+    sigma = (ax + off + 2) * U
+    if offset is not None:
+        sigma = sigma + (128 + 1) * U * off             # the accumulation from -lse, and lse * log2(e) itself
+    if not exact_scores:
+        sigma = sigma + 128 * U * abs(scale) * LOG2E * (_bhnd(q).abs() @ _bhnd(k).abs().transpose(-1, -2))
+    return sigma
+
+
+def check_attn_fwd(o_got, lse_got, q, k, v, scale: float, what: str, exact_scores: bool = False):
+    """lcv_attn_fwd: o_got [B, Nq, H, D] bf16, lse_got [B, H, Nq] fp32 or None; q, k, v as the header addresses them."""
+    scale = _f32(scale)
+    o, lse, p, x = attn_fwd(q, k, v, scale)
+    vf = _bhnd(v)
+    Nk = vf.shape[2]
+    depth = (Nk + 63) // 64 * 64                        # the staged keys: one fma chain per output element (PV), one per row (l)
+    sp = attn_score_err(x, q, k, scale, exact_scores) * p
+    # 1 bf16 ulp of o (rule 1; its spare half ulp also holds the row sum l's own chain, depth u |o| << 2^-9 |o|)
+    # + (BF16_U + depth u) sum_j p_ij |v_jd|: P is the bf16 MFMA operand, rounded relative to whatever running max is in
+    #   force: half an ulp, <= BF16_U relative wherever the max puts P inside its binade, so the tile schedule need not be
+    #   restated; l takes the unrounded P; the PV chain (rule 3 + rule 5)
+    # + sum_j sigma_ij p_ij |v_jd - o_id| <= (sigma p) |v| + rowsum(sigma p) |o|: an error of the exponent moves numerator and l
+    floor = (BF16_U + depth * U) * (p @ vf.abs()) + sp @ vf.abs() + sp.sum(-1, keepdim=True) * o.abs()
+    worst = assert_within(o_got, o.permute(0, 2, 1, 3), 1.0, floor.permute(0, 2, 1, 3), what=f"{what} o")
+    if lse_got is not None:
+        # lse = m scale + __logf(l).  l: an fp32 sum of positive terms, depth u relative, and its terms' own errors
+        # sum_j p_ij sigma_ij; both are absolute errors of log l.  __logf = v_log_f32 * ln 2: 2 u |log l| with 1 <= l <= 64 depth
+        # (the largest term is >= 1, none exceeds 2^ATTN_RESCALE_THR), + 4 u where log l is near 0.  m scale: one rounding,
+        # u max_j |s_ij|.  The final sum: 1 fp32 ulp of lse (assert_within).
+        s_max = x.abs().amax(-1) / LOG2E
+        fl = depth * U + sp.sum(-1) + 2 * U * math.log(64.0 * depth) + 4 * U + U * s_max
+        worst = max(worst, assert_within(lse_got, lse, 1.0, fl, fmt="fp32", what=f"{what} lse"))
+    return worst
+
+
+def attn_bwd(q, k, v, o_in, d_o, lse_in, scale: float):
+    """The backward as a pure function of the kernel's inputs, float64: P = exp(s - lse_in), delta = sum_d dO O_in,
+    dV = P^T dO, dS = P (dO V^T - delta) scale, dQ = dS K, dK = dS^T Q.  -> dq, dk, dv [B, H, N, D] and the intermediates."""
+    qf, kf, vf, of, gf = _bhnd(q), _bhnd(k), _bhnd(v), _bhnd(o_in), _bhnd(d_o)
+    s = (qf @ kf.transpose(-1, -2)) * scale
+    p = torch.exp(s - f64(lse_in).unsqueeze(-1))
+    delta = (gf * of).sum(-1, keepdim=True)
+    dsu = p * (gf @ vf.transpose(-1, -2) - delta)        # dS without the scale
+    ds = dsu * scale
+    return ds @ kf, ds.transpose(-1, -2) @ qf, p.transpose(-1, -2) @ gf, dict(p=p, dsu=dsu, ds=ds, x=s * LOG2E, qf=qf, kf=kf,
+                                                                            vf=vf, of=of, gf=gf)
+
+
+def check_attn_bwd(dq, dk, dv, q, k, v, o_in, d_o, lse_in, scale: float, scale_inside: bool, prev_dk=None, prev_dv=None,
+                   what: str = "", qsplit: int = 1, exact_scores: bool = False):
+    """lcv_attn_bwd: dq [B, Nq, H, D], dk, dv [B, Nk, H, D] bf16 as the kernels left them.  `scale_inside`: dS = P (dP - delta)
+    scale is rounded to bf16 (the general-scale forms) or dS' = P (dP - delta) is and the scale multiplies dQ / dK afterwards
+    (the unit-scale forms).  prev_dk / prev_dv: what dk / dv held before an accumulate_kv call.  qsplit: the number of
+    slices the query sweep of pass A was split into (attn_bwd_qsplit)."""
+    scale = _f32(scale)
+    rq, rk, rv, m = attn_bwd(q, k, v, o_in, d_o, lse_in, scale)
+    p, dsu, ds, x, qf, kf, vf, of, gf = (m[n] for n in ("p", "dsu", "ds", "x", "qf", "kf", "vf", "of", "gf"))
+    Nq, Nk = qf.shape[2], kf.shape[2]
+    depth_q = (Nq + 31) // 32 * 32 + (qsplit if qsplit > 1 else 0)    # pass A: the 32-row tiles' chain, then the slices in order
+    depth_k = (Nk + 63) // 64 * 64                                    # pass B: the staged keys
+    # the operands' errors in front of the MFMAs.  P: its exponent's fp32 error (attn_score_err, lse in the running max's place)
+    # and its rounding to bf16: half a bf16 ulp of the fp32 value, which lies within sigma p of p (rule 5's ulp at |v| + delta)
+    sigma = attn_score_err(x, q, k, scale, exact_scores, offset=f64(lse_in) * LOG2E)
+    e_p = sigma * p + 0.5 * bf16_ulp(p + sigma * p)
+    # dP - delta: two fp32 sums that cancel (rule 1's floor; the unit-scale forms start dP's accumulator at -delta: the same
+    # magnitudes): 128 u (sum_d |dO||V| + sum_d |dO||O|), carried through P scale; P's own error and the two products on dS
+    e_d = 128 * U * (gf.abs() @ vf.abs().transpose(-1, -2) + (gf.abs() * of.abs()).sum(-1, keepdim=True))
+    e_dsu = p * e_d + (sigma + 3 * U) * dsu.abs()
+    # its rounding to bf16, half an ulp of the value the form rounds: dS itself, or dS' = dS / scale with the scale behind it - with
+    # a scale that is no power of two the two lie at different places of their binades, which is all `scale_inside` changes
+    if scale_inside:
+        e_ds = abs(scale) * e_dsu + 0.5 * bf16_ulp(ds.abs() + abs(scale) * e_dsu)
+    else:
+        e_ds = abs(scale) * (e_dsu + 0.5 * bf16_ulp(dsu.abs() + e_dsu))
+    # dV = P^T dO: 1 bf16 ulp + the operand's error times |dO| + the chain over the query sweep (rule 3)
+    f_v = e_p.transpose(-1, -2) @ gf.abs() + depth_q * U * (p.transpose(-1, -2) @ gf.abs())
+    # dQ = dS K, dK = dS^T Q likewise (the scale behind the sum is one more fp32 rounding: u |result|)
+    out = 0.0 if scale_inside else U
+    f_q = e_ds @ kf.abs() + depth_k * U * (ds.abs() @ kf.abs()) + out * rq.abs()
+    f_k = e_ds.transpose(-1, -2) @ qf.abs() + depth_q * U * (ds.abs().transpose(-1, -2) @ qf.abs()) + out * rk.abs()
+    # accumulate_kv: the fp32 sum and what dk / dv held are added in fp32 and rounded ONCE (the store of attn_bwd_dkv_kernel,
+    # attn_bwd_kv_finish_kernel, the epilogue of attn_bwd_dkv2_kernel): the reference is prev + d, still 1 bf16 ulp of it; the
+    # fp32 addition sits in that ulp's spare half
+    if prev_dk is not None:
+        rk = rk + _bhnd(prev_dk)
+    if prev_dv is not None:
+        rv = rv + _bhnd(prev_dv)
+    t = lambda a: a.permute(0, 2, 1, 3)
+    return (assert_within(dq, t(rq), 1.0, t(f_q), what=f"{what} dq"), assert_within(dk, t(rk), 1.0, t(f_k), what=f"{what} dk"),
+            assert_within(dv, t(rv), 1.0, t(f_v), what=f"{what} dv"))

@@ -9,6 +9,7 @@ from pathlib import Path
 import pytest
 import torch
 
+import attn_cases as AC
 import kernel_ref as K
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -17,6 +18,7 @@ EDGES = "test_gpu_kernel_edges.py"
 LORA_EDGES = "test_gpu_lora_kernel_edges.py"
 BWD_EDGES = "test_gpu_bwd_kernel_edges.py"
 UMT5_EDGES = "test_gpu_umt5_kernel_edges.py"
+ATTN_EDGES = "test_gpu_attn_kernel_edges.py"
 
 
 # ------------------------------------------------------------------------------------------------ assert_within itself
@@ -402,6 +404,241 @@ def test_t5_attention_check_has_teeth():
     _fails(K.check_t5_attention, stale, q, k, v, bias, mask)
 
 
+# ------------------------------------------------------------------------------ the flash-attention checks (tests/attn_cases.py)
+def _t(a):
+    return a.permute(0, 2, 1, 3)
+
+
+def _orc():
+    import sys
+    if str(ROOT) not in sys.path:
+        sys.path.insert(0, str(ROOT))
+    from oracle import dit_oracle
+    return dit_oracle
+
+
+# the inputs of every small GPU case, each once: (Nq, Nk, unit, B, H)
+ATTN_FWD_INPUTS = sorted({(nq, nk, unit, AC.B0, AC.H0) for _, nq, nk, unit, _ in AC.FWD_CASES}
+                         | {(AC.WIDE_CASE["Nq"], AC.WIDE_CASE["Nk"], True, AC.WIDE_CASE["B"], AC.WIDE_CASE["H"])})
+ATTN_BWD_INPUTS = sorted({(nq, nk, unit, AC.B0, AC.H0) for nq, nk in AC.BWD_CASES + AC.SPLIT_CASES for unit in (False, True)})
+assert all(AC.is_small(b, h, nq, nk) for nq, nk, _, b, h in ATTN_FWD_INPUTS + ATTN_BWD_INPUTS)
+assert not any(AC.is_small(b, h, nq, nk) for b, h, nq, nk in AC.SPLIT_PAIR)      # B H = 255 / 256: GPU only
+
+
+def _ragged(nq, nk):
+    return nq % 32 != 0 or nk % 64 != 0
+
+
+@pytest.mark.parametrize("Nq,Nk,unit,B,H", sorted(set(ATTN_FWD_INPUTS) | set(ATTN_BWD_INPUTS)))
+def test_attention_cases_hold_what_the_bounds_and_the_corruptions_rest_on(Nq, Nk, unit, B, H):
+    """CPU: exactness in fp32, the heavy keys' shares, the rescale pattern per 32-row group, distinct heads."""
+    c = AC.inputs(Nq, Nk, unit, B, H)
+    q, k = _t(c["q"]).double(), _t(c["k"]).double()
+    for x in (q, k):
+        assert torch.equal(x * 2, (x * 2).round())                              # multiples of 1/2 ...
+    ordinary_rows = [r for r in range(Nq) if r not in (4, 5)] if Nq >= 8 else list(range(Nq))
+    pl = AC.planted(Nq, Nk)
+    ordinary_keys = [j for j in range(Nk) if j not in set(pl["heavy"]) | {pl["j0"], pl["j1"], pl["j2"]}]
+    assert q[:, :, ordinary_rows].abs().max() <= 0.5 and (not ordinary_keys or k[:, :, ordinary_keys].abs().max() <= 0.5)
+    # ... so every partial sum of q . k, in any order and from any start that is itself such a sum (the running max), is a
+    # multiple of 1/4 bounded by 2 sum |q||k| < 2^13: 15 significant bits, exact in fp32
+    mag = q.abs() @ k.abs().transpose(-1, -2)
+    qk = q @ k.transpose(-1, -2)
+    assert 2 * mag.max() < 2 ** 13 and torch.equal(qk * 4, (qk * 4).round()) and torch.equal(qk.float().double(), qk)
+    x = qk * (c["scale"] * K.LOG2E)
+    p = torch.softmax(x / K.LOG2E, -1)
+    # heavy keys: each carries >= 1/4 of rows 0 and Nq - 1, and (where there is more than one key) none carries all of it
+    for r in {0, Nq - 1}:
+        share = p[:, :, r][..., pl["heavy"]]
+        assert share.min() >= 0.25 and (Nk == 1 or share.max() <= 0.75), (r, share.min(), share.max())
+    assert (Nk - 1) in pl["heavy"] and 64 * ((Nk - 1) // 64) in pl["heavy"]
+    if Nq >= 8:
+        assert x[:, :, 4].max() < -40 and x[:, :, 5].min() > 250 and x[:, :, 5].max() < 350
+        growth, rescaled, before = AC.schedule(x)
+        if pl["t1"] is not None:      # tile t1: key j1 lifts row 1 by more than the threshold and lies far below row 2's running max
+            t1, j1 = pl["t1"], pl["j1"]
+            assert growth[t1][..., 1].min() > AC.THR and rescaled[t1][..., 0].all()
+            assert (x[..., 1, j1] - before[t1][..., 1]).min() > AC.THR and (x[..., 2, j1] - before[t1][..., 2]).max() < -40
+        if pl["t2"] is not None:      # tile t2: row 3 grows by (0, THR], no row of its group by more: no rescale
+            g = growth[pl["t2"]]
+            assert g[..., 3].min() > 0 and g[..., 3].max() <= AC.THR and not rescaled[pl["t2"]][..., 0].any()
+    # every (batch, head) differs from every other in q, k, v and dO
+    for name in ("q", "k", "v", "d_o"):
+        flat = _t(c[name]).reshape(B * H, -1)
+        assert all(not torch.equal(flat[i], flat[j]) for i in range(B * H) for j in range(i))
+
+
+def test_every_forward_body_has_a_case_with_the_rescale_pattern():
+    for body in (AC.FWD_SHORT, AC.FWD_GENERAL, AC.FWD_W64, AC.FWD_PIPE):
+        assert any(AC.planted(nq, nk)["t1"] is not None and AC.planted(nq, nk)["t2"] is not None
+                   for b, nq, nk, _, _ in AC.FWD_CASES if b == body), body
+    pl = AC.planted(AC.WIDE_CASE["Nq"], AC.WIDE_CASE["Nk"])
+    assert pl["t1"] is not None and pl["t2"] is not None
+    # the unit-scale short-key body sees the negative first maximum of row 4 too
+    assert any(b == AC.FWD_SHORT and unit and nq >= 8 for b, nq, _, unit, _ in AC.FWD_CASES)
+
+
+def test_attention_workspace_formula_is_the_librarys():
+    """lcv_attn_bwd_ws_floats is host-only: the size the header documents, with attn_bwd_qsplit restated from its source comment."""
+    import sys
+    if str(ROOT) not in sys.path:
+        sys.path.insert(0, str(ROOT))
+    import __graft_entry__ as ge
+    ge.build()                          # (cheap when the library is up to date; this test must also pass when run alone)
+    from lcv_hip import lib as L
+    f = L.load().lcv_attn_bwd_ws_floats
+    shapes = [(AC.B0, AC.H0, nq, nk) for nq, nk in AC.BWD_CASES + AC.SPLIT_CASES] + AC.SPLIT_PAIR
+    for b, h, nq, nk in shapes:
+        assert f(b, h, nq, nk) == AC.ws_floats(b, h, nq, nk), (b, h, nq, nk)
+    assert [AC.qsplit(AC.B0, AC.H0, nq, 77) for nq in (2016, 2017, 2080)] == [1, 4, 4]
+    assert [AC.qsplit(b, h, nq, nk) for b, h, nq, nk in AC.SPLIT_PAIR] == [2, 1]
+
+
+def _fwd_parts(c):
+    qf, kf, vf = (K._bhnd(c[n]) for n in ("q", "k", "v"))
+    s = (qf @ kf.transpose(-1, -2)) * c["scale"]
+    m = s.amax(-1, keepdim=True)
+    return s, m, torch.exp(s - m), vf
+
+
+def _fwd_from_weights(w_num, w_den, m, vf):
+    l = w_den.sum(-1, keepdim=True)
+    return _t((w_num @ vf) / l), (m + torch.log(l)).squeeze(-1)
+
+
+@pytest.mark.parametrize("Nq,Nk,unit,B,H", ATTN_FWD_INPUTS)
+def test_check_attn_fwd_passes_the_tile_restatement_and_fails_the_bugs(Nq, Nk, unit, B, H, capsys):
+    orc = _orc()
+    c = AC.inputs(Nq, Nk, unit, B, H)
+    args = (c["q"], c["k"], c["v"], c["scale"])
+    o, lse = orc.sdpa_at_kernel_rounding(_t(c["q"]), _t(c["k"]), _t(c["v"]), c["scale"], return_lse=True)
+    worst = K.check_attn_fwd(_t(o).to(torch.bfloat16), lse, *args, "tile restatement", exact_scores=True)
+    K.check_attn_fwd(_t(o).to(torch.bfloat16), lse, *args, "tile restatement, general bound")
+    with capsys.disabled():
+        print(f"\ncheck_attn_fwd {Nq}x{Nk} unit={unit}: restatement at {worst:.3f} of the bound", end="")
+    if not _ragged(Nq, Nk):
+        return
+    s, m, w, vf = _fwd_parts(c)
+    right = _fwd_from_weights(w, w, m, vf)
+    K.check_attn_fwd(*right, *args, "float64", exact_scores=True)
+
+    def bad(o_lse):
+        _fails(lambda what: K.check_attn_fwd(*o_lse, *args, what, exact_scores=True))
+
+    def bad_o(o_lse):                  # the output alone must give it away
+        _fails(lambda what: K.check_attn_fwd(o_lse[0], None, *args, what, exact_scores=True))
+    pl = AC.planted(Nq, Nk)
+    if Nk > 1:
+        twice = w.clone(); twice[..., Nk - 1] *= 2                      # the clamped last key counted twice
+        bad_o(_fwd_from_weights(twice, twice, m, vf))
+        for j in {Nk - 1, 64 * ((Nk - 1) // 64)}:                        # the last key / the first key of the last tile dropped
+            drop = w.clone(); drop[..., j] = 0
+            bad_o(_fwd_from_weights(drop, drop, m, vf))
+    if Nq > 1 and Nk > 1:             # (with one key every row's output is v)
+        swapped = right[0].clone(); swapped[:, [Nq - 2, Nq - 1]] = swapped[:, [Nq - 1, Nq - 2]]
+        bad_o((swapped, right[1]))
+    heads = right[0].clone(); heads[:, :, [0, 1]] = heads[:, :, [1, 0]]
+    bad_o((heads, right[1]))
+    for t0 in {0, 64 * ((Nk - 1) // 64)}:                                # one tile's PV contribution doubled (l is right)
+        num = w.clone(); num[..., t0: t0 + 64] *= 2
+        bad_o(_fwd_from_weights(num, w, m, vf))
+    if pl["t1"] is not None:          # O not rescaled after the jump of row 1 in tile t1: what came before stays 2^d too large
+        x = s * K.LOG2E
+        d = x[..., 1, :].amax(-1) - x[..., 1, : 64 * pl["t1"]].amax(-1)
+        num = w.clone(); num[..., 1, : 64 * pl["t1"]] *= torch.exp2(d).unsqueeze(-1)
+        bad_o(_fwd_from_weights(num, w, m, vf))
+    bad((right[0], right[1] * K.LOG2E))                                  # lse in log2 units
+
+
+def _bwd_inputs(c):
+    o64, lse64, _, _ = K.attn_fwd(c["q"], c["k"], c["v"], c["scale"])
+    return _t(o64).to(torch.bfloat16), lse64.float()
+
+
+@pytest.mark.parametrize("Nq,Nk,unit,B,H", ATTN_BWD_INPUTS)
+def test_check_attn_bwd_passes_the_rounding_point_restatement_and_fails_the_bugs(Nq, Nk, unit, B, H, capsys):
+    orc = _orc()
+    c = AC.inputs(Nq, Nk, unit, B, H)
+    o_in, lse_in = _bwd_inputs(c)
+    args = (c["q"], c["k"], c["v"], o_in, c["d_o"], lse_in, c["scale"])
+    qs = AC.qsplit(B, H, Nq, Nk)
+    worst = [0.0, 0.0, 0.0]
+    for inside in (True, False):
+        got = orc.sdpa_backward_at_kernel_rounding(_t(c["q"]), _t(c["k"]), _t(c["v"]), _t(c["d_o"]), c["scale"], scale_inside=inside,
+                                                   o=_t(o_in), lse=lse_in)
+        got = [_t(g).to(torch.bfloat16) for g in got]
+        w3 = K.check_attn_bwd(*got, *args, inside, what=f"restatement inside={inside}", qsplit=qs, exact_scores=True)
+        worst = [max(a, b) for a, b in zip(worst, w3)]
+        K.check_attn_bwd(*got, *args, inside, what=f"restatement inside={inside}, general bound", qsplit=qs)
+    with capsys.disabled():
+        print(f"\ncheck_attn_bwd {Nq}x{Nk} unit={unit}: restatement at dq {worst[0]:.3f} dk {worst[1]:.3f} dv {worst[2]:.3f} of the bound", end="")
+    if not _ragged(Nq, Nk):
+        return
+    rq, rk, rv, m = K.attn_bwd(*args)
+    ds, qf, kf = m["ds"], m["qf"], m["kf"]
+    right = [_t(r) for r in (rq, rk, rv)]
+    K.check_attn_bwd(*right, *args, True, what="float64", qsplit=qs, exact_scores=True)
+
+    def bad(dq, dk, dv, inside=True, **kw):
+        with pytest.raises(AssertionError):
+            K.check_attn_bwd(dq, dk, dv, *args, inside, what="wrong on purpose", qsplit=qs, exact_scores=True, **kw)
+    # an operand rounded more coarsely than bf16 (4 significant bits, as an fp8 e4m3 operand would be) on either side of the scale;
+    # with one key dS is exactly 0 (o = v, so dP = delta)
+    if Nk > 1:
+        coarse = torch.ldexp(torch.round(torch.ldexp(torch.frexp(ds)[0], torch.tensor(4))), torch.frexp(ds)[1] - 4)
+        for inside in (True, False):
+            bad(_t(coarse @ kf), _t(coarse.transpose(-1, -2) @ qf), right[2], inside)
+    last = 32 * ((Nq - 1) // 32)                                          # dK, dV without the last query tile
+    if Nk > 1:
+        bad(right[0], _t(ds[..., :last, :].transpose(-1, -2) @ qf[..., :last, :]), right[2])
+    bad(right[0], right[1], _t(m["p"][..., :last, :].transpose(-1, -2) @ m["gf"][..., :last, :]))
+    if qs > 1:                                                            # one split's slice added twice
+        nt = (Nq + 31) // 32
+        a, b = 32 * (nt * 1 // qs), 32 * (nt * 2 // qs)
+        bad(right[0], _t(rk + ds[..., a:b, :].transpose(-1, -2) @ qf[..., a:b, :]), right[2])
+    if Nq > 1 and Nk > 1:
+        swapped = right[0].clone(); swapped[:, [Nq - 2, Nq - 1]] = swapped[:, [Nq - 1, Nq - 2]]
+        bad(swapped, right[1], right[2])
+    heads = right[2].clone(); heads[:, :, [0, 1]] = heads[:, :, [1, 0]]
+    bad(right[0], right[1], heads)
+    # accumulate_kv: right, ignored, applied twice
+    pk, pv = c["prev_dk"], c["prev_dv"]
+    K.check_attn_bwd(right[0], right[1] + pk.double(), right[2] + pv.double(), *args, True, pk, pv, what="accumulated", qsplit=qs,
+                     exact_scores=True)
+    bad(right[0], right[1], right[2] + pv.double(), prev_dk=pk, prev_dv=pv)
+    bad(right[0], right[1] + pk.double(), right[2], prev_dk=pk, prev_dv=pv)
+    bad(right[0], right[1] + 2 * pk.double(), right[2] + pv.double(), prev_dk=pk, prev_dv=pv)
+    bad(right[0], right[1] + pk.double(), right[2] + 2 * pv.double(), prev_dk=pk, prev_dv=pv)
+
+
+def test_the_side_of_the_scale_is_detectable_only_where_few_operands_carry_an_element():
+    """dS rounded to bf16 on the WRONG side of a scale that is no power of two (dS' = dS / scale rounded where dS should be, or
+    the reverse).  The two roundings differ by at most half an ulp of the coarser side, i.e. at most twice the half ulp the bound
+    grants the right side, and every element also has its own output ulp and the other operands' terms on top.  So the wrong
+    side is rejected only on elements that a few dS entries carry (short key or query sweeps, one dominant probability) and
+    whose entries sit low in their binade on one side of the scale and high on the other; on long sweeps the difference
+    averages out far below the bound.  Counted here over the short backward cases: some are rejected, most are not."""
+    orc = _orc()
+    rejected, total = [], 0
+    for Nq, Nk, unit, B, H in ATTN_BWD_INPUTS:
+        if Nq > 33 or Nk == 1:
+            continue
+        c = AC.inputs(Nq, Nk, unit, B, H)
+        o_in, lse_in = _bwd_inputs(c)
+        for inside in (True, False):
+            got = orc.sdpa_backward_at_kernel_rounding(_t(c["q"]), _t(c["k"]), _t(c["v"]), _t(c["d_o"]), c["scale"], scale_inside=inside,
+                                                       o=_t(o_in), lse=lse_in)
+            got = [_t(g).to(torch.bfloat16) for g in got]
+            total += 1
+            try:
+                K.check_attn_bwd(*got, c["q"], c["k"], c["v"], o_in, c["d_o"], lse_in, c["scale"], not inside, what="wrong side",
+                                 exact_scores=True)
+            except AssertionError:
+                rejected.append((Nq, Nk, unit, inside))
+    print(f"wrong side of the scale rejected in {len(rejected)} of {total} restatements: {rejected}")
+    assert 0 < len(rejected) < total / 2
+
+
 # ----------------------------------------------------------------------------------------------------- coverage guard
 # entry point -> [(test file, test function)] that checks its kernel at kernel level
 KERNEL_TESTS = {
@@ -417,8 +654,11 @@ KERNEL_TESTS = {
     "lcv_qknorm_rope_bwd": [("test_gpu_backward.py", "test_qknorm_rope_backward"),
                             ("test_gpu_backward.py", "test_qk_norm_weight_gradients"), (BWD_EDGES, "test_qknorm_rope_bwd_edges")],
     "lcv_timestep_embedding": [("test_gpu_kernels.py", "test_timestep_embedding_matches_oracle")],
-    "lcv_attn_fwd": [("test_gpu_kernels.py", "test_attention_fuzz_against_the_restatement_of_the_kernels_arithmetic")],
-    "lcv_attn_bwd": [("test_gpu_backward.py", "test_attention_backward_fuzz_against_the_kernels_rounding_points")],
+    "lcv_attn_fwd": [("test_gpu_kernels.py", "test_attention_fuzz_against_the_restatement_of_the_kernels_arithmetic"),
+                     (ATTN_EDGES, "test_attn_fwd_edges"), (ATTN_EDGES, "test_attn_fwd_wide_key_stride_takes_the_64_bit_body")],
+    "lcv_attn_bwd": [("test_gpu_backward.py", "test_attention_backward_fuzz_against_the_kernels_rounding_points"),
+                     (ATTN_EDGES, "test_attn_bwd_edges"), (ATTN_EDGES, "test_attn_bwd_split_query_sweep"),
+                     (ATTN_EDGES, "test_attn_bwd_refuses_bad_strides_and_misaligned_pointers")],
     "lcv_gemm_nt": [("test_gpu_kernels.py", "test_gemm_dispatch_fuzz_bitwise_against_the_one_barrier_kernel"),
                     ("test_gpu_kernels.py", "test_gemm_nt_lora_and_epilogues")],
     "lcv_lora_down": [("test_gpu_kernels.py", "test_gemm_nt_lora_and_epilogues"), (LORA_EDGES, "test_lora_down_edges"),
