@@ -608,14 +608,19 @@ extern "C" int lcv_fm_mse_samples(const float* pred, const void* eps, const void
 
 // ---------------------------------------------------------------------------
 // Sinusoidal timestep features (the input of the timestep MLP): out[i, j] = cos(t_i f_j) for j < half, sin(t_i f_j) after,
-// f_j = exp(-ln(max_period) j / half), all fp32 — the one piece of arithmetic the DiT forward still did in torch.
+// f_j = exp(-ln(max_period) j / half) — the one piece of arithmetic the DiT forward still did in torch.
+// f_j is formed in double and rounded once: an fp32 exponent of magnitude up to ln(max_period) = 9.2 carries an absolute error of
+// a few 2^-24 * 9.2, which expf turns into that RELATIVE error of f_j and so of the argument (5 fp32 ulps at arguments of 10 - 20
+// rad, measured).  With f_j correctly rounded the argument t_i f_j is off by one rounding of f_j and one of the product; the
+// product, cos and sin are fp32.  n * half threads in all (a few hundred): the double exp costs nothing that shows.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void timestep_embedding_kernel(const float* __restrict__ t, float* __restrict__ out, int n,
-                                                                 int half, float neg_log_period_over_half) {
+                                                                 int half, double neg_log_period_over_half) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= n * half) return;
   const int i = idx / half, j = idx - i * half;
-  const float arg = t[i] * expf(neg_log_period_over_half * (float)j);
+  const float f = (float)exp(neg_log_period_over_half * (double)j);
+  const float arg = t[i] * f;
   out[(int64_t)i * 2 * half + j] = cosf(arg);
   out[(int64_t)i * 2 * half + half + j] = sinf(arg);
 }
@@ -625,7 +630,7 @@ extern "C" int lcv_timestep_embedding(const float* t, float* out, int64_t n, int
   if (n == 0) return LCV_OK;
   const int half = (int)(dim / 2);
   hipLaunchKernelGGL(timestep_embedding_kernel, dim3((unsigned)((n * half + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t, out,
-                     (int)n, half, -logf(max_period) / (float)half);
+                     (int)n, half, -log((double)max_period) / (double)half);
   LCV_LAUNCH_CHECK("timestep_embedding");
   return LCV_OK;
 }

@@ -1,5 +1,5 @@
 // What the master-weight optimizer kernels share (optim_master.hip, optim_moments8.hip, optim_accum.hip, optim_anchor.hip,
-// optim_ema.hip):
+// optim_ema.hip), and the default kernels' fp32 AdamW (optim.hip):
 // the (bf16 word, int16 low word) <-> fp32 master format, a thread's eight fp32 values, and the per-element op sequences of SGD
 // and AdamW (their scalars are optim_common.h's).  All of them are built with -ffp-contract=off.
 #pragma once
@@ -10,7 +10,8 @@ typedef __attribute__((ext_vector_type(8))) short s16x8;
 // Every fp32 operation below is one correctly rounded IEEE operation and stays one: contraction is off for the including file,
 // and the arithmetic is written with plain operators.  (hipcc's __fmul_rn / __fadd_rn are `x * y` / `x + y` compiled under the
 // default -ffp-contract=fast, so a product and the sum that takes it may still fuse into one fma; its __fsqrt_rn is the
-// 1-ulp native square root.  `/` and __builtin_sqrtf are the correctly rounded forms, hipcc's default for fp32.)
+// 1-ulp native square root.  `/` and __builtin_sqrtf are the correctly rounded forms, hipcc's default for fp32.  No optimizer
+// kernel uses those intrinsics: optim.hip is written and built the same way.)
 #pragma clang fp contract(off)
 
 __device__ __forceinline__ float master_join(bf16_t h, short l) {
@@ -61,7 +62,8 @@ __device__ __forceinline__ void master_adamw_moments_update(float& p, float& m, 
   p = p + dp;
 }
 
-// the fp32 op sequence of adamw_kernel<true> (optim.hip), each operation correctly rounded; p, m, v in and out
+// the fp32 AdamW op sequence, each operation correctly rounded; p, m, v in and out.  adamw_kernel<true> (optim.hip) is this
+// function, and its bf16 form is the same sequence with a bf16 rounding after each operation of its header's list
 __device__ __forceinline__ void master_adamw_elem(float& p, float& m, float& v, float g, float coef, const AdamScalars& s) {
   g = g * coef;
   p = p * s.c_wd;

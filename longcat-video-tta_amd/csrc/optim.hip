@@ -3,16 +3,22 @@
 //
 // The reference trains bf16 adapters with torch.optim.AdamW(foreach) after torch.nn.utils.clip_grad_norm_
 // (lora_experiment/scripts/run_lora_tta.py:462-468, 513-514), i.e. every intermediate of the update is ROUNDED
-// TO bf16.  The kernel reproduces that op sequence and its rounding points exactly:
+// TO bf16.  The kernel reproduces that op sequence and its rounding points exactly (tests/optim_ref.py restates it in numpy and
+// tests/test_gpu_optim_kernel_edges.py pins it bit for bit):
 //   g  = bf16(g * coef)                                   clip_grad_norm_   (coef is a bf16 value)
 //   p  = bf16(p * (1 - lr*wd))                            _foreach_mul_
 //   m  = bf16(m + (1-b1) * (g - m))                       _foreach_lerp_    (weight < 0.5 form)
 //   v  = bf16(v * b2);  v = bf16(v + ((1-b2) * g) * g)    _foreach_mul_, _foreach_addcmul_
 //   d  = bf16(sqrt(v)); d = bf16(d / sqrt(1-b2^t)); d = bf16(d + eps)
 //   p  = bf16(p + (-lr/(1-b1^t)) * (m / d))               _foreach_addcdiv_
-// For fp32 parameters (the delta methods) the same sequence runs without the bf16 roundings.
+// For fp32 parameters (the delta methods) the same sequence runs without the bf16 roundings: master_adamw_elem (master_elem.h),
+// the one definition the master-weight kernels use too.
+// Every fp32 operation is one correctly rounded IEEE operation: plain operators, `/` and __builtin_sqrtf, and the file is built
+// with -ffp-contract=off (lcv_hip/build.py; master_elem.h's pragma says the same), so no product fuses with the sum that takes
+// it.  (hipcc's __fmul_rn / __fadd_rn are plain operators that contract under its default, and its __fsqrt_rn is the 1-ulp
+// native square root: they are not used.)  The clip's sums of squares (grad_chunk_sumsq's packet path) keep their explicit fmaf.
 // Algorithmic bytes: 14 B / parameter (bf16: p, g, m, v read; p, m, v written).
-#include "optim_common.h"
+#include "master_elem.h"
 #include <math.h>
 
 template <bool F32>
@@ -74,27 +80,21 @@ __global__ __launch_bounds__(256) void adamw_kernel(const lcv_adam_tensor* __res
     if (i >= t.numel) break;
     if (F32) {
       float* P = (float*)t.param; float* M = (float*)t.exp_avg; float* V = (float*)t.exp_avg_sq;
-      const float g = __fmul_rn(((const float*)t.grad)[i], coef);
-      float p = __fmul_rn(P[i], s.c_wd);
-      float m = M[i];
-      m = __fadd_rn(m, __fmul_rn(s.w1, __fsub_rn(g, m)));
-      float v = __fmul_rn(V[i], s.b2);
-      v = __fadd_rn(v, __fmul_rn(__fmul_rn(s.c2, g), g));
-      float d = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), s.bc2_sqrt), s.eps);
-      p = __fadd_rn(p, __fmul_rn(s.step_size, __fdiv_rn(m, d)));
+      float p = P[i], m = M[i], v = V[i];
+      master_adamw_elem(p, m, v, ((const float*)t.grad)[i], coef, s);
       P[i] = p; M[i] = m; V[i] = v;
     } else {
       bf16_t* P = (bf16_t*)t.param; bf16_t* M = (bf16_t*)t.exp_avg; bf16_t* V = (bf16_t*)t.exp_avg_sq;
-      const float g = bfround(__fmul_rn(bf2f(((const bf16_t*)t.grad)[i]), coef));
-      float p = bfround(__fmul_rn(bf2f(P[i]), s.c_wd));
+      const float g = bfround(bf2f(((const bf16_t*)t.grad)[i]) * coef);
+      float p = bfround(bf2f(P[i]) * s.c_wd);
       float m = bf2f(M[i]);
-      m = bfround(__fadd_rn(m, __fmul_rn(s.w1, __fsub_rn(g, m))));
-      float v = bfround(__fmul_rn(bf2f(V[i]), s.b2));
-      v = bfround(__fadd_rn(v, __fmul_rn(__fmul_rn(s.c2, g), g)));
-      float d = bfround(__fsqrt_rn(v));
-      d = bfround(__fdiv_rn(d, s.bc2_sqrt));
-      d = bfround(__fadd_rn(d, s.eps));
-      p = bfround(__fadd_rn(p, __fmul_rn(s.step_size, __fdiv_rn(m, d))));
+      m = bfround(m + s.w1 * (g - m));
+      float v = bfround(bf2f(V[i]) * s.b2);
+      v = bfround(v + (s.c2 * g) * g);
+      float d = bfround(__builtin_sqrtf(v));
+      d = bfround(d / s.bc2_sqrt);
+      d = bfround(d + s.eps);
+      p = bfround(p + s.step_size * (m / d));
       P[i] = f2bf(p); M[i] = f2bf(m); V[i] = f2bf(v);
     }
   }
@@ -136,7 +136,10 @@ extern "C" int lcv_adamw_step(const lcv_adam_tensor* tensors, int64_t n_tensors,
 // SGD (momentum 0) with weight decay, the default optimizer of full-model TTA
 // (lora_experiment/scripts/run_full_tta.py:138-144: SGD(params, lr, momentum=0.0, weight_decay)), in the op order
 // and bf16 rounding points of torch.optim.SGD's foreach path after clip_grad_norm_:
-//   g = bf16(g * coef);  g = bf16(g + wd * p);  p = bf16(p - lr * g)
+//   g = bf16(g * coef);  g = bf16(g + wd * p) if wd != 0;  p = bf16(p + (-lr) * g)
+// with -lr in fp32, as torch's device kernels hold alpha.  fp32 parameters: the same without the roundings, and the decay always
+// added (wd = 0 adds a zero; master_sgd_elem skips it, which differs only where g * coef is -0 or p is not finite).  The 16-byte
+// packet path and the per-element path are one arithmetic.  Every operation correctly rounded, nothing fused (see the top).
 // Same descriptor table as AdamW (exp_avg / exp_avg_sq unused).  8 B / parameter read, 2 written.
 // ---------------------------------------------------------------------------
 template <bool F32>
@@ -153,9 +156,9 @@ __global__ __launch_bounds__(256) void sgd_kernel(const lcv_adam_tensor* __restr
     unpack8(*reinterpret_cast<const u16x8*>((const bf16_t*)t.grad + base), g);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float gg = bfround(__fmul_rn(g[e], coef));
-      if (wd != 0.f) gg = bfround(__fadd_rn(gg, __fmul_rn(wd, p[e])));
-      p[e] = __fadd_rn(p[e], __fmul_rn(-lr, gg));
+      float gg = bfround(g[e] * coef);
+      if (wd != 0.f) gg = bfround(gg + wd * p[e]);
+      p[e] = p[e] + (-lr) * gg;
     }
     *reinterpret_cast<u16x8*>(P) = pack8(p);
     return;
@@ -166,15 +169,15 @@ __global__ __launch_bounds__(256) void sgd_kernel(const lcv_adam_tensor* __restr
     if (i >= t.numel) break;
     if (F32) {
       float* P = (float*)t.param;
-      float g = __fmul_rn(((const float*)t.grad)[i], coef);
-      g = __fadd_rn(g, __fmul_rn(wd, P[i]));
-      P[i] = __fadd_rn(P[i], __fmul_rn(-lr, g));
+      float g = ((const float*)t.grad)[i] * coef;
+      g = g + wd * P[i];
+      P[i] = P[i] + (-lr) * g;
     } else {
       bf16_t* P = (bf16_t*)t.param;
       const float p = bf2f(P[i]);
-      float g = bfround(__fmul_rn(bf2f(((const bf16_t*)t.grad)[i]), coef));
-      if (wd != 0.f) g = bfround(__fadd_rn(g, __fmul_rn(wd, p)));
-      P[i] = f2bf(__fadd_rn(p, __fmul_rn(-lr, g)));
+      float g = bfround(bf2f(((const bf16_t*)t.grad)[i]) * coef);
+      if (wd != 0.f) g = bfround(g + wd * p);
+      P[i] = f2bf(p + (-lr) * g);
     }
   }
 }

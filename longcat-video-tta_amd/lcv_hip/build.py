@@ -30,6 +30,7 @@ _ATTN_FLAGS = ["-fno-honor-nans", "-mno-amdgpu-ieee", "-fno-slp-vectorize"]
 EXTRA = {"attn_fwd.hip": _ATTN_FLAGS, "attn_fwd_pipe.hip": _ATTN_FLAGS, "attn_bwd_dq2.hip": _ATTN_FLAGS, "attn_bwd_dkv2.hip": _ATTN_FLAGS,
          "attn_fwd_w64.hip": _ATTN_FLAGS,
          # bit-exact against an fp32 restatement: no product may fuse with the sum that takes it (the source says so too)
+         "optim.hip": ["-ffp-contract=off"],
          "optim_master.hip": ["-ffp-contract=off"], "optim_moments8.hip": ["-ffp-contract=off"],
          "optim_accum.hip": ["-ffp-contract=off"], "optim_anchor.hip": ["-ffp-contract=off"],
          "optim_ema.hip": ["-ffp-contract=off"], "step_cache.hip": ["-ffp-contract=off"],

@@ -309,6 +309,65 @@ def check_linear_f32_smallm_bwd(got, dy, w, a, act_in: int, what: str):
     return assert_within(got, f * acc, 1.0, f.abs() * depth * U * terms + silu_grad_err(a) * acc.abs(), fmt="fp32", what=what)
 
 
+# ---- lcv_linear_f32_smallm (forward)
+def linear_f32_smallm(a, w, bias, act_in: int):
+    """out[M, N] = act_in(a[M, K]) @ w[N, K]^T + bias -> (the float64 value, |act(a)| @ |w|^T, |bias| broadcast or 0)."""
+    x = silu(f64(a)) if act_in else f64(a)
+    wf = f64(w)
+    b = f64(bias) if bias is not None else torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
+    return x @ wf.t() + b, x.abs() @ wf.abs().t(), b.abs().expand(a.shape[0], -1)
+
+
+def check_linear_f32_smallm(got, a, w, bias, act_in: int, silu_rel: float, what: str):
+    """Rule 3 with the kernel's own tree: a lane's chain of 8 products per 512 columns of K, the 6-level wave tree, then the bias
+    (2: its addition and the result's rounding).  act_in = 1 adds `silu_rel` (the relative error allowed to the kernel's SiLU, whose
+    __expf is no correctly rounded function) times the magnitudes the activations enter with."""
+    ref, mag, b = linear_f32_smallm(a, w, bias, act_in)
+    depth = 8 * math.ceil(a.shape[1] / 512) + 6 + 2
+    floor = depth * U * (mag + b) + (silu_rel * mag if act_in else 0.0)
+    return assert_within(got, ref, 0.0, floor, fmt="fp32", what=what)
+
+
+# ---- lcv_timestep_embedding
+def timestep_embedding(t, dim: int, max_period: float):
+    """out[i] = [cos(t_i f_j) for j < dim/2, sin(t_i f_j) for j < dim/2], f_j = exp(-ln(max_period) j / (dim/2))
+    -> (the float64 value [n, dim], |t_i f_j| laid out the same way)."""
+    half = dim // 2
+    f = torch.exp(-math.log(max_period) * torch.arange(half, dtype=torch.float64, device=t.device) / half)
+    arg = f64(t)[:, None] * f[None, :]
+    return torch.cat([torch.cos(arg), torch.sin(arg)], dim=1), torch.cat([arg, arg], dim=1).abs()
+
+
+def check_timestep_embedding(got, t, dim: int, max_period: float, what: str):
+    """The oracle test of test_gpu_kernels.py allows 2e-4 at arguments of up to 1000 rad (the fp32 error of f_j and of the
+    product t f_j moves the argument, and cos / sin have slope 1); scaled with the argument that is 2e-4 |t f_j| / 1000, and
+    2^-22 on top for cos / sin themselves (a few fp32 ulps of values up to 1)."""
+    ref, arg = timestep_embedding(t, dim, max_period)
+    return assert_within(got, ref, 0.0, 2e-4 * arg / 1000.0 + 2.0 ** -22, fmt="fp32", what=what)
+
+
+# ---- lcv_fm_mse_samples
+FM_MSE_PARTS = 256       # LCV_FM_MSE_PARTS: fixed-order partial sums per sample, 256 lanes each
+
+
+def fm_mse_samples(pred, eps, x0, Tc: int):
+    """loss[b] = mean over sample b of (pred[b, :, Tc:] - bf16(eps[b] - x0[b]))^2; pred [B, C, T, HW] fp32, eps / x0
+    [B or 1, C, T - Tc, HW] bf16.  The velocity target is the bf16 difference (common.py:486)."""
+    vt = f64((eps.float() - x0.float()).to(torch.bfloat16))
+    d = f64(pred)[:, :, Tc:] - vt
+    return (d * d).flatten(1).mean(1)
+
+
+def check_fm_mse_samples(got, pred, eps, x0, Tc: int, what: str):
+    """Rule 3: every term is positive, so sum|terms| / per is the value itself; depth from fm_mse_parts_kernel and
+    fm_mse_finish_kernel: a lane's loop over a stride of 256 x 256 elements, the 6-level wave tree, 2 for the four waves, 8 for
+    the tree over the 256 partials."""
+    ref = fm_mse_samples(pred, eps, x0, Tc)
+    per = pred.shape[1] * (pred.shape[2] - Tc) * pred.shape[3]
+    depth = math.ceil(per / (FM_MSE_PARTS * 256)) + 6 + 2 + 8
+    return assert_within(got, ref, 0.0, depth * U * ref, fmt="fp32", what=what)
+
+
 # ---- lcv_swiglu_bwd / lcv_swiglu_bwd_interleaved
 def swiglu_il_index(F: int, device=None):
     """The fused layout of lcv_swiglu_bwd_interleaved: per 64 columns 32 gate values, then their 32 up partners.

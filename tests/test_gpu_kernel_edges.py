@@ -610,3 +610,155 @@ def test_gemm_transcendental_epilogues_equal_mode_7_bitwise(N, mode, monkeypatch
     monkeypatch.setenv("LCV_GEMM_TILE", mode)
     for case in cases:
         _gx_equal(_gx_run(N, case), _GX_MODE7[N][case], mode, case)
+
+
+# ------------------------------------------------------------------------------------------- lcv_linear_f32_smallm (forward)
+# The relative error of the kernel's SiLU (x / (1 + __expf(-x)); __expf is the hardware exp2 of x * log2(e), whose product carries
+# an absolute error that grows with |x|), measured through the kernel itself by test_linear_f32_smallm_silu_error on an MI355X:
+# the largest |out - silu(a)| / |silu(a)| over 1024 values of a in [-20, 20] is 8.904e-7 (14.9 u, at a = -17.5; 1.0e-7 over the
+# positive half, where 1 + e^-a is close to 1).  The edge cases allow twice this per input.
+SMALLM_SILU_REL = 8.904e-07
+
+
+def _smallm_refused(args):
+    from lcv_hip.lib import LcvError
+    with pytest.raises(LcvError) as e:
+        _call("lcv_linear_f32_smallm", *args)
+    assert e.value.code == -1
+
+
+@gpu
+def test_linear_f32_smallm_silu_error():
+    """N = K = 64 with the identity as the weight: out[m, n] = silu(a[m, n]) plus 63 exact zeros, so the output is the kernel's
+    SiLU itself, held against the float64 SiLU of the same fp32 inputs."""
+    M, N = 16, 64
+    a = torch.linspace(-20.0, 20.0, M * N, dtype=torch.float64, device=DEV).to(F32).view(M, N)
+    assert not (a == 0).any()
+    w = torch.eye(N, dtype=BF16, device=DEV)
+    out = _nan(M * N + 8, dtype=F32)
+    _call("lcv_linear_f32_smallm", _p(a), _p(w), None, _p(out), M, N, N, 1)
+    ref = K.silu(K.f64(a)).flatten()
+    got = K.f64(out[:M * N])
+    assert torch.isfinite(got).all() and torch.isnan(out[M * N:]).all()
+    rel = ((got - ref).abs() / ref.abs())
+    i = int(rel.argmax())
+    print(f"silu_f through linear_f32_smallm: worst relative error {float(rel[i]):.3e} ({float(rel[i]) / U:.1f} u) at a = "
+          f"{float(a.flatten()[i])!r}; positive a: {float(rel[a.flatten() > 0].max()):.3e}")
+    assert float(rel[i]) <= 2 * SMALLM_SILU_REL
+
+
+@gpu
+@pytest.mark.parametrize("M,N,K_,act,has_bias", [
+    (1, 1, 8, 0, False),        # one row, one column, one packet: lane 0 alone works, 15 of a workgroup's 16 columns are past N
+    (16, 17, 520, 0, True),     # a full row group; N = 16 + 1: a second workgroup with one column; K = 512 + 8: lane 0 loops twice
+    (17, 33, 1032, 1, True),    # a second row group of one row; SiLU on the way into LDS; K = 2 * 512 + 8
+    (33, 16, 2560, 0, False),   # three row groups; 16 x 2560 x 4 B = 160 KiB of LDS exactly, the most a workgroup can have
+])
+def test_linear_f32_smallm_edges(M, N, K_, act, has_bias):
+    a = _randn(M, K_, seed=71, scale=2.0, dtype=F32)
+    w = _randn(N, K_, seed=72, scale=0.05)
+    bias = _randn(N, seed=73) if has_bias else None
+    out = _nan(M * N + 8, dtype=F32)           # a canary past the end, NaN everywhere the kernel must write
+    _call("lcv_linear_f32_smallm", _p(a), _p(w), _p(bias), _p(out), M, N, K_, act)
+    assert torch.isnan(out[M * N:]).all()
+    K.check_linear_f32_smallm(out[:M * N].view(M, N), a, w, bias, act, 2 * SMALLM_SILU_REL,
+                              what=f"linear_f32_smallm M={M} N={N} K={K_} act={act}")
+
+
+@gpu
+def test_linear_f32_smallm_refuses_what_it_cannot_stage():
+    a, w, out = torch.zeros(16, dtype=F32, device=DEV), torch.zeros(16, dtype=BF16, device=DEV), _nan(16, dtype=F32)
+    _smallm_refused((_p(a), _p(w), None, _p(out), 1, 1, 2568, 0))      # 16 rows x 2568 x 4 B is past 160 KiB of LDS
+    _smallm_refused((_p(a), _p(w), None, _p(out), 1, 1, 12, 0))        # K is no whole number of 8-element packets
+    _smallm_refused((_p(a), _p(w), None, _p(out), 1, 0, 8, 0))         # N = 0
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all()                                      # nothing ran
+
+
+# -------------------------------------------------------------------------------------------------- lcv_timestep_embedding
+@gpu
+@pytest.mark.parametrize("n,dim,max_period", [
+    (3, 342, 10000.0),     # 3 x 171 = 513 threads: one thread in a third workgroup
+    (4, 2, 10000.0),       # one frequency, f_0 = 1: [cos t, sin t]
+    (4, 256, 100.0),       # another period
+    (0, 256, 10000.0),     # nothing to do: `out` is left alone
+])
+def test_timestep_embedding_edges(n, dim, max_period):
+    """Bound per element (kernel_ref.check_timestep_embedding): the existing oracle test's 2e-4 at arguments of 1000 rad, scaled
+    with the argument, plus 2^-22 for cos / sin themselves and the small arguments: 2e-4 |t f_j| / 1000 + 2^-22.  t = 0 is
+    exact (cos 1, sin 0).  With f_j = expf(fp32 exponent) the kernel missed this bound at arguments of 10 - 20 rad (1.41 x the
+    bound at n = 3, dim = 342, element (0, 248); 1.30 x at max_period = 100, element (3, 243)): the exponent's rounding error,
+    up to ln(max_period) * 2^-24 absolute, is the frequency's relative error.  The kernel now forms f_j in double."""
+    t = torch.tensor([0.0, -37.5, 612.0, 1000.0][:n], dtype=F32, device=DEV)      # 612 is a bf16 value too
+    if n == 3:
+        t = torch.tensor([1000.0, 0.0, -37.5], dtype=F32, device=DEV)             # the largest argument in front
+    out = _nan(n * dim + 8, dtype=F32)
+    _call("lcv_timestep_embedding", _p(t) if n else _p(torch.zeros(1, dtype=F32, device=DEV)), _p(out), n, dim, max_period)
+    assert torch.isnan(out[n * dim:]).all()
+    if n == 0:
+        return
+    got = out[:n * dim].view(n, dim)
+    K.check_timestep_embedding(got, t, dim, max_period, what=f"timestep_embedding n={n} dim={dim} P={max_period}")
+    ref = K.timestep_embedding(t, dim, max_period)[0]
+    zero = int((t == 0).nonzero()[0])
+    assert torch.equal(got[zero], ref[zero].to(F32)) and bool((got[zero, :dim // 2] == 1).all()) and not got[zero, dim // 2:].any()
+
+
+@gpu
+def test_timestep_embedding_refuses_odd_dim_and_periods_up_to_one():
+    from lcv_hip.lib import LcvError
+    t, out = torch.ones(2, dtype=F32, device=DEV), _nan(2 * 8, dtype=F32)
+    for dim, period in ((7, 10000.0), (8, 1.0), (8, 0.5), (0, 10000.0)):
+        with pytest.raises(LcvError) as e:
+            _call("lcv_timestep_embedding", _p(t), _p(out), 2, dim, period)
+        assert e.value.code == -1
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all()
+
+
+# ------------------------------------------------------------------------------------------------------ lcv_fm_mse_samples
+@gpu
+@pytest.mark.parametrize("B,C,T,Tc,HW,eps_pad,shared_x0", [
+    (3, 3, 2, 1, 35, 0, False),          # 105 target elements: one of the 256 part-blocks works, 255 must still write a zero
+    (2, 4, 3, 0, 50, 0, False),          # Tc = 0: every frame is a target
+    (1, 2, 4, 2, 33, 0, False),          # B = 1
+    (2, 1, 2, 1, 64 * 256, 0, False),    # 64 whole part-blocks
+    (2, 1, 2, 1, 256 * 256, 0, True),    # every lane of every part-block has exactly one element
+    (2, 1, 2, 1, 256 * 256 + 1, 0, False),   # and one lane a second
+    (3, 2, 3, 1, 100, 24, False),        # eps rows 24 elements apart
+    (3, 2, 3, 1, 100, 0, True),          # one x0 for every sample (stride 0)
+])
+def test_fm_mse_samples_edges(B, C, T, Tc, HW, eps_pad, shared_x0):
+    """LCV_FM_MSE_PARTS is 256: a sample is summed by 256 part-blocks of 256 lanes, so the sizes at which the code takes another
+    path are 256 x 256 elements (every lane exactly one) and one more (a lane's second pass); 64 x 256 leaves 192 part-blocks
+    idle.  `ws` is NaN first: a part-block that skipped its store would make the loss NaN.  Bound: kernel_ref.check_fm_mse_samples."""
+    from kernel_ref import FM_MSE_PARTS
+    Tt = T - Tc
+    per = C * Tt * HW
+    pred = _randn(B, C, T, HW, seed=81, dtype=F32)
+    eps_rows = _randn(B, per + eps_pad, seed=82)
+    x0 = _randn(1 if shared_x0 else B, C, Tt, HW, seed=83)
+    eps = eps_rows[:, :per].reshape(B, C, Tt, HW)                        # the values the kernel reads, as a tensor of their own
+    loss, ws = _nan(B + 8, dtype=F32), _nan(B * FM_MSE_PARTS, dtype=F32)  # an unwritten partial would make the loss NaN
+    args = (_p(pred), _p(eps_rows), _p(x0), _p(loss), _p(ws), B, C, T, Tc, HW, per + eps_pad, 0 if shared_x0 else per)
+    _call("lcv_fm_mse_samples", *args)
+    assert torch.isnan(loss[B:]).all() and torch.isfinite(ws).all()
+    K.check_fm_mse_samples(loss[:B], pred, eps, x0, Tc, what=f"fm_mse_samples B={B} C={C} T={T} Tc={Tc} HW={HW}")
+    loss2 = _nan(B + 8, dtype=F32)
+    _call("lcv_fm_mse_samples", *args[:3], _p(loss2), *args[4:])
+    assert torch.equal(loss[:B], loss2[:B])                              # fixed-order partial sums: the same bits
+
+
+@gpu
+def test_fm_mse_samples_refuses_overlapping_strides_and_no_target_frame():
+    from lcv_hip.lib import LcvError
+    B, C, T, Tc, HW = 2, 2, 3, 1, 10
+    per = C * (T - Tc) * HW
+    pred, e, x = _randn(B, C, T, HW, seed=84, dtype=F32), _randn(B, per, seed=85), _randn(B, per, seed=86)
+    loss, ws = _nan(B, dtype=F32), _nan(B * 256, dtype=F32)
+    for t, tc, es, xs in ((T, Tc, per - 1, per), (T, Tc, per, 1), (T, T, per, per), (T, T + 1, per, per), (T, -1, per, per)):
+        with pytest.raises(LcvError) as err:
+            _call("lcv_fm_mse_samples", _p(pred), _p(e), _p(x), _p(loss), _p(ws), B, C, t, tc, HW, es, xs)
+        assert err.value.code == -1
+    torch.cuda.synchronize()
+    assert torch.isnan(loss).all() and torch.isnan(ws).all()

@@ -3,6 +3,7 @@ off fails, one non-zero pad element fails, the exact rounding passes; every chec
 way and fails the results a kernel bug would give), and every compute entry point that include/lcv_hip.h
 declares has a kernel-level test (the coverage guard: a new entry point without one fails here, without a GPU)."""
 import ast
+import math
 import re
 from pathlib import Path
 
@@ -19,6 +20,7 @@ LORA_EDGES = "test_gpu_lora_kernel_edges.py"
 BWD_EDGES = "test_gpu_bwd_kernel_edges.py"
 UMT5_EDGES = "test_gpu_umt5_kernel_edges.py"
 ATTN_EDGES = "test_gpu_attn_kernel_edges.py"
+OPTIM_EDGES = "test_gpu_optim_kernel_edges.py"
 
 
 # ------------------------------------------------------------------------------------------------ assert_within itself
@@ -223,6 +225,54 @@ def test_linear_f32_smallm_bwd_check_against_autograd_and_teeth():
         _fails(K.check_linear_f32_smallm_bwd, ad2.grad.float(), dy, w, a, act)         # the last row of W dropped
         _fails(K.check_linear_f32_smallm_bwd, ad.grad.roll(1, 0).float(), dy, w, a, act)
     _fails(K.check_linear_f32_smallm_bwd, (dy.double() @ w.double()).float(), dy, w, a, 1)   # SiLU' forgotten
+
+
+def test_linear_f32_smallm_forward_check_against_torch_and_teeth():
+    M, N, K_ = 17, 33, 1032
+    a, w, b = _rn(M, K_, seed=61, scale=2.0, dtype=torch.float32), _rn(N, K_, seed=62, scale=0.05), _rn(N, seed=63)
+    for act in (0, 1):
+        right = (F.silu(a.double()) if act else a.double()) @ w.double().t() + b.double()
+        K.check_linear_f32_smallm(right.float(), a, w, b, act, 0.0, "right")
+        K.check_linear_f32_smallm((right - b.double()).float(), a, w, None, act, 0.0, "no bias")
+        _fails(K.check_linear_f32_smallm, (right - b.double()).float(), a, w, b, act, 0.0)            # the bias forgotten
+        short = (F.silu(a.double()) if act else a.double())[:, :-8] @ w.double()[:, :-8].t() + b.double()
+        _fails(K.check_linear_f32_smallm, short.float(), a, w, b, act, 0.0)                          # the last packet of K dropped
+        _fails(K.check_linear_f32_smallm, right.roll(1, 0).float(), a, w, b, act, 0.0)               # rows off by one
+        wrong = right.clone(); wrong[-1] = wrong[0]
+        _fails(K.check_linear_f32_smallm, wrong.float(), a, w, b, act, 0.0)                          # the second row group reads the first
+    _fails(K.check_linear_f32_smallm, (a.double() @ w.double().t() + b.double()).float(), a, w, b, 1, 1e-5)   # SiLU forgotten
+
+
+def test_timestep_embedding_restatement_against_the_oracle_and_teeth():
+    t = torch.tensor([0.0, -37.5, 612.0, 1000.0])
+    ref, arg = K.timestep_embedding(t, 342, 10000.0)
+    assert ref.shape == (4, 342) and torch.equal(ref[0, :171], torch.ones(171, dtype=torch.float64)) and not ref[0, 171:].any()
+    assert float(arg.max()) == 1000.0 and torch.equal(arg[:, :171], arg[:, 171:])
+    orc = _orc()
+    assert (orc.timestep_embedding(t, 256).double() - K.timestep_embedding(t, 256, 10000.0)[0]).abs().max() < 2e-4
+    K.check_timestep_embedding(ref.float(), t, 342, 10000.0, "right")
+    _fails(K.check_timestep_embedding, torch.cat([ref[:, 171:], ref[:, :171]], 1).float(), t, 342, 10000.0)      # sin in front
+    _fails(K.check_timestep_embedding, K.timestep_embedding(t, 342, 9990.0)[0].float(), t, 342, 10000.0)         # another period
+    half_off = torch.exp(-math.log(10000.0) * torch.arange(171, dtype=torch.float64) / 170)                       # j / (half - 1)
+    arg2 = t.double()[:, None] * half_off
+    _fails(K.check_timestep_embedding, torch.cat([arg2.cos(), arg2.sin()], 1).float(), t, 342, 10000.0)
+
+
+def test_fm_mse_samples_check_against_torch_and_teeth():
+    B, C, T, Tc, HW = 3, 3, 2, 1, 35
+    pred = _rn(B, C, T, HW, seed=64, dtype=torch.float32)
+    eps, x0 = _rn(B, C, T - Tc, HW, seed=65), _rn(1, C, T - Tc, HW, seed=66)
+    vt = (eps - x0).double()                                       # the bf16 subtraction, widened
+    d = pred.double()[:, :, Tc:] - vt
+    right = (d * d).flatten(1).mean(1)
+    K.check_fm_mse_samples(right.float(), pred, eps, x0, Tc, "right")
+    flat = (d * d).flatten(1)
+    _fails(K.check_fm_mse_samples, (flat[:, :-1].sum(1) / flat.shape[1]).float(), pred, eps, x0, Tc)      # the last element dropped
+    _fails(K.check_fm_mse_samples, right.roll(1).float(), pred, eps, x0, Tc)                               # samples off by one
+    d0 = pred.double()[:, :, :T - Tc] - vt
+    _fails(K.check_fm_mse_samples, (d0 * d0).flatten(1).mean(1).float(), pred, eps, x0, Tc)                # the conditioning frames read
+    exact = pred.double()[:, :, Tc:] - (eps.double() - x0.double())
+    _fails(K.check_fm_mse_samples, (exact * exact).flatten(1).mean(1).float(), pred, eps, x0, Tc)          # the target not rounded to bf16
 
 
 def test_swiglu_bwd_check_against_autograd_and_teeth():
@@ -653,7 +703,9 @@ KERNEL_TESTS = {
                             (BWD_EDGES, "test_qknorm_rope_fwd_leaves_v_alone_when_v_out_is_v_in")],
     "lcv_qknorm_rope_bwd": [("test_gpu_backward.py", "test_qknorm_rope_backward"),
                             ("test_gpu_backward.py", "test_qk_norm_weight_gradients"), (BWD_EDGES, "test_qknorm_rope_bwd_edges")],
-    "lcv_timestep_embedding": [("test_gpu_kernels.py", "test_timestep_embedding_matches_oracle")],
+    "lcv_timestep_embedding": [("test_gpu_kernels.py", "test_timestep_embedding_matches_oracle"),
+                               (EDGES, "test_timestep_embedding_edges"),
+                               (EDGES, "test_timestep_embedding_refuses_odd_dim_and_periods_up_to_one")],
     "lcv_attn_fwd": [("test_gpu_kernels.py", "test_attention_fuzz_against_the_restatement_of_the_kernels_arithmetic"),
                      (ATTN_EDGES, "test_attn_fwd_edges"), (ATTN_EDGES, "test_attn_fwd_wide_key_stride_takes_the_64_bit_body")],
     "lcv_attn_bwd": [("test_gpu_backward.py", "test_attention_backward_fuzz_against_the_kernels_rounding_points"),
@@ -666,7 +718,9 @@ KERNEL_TESTS = {
     "lcv_tn_skinny": [("test_gpu_backward.py", "test_linear_f32_backward_and_tn_skinny_and_unpatchify"),
                       (LORA_EDGES, "test_tn_skinny_workspace_path_edges"), (LORA_EDGES, "test_tn_skinny_atomic_path_edges"),
                       (LORA_EDGES, "test_tn_skinny_rejects_a_small_or_misaligned_workspace")],
-    "lcv_linear_f32_smallm": [("test_gpu_kernels.py", "test_linear_f32_smallm")],
+    "lcv_linear_f32_smallm": [("test_gpu_kernels.py", "test_linear_f32_smallm"), (EDGES, "test_linear_f32_smallm_edges"),
+                              (EDGES, "test_linear_f32_smallm_silu_error"),
+                              (EDGES, "test_linear_f32_smallm_refuses_what_it_cannot_stage")],
     "lcv_linear_f32_smallm_bwd": [("test_gpu_backward.py", "test_linear_f32_backward_and_tn_skinny_and_unpatchify"),
                                   (BWD_EDGES, "test_linear_f32_smallm_bwd_edges")],
     "lcv_swiglu_fwd": [(EDGES, "test_swiglu_fwd_on_views_into_one_buffer_past_the_block_cap")],
@@ -681,11 +735,21 @@ KERNEL_TESTS = {
     "lcv_euler_step": [(EDGES, "test_euler_step_edges")],
     "lcv_fm_noise": [(EDGES, "test_fm_noise_past_the_block_cap")],
     "lcv_fm_mse": [(EDGES, "test_fm_mse_past_the_block_cap_and_deterministic")],
-    "lcv_fm_mse_samples": [("test_gpu_early_stopping.py", "test_fm_mse_samples_matches_torch_and_is_deterministic")],
+    "lcv_fm_mse_samples": [("test_gpu_early_stopping.py", "test_fm_mse_samples_matches_torch_and_is_deterministic"),
+                           (EDGES, "test_fm_mse_samples_edges"),
+                           (EDGES, "test_fm_mse_samples_refuses_overlapping_strides_and_no_target_frame")],
     "lcv_grad_norm_clip": [("test_gpu_backward.py", "test_fused_adamw_clip_matches_reference_trace"),
-                           ("test_gpu_backward.py", "test_joint_clip_over_bf16_and_fp32_parameters_matches_torch")],
-    "lcv_adamw_step": [("test_gpu_backward.py", "test_fused_adamw_clip_matches_reference_trace")],
-    "lcv_sgd_step": [("test_gpu_backward.py", "test_fused_sgd_clip_matches_torch")],
+                           ("test_gpu_backward.py", "test_joint_clip_over_bf16_and_fp32_parameters_matches_torch"),
+                           (OPTIM_EDGES, "test_step_bits"), (OPTIM_EDGES, "test_301_tensors_one_clipped_step_bits")],
+    "lcv_adamw_step": [("test_gpu_backward.py", "test_fused_adamw_clip_matches_reference_trace"), (OPTIM_EDGES, "test_step_bits"),
+                       (OPTIM_EDGES, "test_301_tensors_one_clipped_step_bits"),
+                       (OPTIM_EDGES, "test_fp32_step_and_master_weight_step_with_fp32_gradient_are_one_arithmetic"),
+                       (OPTIM_EDGES, "test_special_elements"), (OPTIM_EDGES, "test_torch_device_optimizer_against_the_restatement")],
+    "lcv_sgd_step": [("test_gpu_backward.py", "test_fused_sgd_clip_matches_torch"), (OPTIM_EDGES, "test_step_bits"),
+                     (OPTIM_EDGES, "test_301_tensors_one_clipped_step_bits"),
+                     (OPTIM_EDGES, "test_sgd_packet_path_and_element_path_are_one_arithmetic"),
+                     (OPTIM_EDGES, "test_fp32_step_and_master_weight_step_with_fp32_gradient_are_one_arithmetic"),
+                     (OPTIM_EDGES, "test_special_elements"), (OPTIM_EDGES, "test_torch_device_optimizer_against_the_restatement")],
     "lcv_transpose_pad": [(EDGES, "test_transpose_pad_and_rowsum_edges")],
     "lcv_rowsum": [(EDGES, "test_transpose_pad_and_rowsum_edges"), (EDGES, "test_rowsum_cols_not_a_multiple_of_512")],
     "lcv_linear_f32_smallm_wgrad": [(EDGES, "test_linear_f32_smallm_wgrad_edges")],
