@@ -173,6 +173,15 @@ _SIGNATURES_SR = {
     "lcv_sr_round": [P, P, I64, U64, U64, P],
 }
 
+# include/lcv_hip_dora.h (a header of its own: the row norm and the column scale of weight-decomposed LoRA): norm takes (w, a, b,
+# double scaling, N, K, R, wn_out), fwd (pre, m, wn, bias, y, M, N), bwd (dy, pre, m, wn, dpre, dm, ws, ws_bytes, M, N); all return int
+_SIGNATURES_DORA = {
+    "lcv_dora_weight_norm": [P, P, P, F64, I64, I64, I64, P, P],
+    "lcv_dora_colscale_fwd": [P, P, P, P, P, I64, I64, P],
+    "lcv_dora_colscale_bwd": [P, P, P, P, P, P, P, I64, I64, I64, P],
+}
+LCV_DORA_NORM_KTILE, LCV_DORA_NORM_ROWS, LCV_DORA_SLAB, LCV_DORA_SLAB_QUARTER = 512, 16, 64, 16
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -228,11 +237,14 @@ def load():
     lib.lcv_det_ws_bytes.argtypes = [I, I64, I64, I64]
     lib.lcv_tn_skinny_dropout_ws_bytes.restype = c_int64   # likewise
     lib.lcv_tn_skinny_dropout_ws_bytes.argtypes = [I64, I64, I64]
+    lib.lcv_dora_colscale_bwd_ws_bytes.restype = c_int64   # likewise
+    lib.lcv_dora_colscale_bwd_ws_bytes.argtypes = [I64, I64]
     for name, args in (list(_SIGNATURES.items()) + list(_SIGNATURES_LPIPS.items()) + list(_SIGNATURES_DET.items())
                        + list(_SIGNATURES_LORA.items()) + list(_SIGNATURES_MASTER.items()) + list(_SIGNATURES_MOMENTS8.items())
                        + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())
                        + list(_SIGNATURES_STEPCACHE.items()) + list(_SIGNATURES_SOLVER.items())
-                       + list(_SIGNATURES_CFGREUSE.items()) + list(_SIGNATURES_SR.items()) + list(_SIGNATURES_APG.items())):
+                       + list(_SIGNATURES_CFGREUSE.items()) + list(_SIGNATURES_SR.items()) + list(_SIGNATURES_APG.items())
+                       + list(_SIGNATURES_DORA.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

@@ -353,6 +353,67 @@ def lora_dropout_mask(M: int, K: int, p: float, seed: int, offset: int, row0: in
     return out
 
 
+# ---------------------------------------------------- weight-decomposed LoRA ---
+# include/lcv_hip_dora.h: wn = |W + s B A| per row, and the column scale c = m / wn of the LoRA GEMM's output
+def dora_weight_norm(w: torch.Tensor, A: Optional[torch.Tensor] = None, B: Optional[torch.Tensor] = None, s: float = 0.0,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wn fp32 [N] = |w[n, :] + s * B[n, :] A|_2 (w bf16 [N, K], A bf16 [R, K], B bf16 [N, R]); without A and B, |w[n, :]|_2."""
+    _req(w, BF16, "dora_weight_norm.w")
+    if w.dim() != 2 or not w.is_contiguous():
+        raise _lib.LcvError("dora_weight_norm: w must be 2-D and contiguous")
+    N, K = w.shape
+    if (A is None) != (B is None):
+        raise _lib.LcvError("dora_weight_norm: A and B come together")
+    R = 0
+    if A is not None:
+        _req(A, BF16, "dora_weight_norm.A"); _req(B, BF16, "dora_weight_norm.B")
+        R = A.shape[0]
+        if A.shape != (R, K) or B.shape != (N, R) or not A.is_contiguous() or not B.is_contiguous():
+            raise _lib.LcvError("dora_weight_norm: A must be [R, K] and B [N, R], both contiguous")
+    out = torch.empty((N,), dtype=F32, device=w.device) if out is None else out
+    _req(out, F32, "dora_weight_norm.out")
+    if out.shape != (N,) or not out.is_contiguous():
+        raise _lib.LcvError("dora_weight_norm: out must be a contiguous [N] tensor")
+    call("lcv_dora_weight_norm", _ptr(w), _ptr(A), _ptr(B), float(s), N, K, R, _ptr(out), _stream())
+    return out
+
+
+def _dora_req(name: str, N: int, m: torch.Tensor, wn: torch.Tensor, *mats) -> None:
+    _req(m, F32, name + ".m"); _req(wn, F32, name + ".wn")
+    if m.shape != (N,) or wn.shape != (N,) or not m.is_contiguous() or not wn.is_contiguous():
+        raise _lib.LcvError(f"{name}: m and wn must be contiguous [N] tensors")
+    for t in mats:
+        _req(t, BF16, name)
+        if t.dim() != 2 or t.shape != mats[0].shape or not t.is_contiguous():
+            raise _lib.LcvError(f"{name}: the matrices must be 2-D, contiguous and of one shape")
+
+
+def dora_colscale_fwd(pre: torch.Tensor, m: torch.Tensor, wn: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = bf16(pre * (m / wn) + bias), column-wise; `out` may be `pre` itself."""
+    out = torch.empty_like(pre) if out is None else out
+    _dora_req("dora_colscale_fwd", pre.shape[-1], m, wn, pre, out)
+    M, N = pre.shape
+    if bias is not None:
+        _req(bias, BF16, "dora_colscale_fwd.bias")
+        if bias.shape != (N,) or not bias.is_contiguous():
+            raise _lib.LcvError("dora_colscale_fwd: bias must be a contiguous [N] tensor")
+    call("lcv_dora_colscale_fwd", _ptr(pre), _ptr(m), _ptr(wn), _ptr(bias), _ptr(out), M, N, _stream())
+    return out
+
+
+def dora_colscale_bwd(dy: torch.Tensor, pre: torch.Tensor, m: torch.Tensor, wn: torch.Tensor):
+    """(dpre bf16 [M, N], dm fp32 [N]) = (dy * (m / wn), (sum_t dy * pre) / wn), the sum in fixed slab order."""
+    _dora_req("dora_colscale_bwd", pre.shape[-1], m, wn, dy, pre)
+    M, N = pre.shape
+    dpre = torch.empty_like(dy)
+    dm = torch.empty((N,), dtype=F32, device=dy.device)
+    ws_bytes = int(_lib.load().lcv_dora_colscale_bwd_ws_bytes(M, N))
+    ws = torch.empty((max(ws_bytes, 16) // 4,), dtype=F32, device=dy.device)    # per-slab partial sums (caching allocator)
+    call("lcv_dora_colscale_bwd", _ptr(dy), _ptr(pre), _ptr(m), _ptr(wn), _ptr(dpre), _ptr(dm), _ptr(ws), ws_bytes, M, N, _stream())
+    return dpre, dm
+
+
 def swiglu(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
     _req(gate, BF16, "swiglu.gate"); _req(up, BF16, "swiglu.up")
     rows, F = gate.shape

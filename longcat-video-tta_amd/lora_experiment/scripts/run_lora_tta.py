@@ -32,8 +32,8 @@ from tta import runner_common as R  # noqa: E402
 from tta.inner_loop import finetune_lora_on_conditioning  # noqa: E402
 from tta.lora import (count_builtin_lora_parameters, get_builtin_lora_parameters, inject_builtin_lora_into_dit,  # noqa: E402
                       reset_builtin_lora_weights, save_builtin_lora_weights)
-from tta.lora import (count_lora_parameters, get_lora_parameters, inject_lora_into_dit, reset_lora_weights,  # noqa: E402
-                      save_lora_weights)
+from tta.lora import (count_lora_parameters, get_dora_magnitudes, get_lora_parameters, inject_lora_into_dit,  # noqa: E402
+                      reset_lora_weights, save_lora_weights)
 
 
 def build_parser():
@@ -43,6 +43,11 @@ def build_parser():
     p.add_argument("--lora-rank", type=int, default=8)
     p.add_argument("--lora-alpha", type=float, default=16.0)
     p.add_argument("--lora-dropout", type=float, default=0.0)
+    p.add_argument("--lora-dora", action="store_true",
+                   help="weight-decomposed LoRA: every adapted linear also trains an fp32 magnitude per output, y = (m / |W + s B A|) "
+                        "(.) (x W^T + s (x A^T) B^T) + b, the row norm a constant of the backward (include/lcv_hip_dora.h); custom "
+                        "implementation only, not with --master-weights, --adam-8bit, --grad-accum above 1, --weight-ema or "
+                        "--stochastic-rounding")
     p.add_argument("--target-ffn", action="store_true")
     p.add_argument("--target-modules", type=str, default="qkv,proj")
     p.add_argument("--lora-target-blocks", type=str, default="all")
@@ -63,13 +68,36 @@ def build_parser():
     return p
 
 
+def check_lora_dora_args(args) -> None:
+    """--lora-dora trains fp32 magnitudes with a plain AdamW of their own beside the bf16 adapters' (tta.inner_loop); the
+    combinations that optimizer pair does not cover are refused here, before a model is loaded."""
+    if not getattr(args, "lora_dora", False):
+        return
+    refusals = [
+        (args.use_builtin_lora, "--use-builtin-lora (the builtin adapters are hooked forwards without a magnitude)"),
+        (args.master_weights, "--master-weights (the magnitudes are fp32 already, and the joint clip reads bf16 .grad)"),
+        (args.adam_8bit, "--adam-8bit (a master-weight form)"),
+        (args.grad_accum > 1, "--grad-accum above 1 (the magnitudes' optimizer has no accumulators)"),
+        (args.weight_ema is not None, "--weight-ema (the average is kept beside master weights only)"),
+        (args.stochastic_rounding, "--stochastic-rounding (an fp32 magnitude has nothing to round, and a joint run would mix "
+                                   "the two forms)"),
+    ]
+    for refused, what in refusals:
+        if refused:
+            raise ValueError(f"--lora-dora cannot be combined with {what}")
+
+
 def parse_args(argv=None):
-    return C.parse_with_step_cache(build_parser(), argv, C.parse_optimizer_args)
+    args = C.parse_with_step_cache(build_parser(), argv, C.parse_optimizer_args)
+    check_lora_dora_args(args)
+    return args
 
 
 def lora_method(args) -> R.TTAMethod:
     """The LoRA job as `R.run_tta_job` takes it: adapters injected once (custom or builtin, run_lora_tta.py:783, 818-846) and
     reset for every video, `config.json` in the reference's layout, `<name>_lora.pt` under --save-lora-weights."""
+    check_lora_dora_args(args)
+    dora = bool(getattr(args, "lora_dora", False))
     target_modules = [m.strip() for m in args.target_modules.split(",") if m.strip()]
     impl = "builtin" if args.use_builtin_lora else "custom"
     if impl == "builtin":                                      # its injector takes no dropout
@@ -77,7 +105,7 @@ def lora_method(args) -> R.TTAMethod:
         count, get_params, reset, save = (count_builtin_lora_parameters, get_builtin_lora_parameters, reset_builtin_lora_weights,
                                           save_builtin_lora_weights)
     else:
-        inject, inject_kw = inject_lora_into_dit, {"dropout": args.lora_dropout}
+        inject, inject_kw = inject_lora_into_dit, {"dropout": args.lora_dropout, **({"dora": True} if dora else {})}   # flag absent: today's call
         count, get_params, reset, save = count_lora_parameters, get_lora_parameters, reset_lora_weights, save_lora_weights
     lora_dir = os.path.join(args.output_dir, "lora_weights")
     lora_modules = []                                          # filled once the model is loaded
@@ -94,7 +122,7 @@ def lora_method(args) -> R.TTAMethod:
         gate = R.clip_gate_summary(args)
         return {"method": f"lora_tta_{impl}",
                 "lora": {"implementation": impl, "rank": args.lora_rank, "alpha": args.lora_alpha,
-                         "dropout": args.lora_dropout, "target_modules": target_modules,
+                         "dropout": args.lora_dropout, **({"dora": True} if dora else {}), "target_modules": target_modules,
                          "target_blocks": args.lora_target_blocks, "target_ffn": args.target_ffn,
                          "num_modules": len(lora_modules), "trainable_params": count(lora_modules)["trainable"]},
                 "training": {"learning_rate": args.learning_rate, "num_steps": args.num_steps,
@@ -116,6 +144,7 @@ def lora_method(args) -> R.TTAMethod:
                                              weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm, device=device,
                                              dtype=torch.bfloat16, early_stopper=es,
                                              lora_param_fn=lambda: get_params(lora_modules), train_latents_variants=variants,
+                                             **({"dora_magnitudes": get_dora_magnitudes(lora_modules)} if dora else {}),
                                              **C.optimizer_kwargs(args))
 
     def row_extra(tr, variants, blob):

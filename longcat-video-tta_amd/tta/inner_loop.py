@@ -241,6 +241,33 @@ def refuse_stochastic_rounding_under_sp(module, stochastic_rounding: bool) -> No
                          "the same rounding bits)")
 
 
+def _dora_optimizer(dit, dora_magnitudes, lr: float, **refused) -> Optional[FusedAdamWClip]:
+    """The second optimizer of a DoRA run (tta/lora.py, include/lcv_hip_dora.h): an fp32 table over the magnitudes with the
+    adapters' lr and betas and no weight decay (a decay would pull every row's length toward zero).  None without magnitudes.
+    The options that belong to the bf16 master-weight forms, and sequence parallelism (the magnitudes' gradients would need a
+    sync of their own), are refused before anything is built."""
+    if not dora_magnitudes:
+        return None
+    on = [name for name, value in refused.items() if value]
+    if on:
+        raise ValueError(f"DoRA magnitudes cannot be combined with {', '.join(on)}: the fp32 magnitudes are stepped by a plain "
+                         "AdamW tied to the adapters' by a joint clip, which those forms do not take part in")
+    if getattr(getattr(dit, "dit", dit), "_sp_group", None) is not None:
+        raise ValueError("DoRA magnitudes cannot be combined with sequence parallelism (their gradients are not synchronised)")
+    if any(m.dtype != torch.float32 for m in dora_magnitudes):
+        raise ValueError("DoRA magnitudes must be fp32 (a bf16 magnitude loses every update at these learning rates)")
+    return FusedAdamWClip(list(dora_magnitudes), lr=lr, betas=(0.9, 0.999), weight_decay=0.0, eps=1e-8)
+
+
+def _joint_optimizer_step(opts, max_grad_norm: float) -> Callable[[], None]:
+    """One clip coefficient over both optimizers' gradients, as the norm + delta tuning loop has it (tta/delta.py)."""
+    def go():
+        FusedAdamWClip.joint_clip_grad_norm_(opts, max_grad_norm)
+        for opt in opts:
+            opt.step()
+    return go
+
+
 # ------------------------------------------------------------------------------------------------ public: LoRA
 def _adapter_params(lora_modules, lora_param_fn) -> List[torch.Tensor]:
     params = lora_param_fn() if lora_param_fn is not None else get_lora_parameters(lora_modules)
@@ -256,12 +283,18 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
                                   device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                                   early_stopper: Optional[AnchoredEarlyStopper] = None, lora_param_fn=None,
                                   train_latents_variants: Optional[List[Dict]] = None, stochastic_rounding: bool = False,
+                                  dora_magnitudes: Optional[Sequence[torch.Tensor]] = None,
                                   *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                                   grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """`stochastic_rounding`: the bf16 adapters and moments take the fp32 step with stochastically rounded stores
-    (include/lcv_hip_sr.h); no state beside them, so the stopper's snapshot and restore are the plain form's."""
+    (include/lcv_hip_sr.h); no state beside them, so the stopper's snapshot and restore are the plain form's.
+    `dora_magnitudes`: the fp32 magnitudes of DoRA adapters (tta.lora.get_dora_magnitudes), stepped by an optimizer of their own
+    under one joint clip; the stopper's snapshot covers both lists."""
     params = _adapter_params(lora_modules, lora_param_fn)
     refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
+    dora_opt = _dora_optimizer(dit, dora_magnitudes, lr, master_weights=master_weights, moments_8bit=moments_8bit,
+                               stochastic_rounding=stochastic_rounding, weight_ema=weight_ema is not None,
+                               **{"grad_accum > 1": grad_accum > 1})
     # made per call, so per video: the low words of `master_weights` start at zero next to freshly reset adapters
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
                          master_weights=master_weights, moments_8bit=moments_8bit, stochastic_rounding=stochastic_rounding,
@@ -269,6 +302,10 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
     if weight_ema is not None:       # the fp32 average of the adapters (+4 B / parameter): scored by the stopper, left in the
         opt.enable_weight_ema(weight_ema, ema_warmup)    # adapters at the end (see run_adaptation)
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
+    if dora_opt is not None:
+        opts = [opt, dora_opt]
+        return run_adaptation(dit, params + list(dora_magnitudes), opts, _fm_loss(dit, feed, device, dtype),
+                              _joint_optimizer_step(opts, max_grad_norm), num_steps, lr, warmup_steps, early_stopper)
     return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
                           num_steps, lr, warmup_steps, early_stopper, grad_sync=_sp_sync(dit, opt), grad_accum=grad_accum)
 
@@ -276,19 +313,27 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
 def finetune_lora_batch(dit: nn.Module, lora_modules, batch_data: List[Dict], num_steps: int = 20, lr: float = 2e-4,
                         warmup_steps: int = 3, weight_decay: float = 0.01, max_grad_norm: float = 1.0,
                         device: str = "cuda", dtype: torch.dtype = torch.bfloat16, lora_param_fn=None,
-                        stochastic_rounding: bool = False,
+                        stochastic_rounding: bool = False, dora_magnitudes: Optional[Sequence[torch.Tensor]] = None,
                         *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Shared adapters trained round-robin over the eval video and its neighbours; no early stopping (:558-634).  The feed
     receives the micro-step index, so `grad_accum` = number of videos puts every video behind each update.  `weight_ema`: the
-    adapters end as their fp32 average over the steps.  `stochastic_rounding`: as in `finetune_lora_on_conditioning`."""
+    adapters end as their fp32 average over the steps.  `stochastic_rounding` and `dora_magnitudes`: as in
+    `finetune_lora_on_conditioning`."""
     params = _adapter_params(lora_modules, lora_param_fn)
     refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
+    dora_opt = _dora_optimizer(dit, dora_magnitudes, lr, master_weights=master_weights, moments_8bit=moments_8bit,
+                               stochastic_rounding=stochastic_rounding, weight_ema=weight_ema is not None,
+                               **{"grad_accum > 1": grad_accum > 1})
     opt = FusedAdamWClip(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, eps=1e-8,
                          master_weights=master_weights, moments_8bit=moments_8bit, stochastic_rounding=stochastic_rounding,
                          grad_accum=grad_accum)
     if weight_ema is not None:
         opt.enable_weight_ema(weight_ema, ema_warmup)
     feed = _RoundRobin(batch_data, device)
+    if dora_opt is not None:
+        opts = [opt, dora_opt]
+        return run_adaptation(dit, params + list(dora_magnitudes), opts, _fm_loss(dit, feed, device, dtype),
+                              _joint_optimizer_step(opts, max_grad_norm), num_steps, lr, warmup_steps, None)
     return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
                           num_steps, lr, warmup_steps, None, grad_sync=_sp_sync(dit, opt), grad_accum=grad_accum)

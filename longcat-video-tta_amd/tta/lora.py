@@ -8,6 +8,9 @@ With dropout p > 0 in train() the adapter sees xd = bf16(x * mask * scale) inste
 mask is a pure function of (seed, offset, element index) (include/lcv_hip_lora.h) and is regenerated where it is needed:
   forward   hs = s * bf16(xd A^T) by lora_down_dropout, then the same GEMM
   backward  dx = dy W (plain GEMM) + mask * scale * (g A) by lora_dx_dropout_add;  dA = g^T xd by tn_skinny_dropout
+With `dora=True` (weight-decomposed LoRA, include/lcv_hip_dora.h) the same function produces the bracket `pre` without the bias,
+and a column scale follows:  y = c (.) pre + b,  c = m / wn,  wn = |W + s B A| per row, a constant of the backward, cached until
+an adapter changes;  m is an fp32 parameter that starts at |W|, so that c == 1 while B = 0.
 """
 import math
 from typing import Callable, Dict, List, Optional
@@ -60,6 +63,23 @@ class _LoRALinearFn(torch.autograd.Function):
         return dx, None, None, dA.to(lora_a.dtype), dB.to(lora_b.dtype), None, None
 
 
+class _DoRAScaleFn(torch.autograd.Function):
+    """y = bf16(pre * (m / wn) + b) column-wise; `wn` is a constant (the detached norm of the adapted weight).  Saves `pre`: one
+    output-sized bf16 tensor per adapted linear."""
+
+    @staticmethod
+    def forward(ctx, pre, m, wn, b):
+        y = ops.dora_colscale_fwd(pre, m.detach(), wn, b)
+        ctx.save_for_backward(pre, m, wn)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        pre, m, wn = ctx.saved_tensors
+        dpre, dm = ops.dora_colscale_bwd(dy.contiguous(), pre, m.detach(), wn)
+        return dpre, dm, None, None
+
+
 # Observer of the dropout draws: when set, called as DRAW_HOOK(module, seed, offset) for every training forward with p > 0
 # (a recomputed forward under gradient checkpointing included).  For tests and for debugging a run; None costs nothing.
 DRAW_HOOK: Optional[Callable] = None
@@ -73,7 +93,7 @@ draw_dropout_offset = ops.draw_philox_offset
 class LoRALinear(nn.Module):
     """Low-rank adapter around an existing nn.Linear (frozen).  Output = original(x) + up(down(x)) * alpha / rank."""
 
-    def __init__(self, original: nn.Linear, rank: int = 8, alpha: float = 16.0, dropout: float = 0.0):
+    def __init__(self, original: nn.Linear, rank: int = 8, alpha: float = 16.0, dropout: float = 0.0, dora: bool = False):
         super().__init__()
         if rank < 1 or rank > 32:
             raise ValueError("LoRA rank must be in 1..32 for the fused kernels")
@@ -86,6 +106,49 @@ class LoRALinear(nn.Module):
         self.dropout = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
         nn.init.kaiming_uniform_(self.lora_down.weight, a=math.sqrt(5))
         nn.init.zeros_(self.lora_up.weight)
+        self.dora = bool(dora)
+        self._dora_wn = None          # (key, wn): the row norms of W + s B A and what they were computed from
+        if self.dora:
+            # fp32 whatever the module is cast to (see _apply): next to a bf16 magnitude of about 1.3 every AdamW update at
+            # lr 2e-4 is below half an ulp and would be lost (the argument of include/lcv_hip_master.h)
+            self.dora_magnitude = nn.Parameter(torch.zeros(original.out_features, dtype=torch.float32,
+                                                           device=original.weight.device))
+            self._dora_ready = False
+            if original.weight.is_cuda and original.weight.dtype == torch.bfloat16:
+                self.reset_dora_magnitude()
+
+    def _apply(self, fn, *args, **kwargs):
+        """`.to(dtype=bf16)` (inject_lora_into_dit) casts the adapters; the magnitude follows the device and stays fp32, without
+        passing through bf16 on the way."""
+        m = self._parameters.pop("dora_magnitude", None) if self.dora else None
+        super()._apply(fn, *args, **kwargs)
+        if m is not None:
+            moved = fn(m.data)
+            m.data = moved if moved.dtype == torch.float32 else m.data.to(device=moved.device)
+            self._parameters["dora_magnitude"] = m
+            self._dora_wn = None
+        return self
+
+    def reset_dora_magnitude(self) -> None:
+        """m = |W[n, :]|, by the kernel that computes wn (minus the adapter term): c == 1 to the bit while B = 0."""
+        if not self.dora:
+            return
+        with torch.no_grad():
+            ops.dora_weight_norm(self.original.weight.detach(), out=self.dora_magnitude.data)
+        self._dora_ready = True
+        self._dora_wn = None
+
+    def dora_weight_norm(self) -> torch.Tensor:
+        """wn fp32 [out], recomputed only when W, A or B changed: the fused optimizers write through raw pointers and bump
+        ops.PARAM_EPOCH, everything else (reset, the stopper's restore, a load, copy_) bumps the tensors' `_version`.  A forward
+        recomputed under gradient checkpointing finds the key unchanged and reuses the norm."""
+        w, a, b = self.original.weight, self.lora_down.weight, self.lora_up.weight
+        key = (ops.PARAM_EPOCH, w._version, a._version, b._version, w.data_ptr(), a.data_ptr(), b.data_ptr())
+        if self._dora_wn is None or self._dora_wn[0] != key:
+            with torch.no_grad():
+                wn = ops.dora_weight_norm(w.detach(), a.detach(), b.detach(), self.scaling)   # a new tensor: a graph may hold the old
+            self._dora_wn = (key, wn)
+        return self._dora_wn[1]
 
     @property
     def in_features(self):
@@ -109,6 +172,14 @@ class LoRALinear(nn.Module):
             if DRAW_HOOK is not None:
                 DRAW_HOOK(self, seed, offset)
             draw = (float(self.dropout.p), seed, offset)
+        if self.dora:
+            if not self._dora_ready:
+                raise LcvError("LoRALinear(dora=True): the magnitude is not initialised; call reset_dora_magnitude() once the "
+                               "module lives on the GPU")
+            pre = _LoRALinearFn.apply(x2.contiguous(), self.original.weight, None, self.lora_down.weight,
+                                      self.lora_up.weight, self.scaling, draw)
+            y = _DoRAScaleFn.apply(pre, self.dora_magnitude, self.dora_weight_norm(), self.original.bias)
+            return y.view(*shp[:-1], self.original.out_features)
         y = _LoRALinearFn.apply(x2.contiguous(), self.original.weight, self.original.bias, self.lora_down.weight,
                                 self.lora_up.weight, self.scaling, draw)
         return y.view(*shp[:-1], self.original.out_features)
@@ -133,9 +204,10 @@ def _parse_target_blocks(target_blocks: str, num_blocks: int) -> Optional[set]:
 
 def inject_lora_into_dit(dit: nn.Module, rank: int = 8, alpha: float = 16.0, dropout: float = 0.0,
                          target_modules=("qkv", "proj"), target_ffn: bool = False,
-                         target_blocks: str = "all") -> List[LoRALinear]:
+                         target_blocks: str = "all", dora: bool = False) -> List[LoRALinear]:
     """`setattr`-replace attn.{qkv,proj}, cross_attn.{q_linear,kv_linear,proj} and optionally ffn.w{1,2,3} of the
-    selected blocks; the returned order is the optimizer's parameter order."""
+    selected blocks; the returned order is the optimizer's parameter order.  `dora`: every adapter also owns an fp32
+    magnitude (get_dora_magnitudes)."""
     lora_modules: List[LoRALinear] = []
     device = next(dit.parameters()).device
     dtype = next(dit.parameters()).dtype
@@ -149,7 +221,7 @@ def inject_lora_into_dit(dit: nn.Module, rank: int = 8, alpha: float = 16.0, dro
         orig = getattr(owner, name)
         if not isinstance(orig, nn.Linear):
             return
-        lora = LoRALinear(orig, rank=rank, alpha=alpha, dropout=dropout).to(device=device, dtype=dtype)
+        lora = LoRALinear(orig, rank=rank, alpha=alpha, dropout=dropout, dora=dora).to(device=device, dtype=dtype)
         setattr(owner, name, lora)
         lora_modules.append(lora)
 
@@ -196,17 +268,29 @@ def get_lora_parameters(lora_modules: List[LoRALinear]) -> List[nn.Parameter]:
     return params
 
 
+def get_dora_magnitudes(lora_modules: List[LoRALinear]) -> List[nn.Parameter]:
+    """The fp32 magnitudes of the adapters made with dora=True, in injection order (an optimizer of their own steps them)."""
+    return [lora.dora_magnitude for lora in lora_modules if getattr(lora, "dora", False)]
+
+
 def count_lora_parameters(lora_modules: List[LoRALinear]) -> Dict[str, int]:
     total = sum(p.numel() for lora in lora_modules for p in lora.parameters())
     trainable = sum(p.numel() for lora in lora_modules
                     for p in [*lora.lora_down.parameters(), *lora.lora_up.parameters()])
-    return {"total_lora": total, "trainable": trainable}
+    counts = {"total_lora": total, "trainable": trainable}
+    magnitudes = get_dora_magnitudes(lora_modules)
+    if magnitudes:
+        counts["dora_magnitude"] = sum(m.numel() for m in magnitudes)
+        counts["trainable"] += counts["dora_magnitude"]
+    return counts
 
 
 def reset_lora_weights(lora_modules: List[LoRALinear]):
     for lora in lora_modules:
         nn.init.kaiming_uniform_(lora.lora_down.weight, a=math.sqrt(5))
         nn.init.zeros_(lora.lora_up.weight)
+        if getattr(lora, "dora", False):
+            lora.reset_dora_magnitude()           # m = |W|, and the cached norm is dropped
 
 
 def save_lora_weights(lora_modules: List[LoRALinear], path: str):
@@ -214,6 +298,8 @@ def save_lora_weights(lora_modules: List[LoRALinear], path: str):
     for i, lora in enumerate(lora_modules):
         state[f"lora_{i}.down"] = lora.lora_down.weight.detach().cpu()
         state[f"lora_{i}.up"] = lora.lora_up.weight.detach().cpu()
+        if getattr(lora, "dora", False):
+            state[f"lora_{i}.magnitude"] = lora.dora_magnitude.detach().cpu()
     torch.save(state, path)
 
 
