@@ -33,9 +33,12 @@ struct AttnFwdW64Params : AttnFwdLead {
 // 8-cycle transcendental (MI355X issue-cost constants: v_exp 8, v_cvt_pk 5, the rest 4).  An iteration carries more than the
 // 64 gaps can hide once the row sums are scalar (64 exp, 32 pack, 64 add, 32 max3, 48 fragment reads and their waits, 8 DMA
 // pieces, 8 offset moves: ~1 560 issue-cycles against 64 x 24), so the table spreads the load: 3 exps per 2 gaps in phase 1
-// with the pair on the read-free (even) gaps, phase 2's exps over gaps 0..21, its DMA pieces on the read-free even gaps 0..14,
-// the row-max chain in gaps 8..23 and its exchange / ballot in the otherwise empty tail.  tools/mfma_gaps.py prices the
-// compiler's output gap by gap; tests/test_attn_fwd_gap_budget.py holds it there.
+// with the pair on the read-free (even) gaps.  Phase 2 is laid out level: gap 0 holds one exp only, its DMA pieces sit on the
+// read-free even gaps 2..16 with what their compiled scalar extras leave room for, its exps run one per gap over gaps 0..11 and
+// 18..22 (the last pack two gaps ahead of the PV MFMA that reads it), and the two row-max chains run one behind the other (block
+// 0 in gaps 12..22, block 1 in gaps 19..27) so that no odd gap carries two max steps; the row sums of elements 28..31, the half
+// exchanges and the ballots fill the tail.  tools/mfma_gaps.py prices the compiler's output gap by gap;
+// tests/test_attn_fwd_gap_budget.py and tests/test_attn_fwd_gap_level.py hold it there.
 // Order inside a gap is the order of the entries: packs / adds of earlier exps first, the gap's own exps last, and every pack
 // far ahead of the PV MFMA that reads it.  Every odd gap OPENS with the fragment read that the MFMA after it used to ask for (its
 // ring slot is free: the MFMA in front of the gap was the last to read it) and closes with the wait of an earlier one.  Those
@@ -44,13 +47,14 @@ template <int I, int N, class F>
 __device__ __forceinline__ void w64_static_for(F&& f) {
   if constexpr (I < N) { f(std::integral_constant<int, I>{}); w64_static_for<I + 1, N>(f); }
 }
-enum : unsigned char { W64_NONE, W64_EXP, W64_ADD, W64_PACK, W64_LRUN, W64_VOFF, W64_MAX, W64_HMAX, W64_BALLOT, W64_M0, W64_DMA };
+enum : unsigned char { W64_NONE, W64_EXP, W64_ADD, W64_PACK, W64_LRUN, W64_VOFF, W64_MAX, W64_HCPY, W64_HSWAP, W64_HMAX, W64_BALLOT, W64_M0, W64_DMA };
 struct W64Op { unsigned char kind, b, e; };   // b: query block (or DMA piece / offset index), e: element / pair / max step
 constexpr int W64_SLOTS = 6;
 // EXP b e: ex[b][e] = exp2(S(t)[b][e]) | ADD b e: psum[b] += ex[b][e] (e = 1: psum = ex[0] + ex[1]), the two-wave kernel's
 // order | PACK b m: pw[b][m] = bf16(ex[b][2m], ex[b][2m+1]) | LRUN b: l_run[b] += psum[b] | VOFF k: V read offset k to tile
-// t's slot | MAX b s: step s of block b's two max3 chains over S(t+1) | HMAX b: exchange with the partner half | BALLOT b:
-// rescale test | M0 d / DMA d: LDS destination and request of DMA piece d (d < 4: K(t+3), else V(t+2)), one gap apart or more
+// t's slot | MAX b s: step s of block b's two max3 chains over S(t+1) | HCPY b, HSWAP b, HMAX b: the exchange with the partner
+// half as three entries (copy, v_permlane32_swap, max: half_max() of attn_common.h, its wait states covered by table work:
+// w64_issues_between) | BALLOT b: rescale test | M0 d / DMA d: LDS destination and request of DMA piece d (d < 4: K(t+3), else V(t+2)), one gap apart or more
 // (the number after each row: the gap's issue-cycles at the prices above, its fragment read and wait included)
 constexpr W64Op W64_P1[32][W64_SLOTS] = {
   {{W64_EXP, 0, 0}, {W64_EXP, 1, 0}},   //  0: 16
@@ -87,43 +91,42 @@ constexpr W64Op W64_P1[32][W64_SLOTS] = {
   {{W64_PACK, 0, 11}, {W64_ADD, 0, 23}, {W64_ADD, 1, 22}, {W64_EXP, 1, 23}},   // 31: 29
 };
 constexpr W64Op W64_P2[32][W64_SLOTS] = {
-  {{W64_M0, 0, 0}, {W64_PACK, 1, 11}, {W64_ADD, 1, 23}, {W64_EXP, 0, 24}, {W64_DMA, 0, 0}},   //  0: 25
-  {{W64_ADD, 0, 24}, {W64_EXP, 1, 24}},   //  1: 24
-  {{W64_M0, 1, 0}, {W64_ADD, 1, 24}, {W64_EXP, 0, 25}, {W64_DMA, 1, 0}},   //  2: 20
-  {{W64_PACK, 0, 12}, {W64_ADD, 0, 25}},   //  3: 21
-  {{W64_M0, 2, 0}, {W64_EXP, 1, 25}, {W64_DMA, 2, 0}},   //  4: 16
-  {{W64_PACK, 1, 12}, {W64_ADD, 1, 25}, {W64_EXP, 0, 26}},   //  5: 29
-  {{W64_M0, 3, 0}, {W64_ADD, 0, 26}, {W64_DMA, 3, 0}},   //  6: 12
-  {{W64_EXP, 1, 26}},   //  7: 20
-  {{W64_M0, 4, 0}, {W64_ADD, 1, 26}, {W64_MAX, 0, 0}, {W64_EXP, 0, 27}, {W64_DMA, 4, 0}},   //  8: 28
-  {{W64_PACK, 0, 13}, {W64_ADD, 0, 27}, {W64_MAX, 1, 0}},   //  9: 29
-  {{W64_M0, 5, 0}, {W64_MAX, 0, 1}, {W64_EXP, 1, 27}, {W64_DMA, 5, 0}},   // 10: 24
-  {{W64_PACK, 1, 13}, {W64_ADD, 1, 27}, {W64_MAX, 1, 1}, {W64_EXP, 0, 28}},   // 11: 37
-  {{W64_M0, 6, 0}, {W64_ADD, 0, 28}, {W64_MAX, 0, 2}, {W64_EXP, 1, 28}, {W64_DMA, 6, 0}},   // 12: 28
-  {{W64_ADD, 1, 28}, {W64_MAX, 1, 2}},   // 13: 24
-  {{W64_M0, 7, 0}, {W64_MAX, 0, 3}, {W64_EXP, 0, 29}, {W64_DMA, 7, 0}},   // 14: 24
-  {{W64_PACK, 0, 14}, {W64_ADD, 0, 29}, {W64_MAX, 1, 3}, {W64_EXP, 1, 29}},   // 15: 37
-  {{W64_PACK, 1, 14}, {W64_ADD, 1, 29}, {W64_MAX, 0, 4}},   // 16: 17
-  {{W64_MAX, 1, 4}, {W64_EXP, 0, 30}},   // 17: 28
-  {{W64_ADD, 0, 30}, {W64_MAX, 0, 5}, {W64_EXP, 1, 30}},   // 18: 20
-  {{W64_ADD, 1, 30}, {W64_MAX, 1, 5}},   // 19: 24
-  {{W64_MAX, 0, 6}, {W64_EXP, 0, 31}},   // 20: 16
-  {{W64_PACK, 0, 15}, {W64_ADD, 0, 31}, {W64_MAX, 1, 6}, {W64_EXP, 1, 31}},   // 21: 37
-  {{W64_PACK, 1, 15}, {W64_ADD, 1, 31}, {W64_LRUN, 0, 0}, {W64_MAX, 0, 7}},   // 22: 17
-  {{W64_LRUN, 1, 0}, {W64_MAX, 0, 8}, {W64_MAX, 1, 7}},   // 23: 24
-  {{W64_MAX, 1, 8}, {W64_HMAX, 0, 0}},   // 24: 24
-  {{W64_HMAX, 1, 0}},   // 25: 32
-  {{W64_BALLOT, 0, 0}},   // 26: 4
-  {{W64_BALLOT, 1, 0}},   // 27: 12
-  {},   // 28: 0
-  {},   // 29: 8
-  {},   // 30: 0
-  {},   // 31: 0
+  {{W64_EXP, 0, 24}},   //  0: 8
+  {{W64_ADD, 1, 23}, {W64_EXP, 1, 24}},   //  1: 24
+  {{W64_M0, 0, 0}, {W64_EXP, 0, 25}, {W64_DMA, 0, 0}},   //  2: 16
+  {{W64_ADD, 0, 24}, {W64_EXP, 1, 25}},   //  3: 24
+  {{W64_M0, 1, 0}, {W64_PACK, 1, 11}, {W64_ADD, 0, 25}, {W64_EXP, 0, 26}, {W64_DMA, 1, 0}},   //  4: 25
+  {{W64_ADD, 1, 24}, {W64_EXP, 1, 26}},   //  5: 24
+  {{W64_M0, 2, 0}, {W64_PACK, 0, 12}, {W64_EXP, 0, 27}, {W64_DMA, 2, 0}},   //  6: 21
+  {{W64_ADD, 1, 25}, {W64_EXP, 1, 27}},   //  7: 24
+  {{W64_M0, 3, 0}, {W64_ADD, 0, 26}, {W64_EXP, 0, 28}, {W64_DMA, 3, 0}},   //  8: 20
+  {{W64_PACK, 1, 12}, {W64_EXP, 1, 28}},   //  9: 25
+  {{W64_M0, 4, 0}, {W64_ADD, 0, 27}, {W64_DMA, 4, 0}},   // 10: 12
+  {{W64_ADD, 1, 26}, {W64_EXP, 0, 29}},   // 11: 24
+  {{W64_M0, 5, 0}, {W64_MAX, 0, 0}, {W64_DMA, 5, 0}},   // 12: 16
+  {{W64_PACK, 0, 13}, {W64_MAX, 0, 1}},   // 13: 25
+  {{W64_M0, 6, 0}, {W64_MAX, 0, 2}, {W64_DMA, 6, 0}},   // 14: 16
+  {{W64_PACK, 1, 13}, {W64_MAX, 0, 3}},   // 15: 25
+  {{W64_M0, 7, 0}, {W64_MAX, 0, 4}, {W64_DMA, 7, 0}},   // 16: 16
+  {{W64_ADD, 0, 28}, {W64_MAX, 0, 5}},   // 17: 24
+  {{W64_PACK, 0, 14}, {W64_ADD, 1, 27}, {W64_MAX, 0, 6}, {W64_EXP, 1, 29}},   // 18: 25
+  {{W64_MAX, 1, 0}, {W64_EXP, 0, 30}},   // 19: 28
+  {{W64_PACK, 1, 14}, {W64_MAX, 0, 7}, {W64_MAX, 1, 1}, {W64_EXP, 1, 30}},   // 20: 25
+  {{W64_MAX, 1, 2}, {W64_EXP, 0, 31}},   // 21: 28
+  {{W64_PACK, 0, 15}, {W64_MAX, 0, 8}, {W64_MAX, 1, 3}, {W64_EXP, 1, 31}},   // 22: 25
+  {{W64_PACK, 1, 15}, {W64_MAX, 1, 4}},   // 23: 25
+  {{W64_ADD, 0, 29}, {W64_ADD, 1, 28}, {W64_HCPY, 0, 0}, {W64_MAX, 1, 5}},   // 24: 20
+  {{W64_ADD, 0, 30}, {W64_MAX, 1, 6}},   // 25: 24
+  {{W64_ADD, 0, 31}, {W64_ADD, 1, 29}, {W64_MAX, 1, 7}, {W64_HSWAP, 0, 0}},   // 26: 16
+  {{W64_ADD, 1, 30}, {W64_MAX, 1, 8}, {W64_HMAX, 0, 0}},   // 27: 20
+  {{W64_LRUN, 0, 0}, {W64_ADD, 1, 31}, {W64_BALLOT, 0, 0}, {W64_HCPY, 1, 0}},   // 28: 16
+  {{W64_HSWAP, 1, 0}},   // 29: 12
+  {{W64_LRUN, 1, 0}, {W64_HMAX, 1, 0}},   // 30: 8
+  {{W64_BALLOT, 1, 0}},   // 31: 4
 };
 // issue-cycle price of a table entry, and of the fragment read at the head of an odd gap i and the wait at its end
 constexpr int w64_op_cost(W64Op o) {
-  return o.kind == W64_EXP ? 8 : o.kind == W64_PACK ? 5 : o.kind == W64_MAX ? (o.e < 7 ? 8 : 4) : o.kind == W64_HMAX ? 20 :
-         o.kind == W64_NONE ? 0 : 4;
+  return o.kind == W64_EXP ? 8 : o.kind == W64_PACK ? 5 : o.kind == W64_MAX ? (o.e < 7 ? 8 : 4) : o.kind == W64_NONE ? 0 : 4;
 }
 constexpr bool w64_read_first(int phase, int i) { return (i & 1) && (phase == 1 || i <= 29); }   // a fragment read opens the gap
 constexpr bool w64_wait_last(int phase, int i) { return (i & 1) && (phase == 1 || i <= 29); }    // a wait (phase 1, gap 31: the barrier's) closes it
@@ -150,8 +153,20 @@ constexpr bool w64_apart(int from, int to) {
   }
   return false;
 }
+// instructions issued between two table positions: table entries (a MAX step below 7 is two), the MFMAs, the fragment reads
+// (a V^T fragment counted once) and the waits.  v_permlane32_swap needs 2 wait states behind a VALU write of either operand.
+constexpr int w64_issues_between(int from, int to) {
+  int n = 0;
+  for (int at = from + 1; at < to; ++at) {
+    const int g = at / 8, s = at % 8, ph = g < 32 ? 1 : 2, i = g & 31;
+    if (s < W64_SLOTS) { const W64Op o = ph == 1 ? W64_P1[i][s] : W64_P2[i][s]; n += o.kind == W64_NONE ? 0 : (o.kind == W64_MAX && o.e < 7) ? 2 : 1; }
+    if (s == W64_SLOTS && w64_wait_last(ph, i)) ++n;
+    if (s == W64_SLOTS + 1) n += 1 + (w64_read_first(g + 1 < 32 ? 1 : 2, (g + 1) & 31) ? 1 : 0);   // the MFMA, the next gap's read
+  }
+  return n;
+}
 constexpr bool w64_table_complete() {   // every exp, add, pack exactly once; each after what it reads, and no s_nop in front of it
-  int exp_at[2][32] = {}, add_at[2][32] = {}, pack_at[2][16] = {}, max_at[2][9] = {}, n = 0;
+  int exp_at[2][32] = {}, add_at[2][32] = {}, pack_at[2][16] = {}, max_at[2][9] = {}, cpy_at[2] = {-1, -1}, swap_at[2] = {-1, -1}, hmax_at[2] = {-1, -1}, n = 0;
   for (int b = 0; b < 2; ++b) for (int m = 0; m < 9; ++m) max_at[b][m] = -1;
   for (int b = 0; b < 2; ++b) for (int e = 0; e < 32; ++e) { exp_at[b][e] = -1; add_at[b][e] = -1; }
   for (int b = 0; b < 2; ++b) for (int m = 0; m < 16; ++m) pack_at[b][m] = -1;
@@ -164,23 +179,30 @@ constexpr bool w64_table_complete() {   // every exp, add, pack exactly once; ea
       if (o.kind == W64_PACK) { if (exp_at[o.b][2 * o.e] < 0 || exp_at[o.b][2 * o.e + 1] < 0) return false; pack_at[o.b][o.e] = at; }
       if (o.kind == W64_LRUN && add_at[o.b][31] < 0) return false;
       if (o.kind == W64_MAX) { if (o.e > 0 && max_at[o.b][o.e - 1] < 0) return false; max_at[o.b][o.e] = at; }
-      if (o.kind == W64_HMAX && max_at[o.b][8] < 0) return false;
+      if (o.kind == W64_HCPY) { if (max_at[o.b][8] < 0 || cpy_at[o.b] >= 0) return false; cpy_at[o.b] = at; }
+      if (o.kind == W64_HSWAP) { if (cpy_at[o.b] < 0 || swap_at[o.b] >= 0) return false; swap_at[o.b] = at; }
+      if (o.kind == W64_HMAX) { if (swap_at[o.b] < 0 || hmax_at[o.b] >= 0) return false; hmax_at[o.b] = at; }
+      if (o.kind == W64_BALLOT && hmax_at[o.b] < 0) return false;
       if (o.kind == W64_ADD && !(w64_apart(exp_at[o.b][o.e], at) && w64_apart(o.e == 1 ? exp_at[o.b][0] : add_at[o.b][o.e - 1], at))) return false;
       if (o.kind == W64_PACK && !(w64_apart(exp_at[o.b][2 * o.e], at) && w64_apart(exp_at[o.b][2 * o.e + 1], at))) return false;
       if (o.kind == W64_LRUN && !w64_apart(add_at[o.b][31], at)) return false;
       if (o.kind == W64_MAX && o.e > 0 && !w64_apart(max_at[o.b][o.e - 1], at)) return false;
-      if (o.kind == W64_HMAX && !w64_apart(max_at[o.b][8], at)) return false;
+      if (o.kind == W64_HCPY && !w64_apart(max_at[o.b][8], at)) return false;
+      if (o.kind == W64_HSWAP && !(w64_apart(cpy_at[o.b], at) && w64_issues_between(cpy_at[o.b], at) >= 2 && w64_issues_between(max_at[o.b][8], at) >= 2)) return false;
+      if (o.kind == W64_HMAX && !w64_apart(swap_at[o.b], at)) return false;
     }
   for (int b = 0; b < 2; ++b)
     for (int m = 0; m < 16; ++m)   // pack of k-step m / 4 before PV MFMA 8 (m / 4) + b of phase 2 (MFMA j follows gap j - 1)
       if (pack_at[b][m] < 0 || pack_at[b][m] >= 8 * (32 + 8 * (m / 4) + b - 1) + W64_SLOTS) return false;
-  return n == 64;
+  return n == 64 && hmax_at[0] >= 0 && hmax_at[1] >= 0;
 }
 static_assert(w64_table_complete(), "attn_fwd_w64 gap table: an exp, add or pack is missing, doubled, out of order or right behind what it reads");
-static_assert(w64_table_ok(W64_P1, 1, 38, 2) && w64_table_ok(W64_P2, 2, 37, 1), "attn_fwd_w64 gap table over its budget");
+static_assert(w64_table_ok(W64_P1, 1, 38, 2) && w64_table_ok(W64_P2, 2, 28, 1), "attn_fwd_w64 gap table over its budget");
 
 // GUARD: wait states in front of the MFMA wherever hipcc may have placed a register copy of one of its operands right before the
-// statement (everywhere outside the straight-line steady loop, and the first MFMAs of every phase)
+// statement: everywhere outside the straight-line steady loop.  Inside it the first MFMAs of a phase carried the guard too (16
+// cycles each); the compiled loop has no operand copy there (a fragment read and its wait, or the barrier, stand in front of
+// them, and the rare rescale path ends in fence_o), and tests/test_isa_hazards.py fails on the build that places one.
 template <bool GUARD>
 __device__ __forceinline__ void mfma_s(f32x16& c, const bf16x8& a, const bf16x8& b) {   // score chain link: VGPR accumulator, B in AGPRs
   if constexpr (GUARD) asm volatile("s_nop 3\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(a), "a"(b));
@@ -440,7 +462,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
     float psum[2];        // row sums of P(t), one chain per query block in element order (attn_fwd_pipe.hip's order)
     float ex[2][32];      // P(t) in fp32
     unsigned pw[2][16];   // P(t) as packed bf16 pairs: word m = elements (2m, 2m + 1)
-    float mxa[2] = {0.f, 0.f}, mxb[2] = {0.f, 0.f}, mxh[2] = {0.f, 0.f};
+    float mxa[2] = {0.f, 0.f}, mxb[2] = {0.f, 0.f}, mxc[2] = {0.f, 0.f}, mxh[2] = {0.f, 0.f};
     bool need[2] = {false, false};
     // one entry of the gap table (every field folds to a constant once the phase loops are unrolled)
     auto run_op = [&](auto phase_c, auto gap_c, auto slot_c) __attribute__((always_inline)) {
@@ -465,7 +487,10 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
           mxb[b_] = gap_max3(mxa[b_], n[1][b_][15], n[1][b_][14]);
         }
       }
-      if constexpr (o.kind == W64_HMAX) mxh[b_] = half_max(mxb[b_]);
+      // half_max(mxb) in three statements: the copy the swap needs (two distinct registers), the swap, the maximum of the halves
+      if constexpr (o.kind == W64_HCPY) asm volatile("v_mov_b32 %0, %1" : "=v"(mxc[b_]) : "v"(mxb[b_]));
+      if constexpr (o.kind == W64_HSWAP) asm volatile("v_permlane32_swap_b32 %0, %1" : "+v"(mxb[b_]), "+v"(mxc[b_]));
+      if constexpr (o.kind == W64_HMAX) asm volatile("v_max_f32 %0, %1, %2" : "=v"(mxh[b_]) : "v"(mxb[b_]), "v"(mxc[b_]));
       if constexpr (o.kind == W64_BALLOT) need[b_] = __builtin_amdgcn_ballot_w64(mxh[b_] > ATTN_RESCALE_THR) != 0ull;
       // the eight LDS-DMA requests of this iteration: K(t+3) into K(t+1)'s buffer, V(t+2) into V(t-1)'s slot (both free since
       // the barrier); waited for at the next barrier, a whole iteration away
@@ -484,13 +509,8 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
       constexpr int i = decltype(i_c)::value;
       const int f = i >> 1, nb = i & 1;               // fragment f = (k-step f >> 1, key block f & 1) feeds MFMAs 2 f, 2 f + 1
       if (i == 0) kfr[PD % RING] = read_k(kb, PD);
-      if (f < 2) {
-        if (STEADY && i >= 1) mfma_s_first<false>(n[f & 1][nb], minit[nb], kfr[f % RING], qf[nb][0]);
-        else mfma_s_first<true>(n[f & 1][nb], minit[nb], kfr[f % RING], qf[nb][0]);
-      } else {
-        if (STEADY) mfma_s<false>(n[f & 1][nb], kfr[f % RING], qf[nb][f >> 1]);
-        else mfma_s<true>(n[f & 1][nb], kfr[f % RING], qf[nb][f >> 1]);
-      }
+      if (f < 2) mfma_s_first<!STEADY>(n[f & 1][nb], minit[nb], kfr[f % RING], qf[nb][0]);
+      else mfma_s<!STEADY>(n[f & 1][nb], kfr[f % RING], qf[nb][f >> 1]);
       SCHED_FENCE();
       if (nb == 1) {   // the read of fragment f + 1 + PD, into the ring slot MFMA i was the last to read (see above the table)
         const int fn = f + 1;
@@ -515,8 +535,7 @@ __global__ __launch_bounds__(256) void attn_fwd_w64_kernel(const AttnFwdW64Param
       const int g = j >> 1, nb = j & 1;               // fragment g = (k-step g >> 2, dim block g & 3) feeds MFMAs 2 g, 2 g + 1
       const int kk = g >> 2;
       const u32x4 pbw = {pw[nb][4 * kk], pw[nb][4 * kk + 1], pw[nb][4 * kk + 2], pw[nb][4 * kk + 3]};
-      if (STEADY && j >= 2) mfma_o<false>(oacc[nb][g & 3], vfr[g % RING], __builtin_bit_cast(bf16x8, pbw));
-      else mfma_o<true>(oacc[nb][g & 3], vfr[g % RING], __builtin_bit_cast(bf16x8, pbw));
+      mfma_o<!STEADY>(oacc[nb][g & 3], vfr[g % RING], __builtin_bit_cast(bf16x8, pbw));
       SCHED_FENCE();
       if (nb == 1 && g + 1 < 16) {   // (V fragment PD was read behind the last score MFMA)
         const int gn = g + 1;
