@@ -1,5 +1,5 @@
 // What the master-weight optimizer kernels share (optim_master.hip, optim_moments8.hip, optim_accum.hip, optim_anchor.hip,
-// optim_ema.hip), and the default kernels' fp32 AdamW (optim.hip):
+// optim_ema.hip, optim_trust.hip), and the default kernels' fp32 AdamW (optim.hip):
 // the (bf16 word, int16 low word) <-> fp32 master format, a thread's eight fp32 values, and the per-element op sequences of SGD
 // and AdamW (their scalars are optim_common.h's).  All of them are built with -ffp-contract=off.
 #pragma once
@@ -100,4 +100,12 @@ __device__ __forceinline__ float master_ema_elem(float w, float e, float b) {
   const float d = w - e;
   const float t = b * d;
   return w - t;
+}
+
+// ---- the projection onto the ball around the base weights (include/lcv_hip_trust.h) ----
+// the drift w - w0 scaled by c and put back on w0: c = 1 gives w back up to the rounding of (w - w0) + w0
+__device__ __forceinline__ float master_trust_elem(float w, float w0, float c) {
+  const float d = w - w0;
+  const float u = c * d;
+  return w0 + u;
 }

@@ -182,6 +182,15 @@ _SIGNATURES_DORA = {
 }
 LCV_DORA_NORM_KTILE, LCV_DORA_NORM_ROWS, LCV_DORA_SLAB, LCV_DORA_SLAB_QUARTER = 512, 16, 64, 16
 
+# include/lcv_hip_trust.h (a header of its own: the trust-region cap on the drift from the base weights): sumsq takes (tensors, low,
+# anchor, n_tensors, total_chunks, int param_f32, partials, partials_bytes, per_tensor, out), project (tensors, low, anchor, n_tensors,
+# total_chunks, int param_f32, int scope, sumsq, per_tensor, double r2_or_R2, trace_slot); both return int
+_SIGNATURES_TRUST = {
+    "lcv_trust_sumsq": [P, P, P, I64, I64, I, P, I64, P, P, P],
+    "lcv_trust_project": [P, P, P, I64, I64, I, I, P, P, F64, P, P],
+}
+LCV_TRUST_GLOBAL, LCV_TRUST_TENSOR = 0, 1
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -244,7 +253,7 @@ def load():
                        + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())
                        + list(_SIGNATURES_STEPCACHE.items()) + list(_SIGNATURES_SOLVER.items())
                        + list(_SIGNATURES_CFGREUSE.items()) + list(_SIGNATURES_SR.items()) + list(_SIGNATURES_APG.items())
-                       + list(_SIGNATURES_DORA.items())):
+                       + list(_SIGNATURES_DORA.items()) + list(_SIGNATURES_TRUST.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

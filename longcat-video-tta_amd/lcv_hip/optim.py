@@ -64,6 +64,12 @@ class FusedAdamWClip:
     takes one (seed, offset) pair from the device's default generator (`ops.draw_philox_offset`, the generator moves on by 4),
     so the steps follow `torch.manual_seed`.
 
+    `enable_max_drift(radius_rms, scope)` (bf16 parameters with `master_weights=True`, or fp32 parameters; once, before the first
+    step) keeps the parameters inside a ball around their base values (include/lcv_hip_trust.h): the module-level
+    `project_max_drift([...])`, called after the optimizers' `step()`s, measures |theta - theta0| in a fixed order and scales
+    the drift back onto the ball where it has left it, on the device, with no host sync; a weight average then takes the
+    projected masters.
+
     A subclass supplies its `param_groups` entry (through `_init`), its moment storage (`_init_moments`), its hyper-parameter
     tuple (`_hyper`) and its `STEPS`."""
     CHUNK = 2048
@@ -72,6 +78,7 @@ class FusedAdamWClip:
     weight_ema = None        # the beta of enable_weight_ema(), or None: no average is kept
     ema_in_params = False    # True between an ema_swap() and the next: the parameters hold the average
     _ema = ()
+    max_drift = None         # the RMS radius of enable_max_drift(), or None: no ball is kept
 
     # The step entry points as the headers list them (lcv_hip.h, lcv_hip_master.h, lcv_hip_accum.h, lcv_hip_moments8.h,
     # lcv_hip_anchor.h).  (anchor, moments_8bit, grad_accum > 1, master_weights) -> the entry point, the pointer tables that
@@ -179,16 +186,18 @@ class FusedAdamWClip:
                 raise _lib.LcvError(f"{name}: stochastic_rounding=True cannot be combined with {what} (it exists for the "
                                     "master-weight form only)")
 
-    def _check_anchor(self, anchor):
-        """A list of base words that fits `params`: contiguous bf16 GPU tensors of the parameters' shapes."""
+    def _check_anchor(self, anchor, dtype=BF16):
+        """A list of base words that fits `params`: contiguous bf16 GPU tensors of the parameters' shapes (fp32 ones for the
+        ball of fp32 parameters, enable_max_drift)."""
         name = type(self).__name__
         anchor = [a for a in anchor]
         if len(anchor) != len(self.params):
             raise _lib.LcvError(f"{name}: anchor has {len(anchor)} tensors for {len(self.params)} parameters")
         for a, p in zip(anchor, self.params):
-            if a.dtype != BF16 or not a.is_cuda or not a.is_contiguous() or a.shape != p.shape or a.device != p.device:
-                raise _lib.LcvError(f"{name}: every anchor must be a contiguous bf16 tensor on the parameter's GPU with its "
-                                    f"shape; got {a.dtype} {tuple(a.shape)} on {a.device} for {tuple(p.shape)}")
+            if a.dtype != dtype or not a.is_cuda or not a.is_contiguous() or a.shape != p.shape or a.device != p.device:
+                raise _lib.LcvError(f"{name}: every anchor must be a contiguous {'bf16' if dtype == BF16 else 'fp32'} tensor on the "
+                                    f"parameter's GPU with its shape; got {a.dtype} {tuple(a.shape)} on {a.device} for "
+                                    f"{tuple(p.shape)}")
         return anchor
 
     def _init_anchor(self, anchor) -> None:
@@ -330,6 +339,99 @@ class FusedAdamWClip:
         ops.call("lcv_master_ema_swap", *self._ema_table(), _stream())
         self.ema_in_params = not self.ema_in_params
         ops.PARAM_EPOCH += 1         # the parameters changed under cached copies of them, as after a step
+
+    # ------------------------------------------------------------------------------------------------ the trust region
+    MAX_DRIFT_SCOPES = ("global", "tensor")   # LCV_TRUST_GLOBAL, LCV_TRUST_TENSOR
+
+    def enable_max_drift(self, radius_rms: float, scope: str = "global", anchor=None, trace_len: int = 4096) -> None:
+        """Keep the parameters inside a ball around their base values (include/lcv_hip_trust.h): after every step,
+        `project_max_drift([...])` scales the drift theta - theta0 back onto the ball when it has left it.  `radius_rms` > 0 is
+        the radius in RMS per element (`inf`: nothing is ever written, the trace is still recorded); `scope` "global" is one ball
+        over every optimizer handed to `project_max_drift` together, "tensor" one ball per parameter tensor.  For bf16
+        parameters with `master_weights=True`, or for fp32 parameters.  `anchor`: the base values (bf16 words for bf16
+        parameters, fp32 values for fp32 ones, held by reference); None reuses the optimizer's own `anchor=`, else means zeros
+        for fp32 parameters and is refused for bf16 ones.  Once, before the first `step()`.  Allocates one float per chunk and
+        per tensor and `trace_len` pairs of floats for the per-step trace; steps past `trace_len` are projected and not
+        recorded."""
+        name = type(self).__name__
+        if self.max_drift is not None:
+            raise _lib.LcvError(f"{name}: enable_max_drift() was already called")
+        radius = float(radius_rms)
+        if not radius > 0.0:                 # a NaN fails too
+            raise _lib.LcvError(f"{name}: the radius of enable_max_drift() must be > 0 (RMS per element, inf allowed), got {radius}")
+        if scope not in self.MAX_DRIFT_SCOPES:
+            raise _lib.LcvError(f"{name}: the scope of enable_max_drift() is 'global' or 'tensor', got {scope!r}")
+        if self.stochastic_rounding:
+            raise _lib.LcvError(f"{name}: enable_max_drift() cannot be combined with stochastic_rounding=True (the ball needs "
+                                "master weights)")
+        if not self.f32 and not self.master_weights:
+            raise _lib.LcvError(f"{name}: enable_max_drift() on bf16 parameters needs master_weights=True (a contraction "
+                                "(1 - c) * |d| below half a bf16 ulp rounds back to the same word, so the bound would not hold)")
+        if self.step_count:
+            raise _lib.LcvError(f"{name}: enable_max_drift() comes before the first step(), not after {self.step_count}")
+        if int(trace_len) < 1:
+            raise _lib.LcvError(f"{name}: trace_len must be at least 1, got {trace_len}")
+        if any(not p.is_cuda or not p.is_contiguous() for p in self.params):
+            raise _lib.LcvError(f"{name}: enable_max_drift() needs contiguous parameters on the GPU (no CPU path exists)")
+        if anchor is not None:
+            anchor = self._check_anchor(anchor, F32 if self.f32 else BF16)
+        elif self._anchor:
+            anchor = self._anchor
+        elif not self.f32:
+            raise _lib.LcvError(f"{name}: enable_max_drift() on bf16 parameters needs an anchor (the optimizer holds none)")
+        sel = self._nonempty()
+        if not sel:
+            raise _lib.LcvError(f"{name}: a ball over no elements")
+        dev = self.params[0].device
+        chunks = sum((self.params[i].numel() + self.CHUNK - 1) // self.CHUNK for i in sel)
+        self._md_anchor = anchor             # a list, or None: every base value is zero
+        self._md_scope = scope
+        self._md_numel = sum(self.params[i].numel() for i in sel)
+        self._md_part = torch.empty((chunks,), dtype=F32, device=dev)
+        self._md_per = torch.empty((len(sel),), dtype=F32, device=dev)
+        self._md_out = torch.zeros(2, dtype=F32, device=dev)
+        self._md_trace = torch.zeros((int(trace_len), 2), dtype=F32, device=dev)
+        self._md_steps = 0
+        self._md_stepped = False             # a step() since the last projection: its weight average is due an update
+        self.max_drift = radius
+
+    def _md_needs(self, what: str) -> None:
+        if self.max_drift is None:
+            raise _lib.LcvError(f"{type(self).__name__}: {what} needs enable_max_drift()")
+
+    def _trust_args(self):
+        """The leading arguments of the two trust entry points: the descriptor table over ALL non-empty parameters (with or
+        without a gradient, as drift_norm's), the low-word and base pointers beside it, the counts and param_f32."""
+        sides = {k: ts for k, ts in (("low", self._low), ("anchor", self._md_anchor)) if ts}
+        key = tuple(t.data_ptr() for ts in (self.params, *sides.values()) for t in ts)
+        t = self._cached("trust", key, lambda: self._build_table(self._nonempty(), **sides))
+        return _ptr(t.desc), _ptr(t.sides.get("low")), _ptr(t.sides.get("anchor")), t.n, t.chunks, 1 if self.f32 else 0
+
+    def drift_sumsq(self) -> torch.Tensor:
+        """|theta - theta0|^2 over ALL parameters of this optimizer as a 0-dim fp32 device tensor, no host sync (lcv_trust_sumsq,
+        fixed order); the per-tensor sums are left in `_md_per`.  The tensor is the optimizer's own buffer: the next call
+        overwrites it."""
+        self._md_needs("drift_sumsq()")
+        ops.call("lcv_trust_sumsq", *self._trust_args(), _ptr(self._md_part), self._md_part.numel() * 4, _ptr(self._md_per),
+                 _ptr(self._md_out), _stream())
+        return self._md_out[0]
+
+    def _trust_project(self, sumsq: torch.Tensor, numel: int) -> None:
+        """Launch this optimizer's projection against the total `sumsq` (a device tensor) of a ball of `numel` elements, and
+        record the step in the trace while it has room."""
+        tensor = self._md_scope == "tensor"
+        rr = self.max_drift * self.max_drift * (1.0 if tensor else float(numel))      # R * R [* N], formed in double
+        slot = self._md_trace[self._md_steps] if self._md_steps < self._md_trace.shape[0] else None
+        ops.call("lcv_trust_project", *self._trust_args(), _lib.LCV_TRUST_TENSOR if tensor else _lib.LCV_TRUST_GLOBAL, _ptr(sumsq),
+                 _ptr(self._md_per), rr, _ptr(slot), _stream())
+        self._md_steps += 1
+
+    def max_drift_trace(self) -> torch.Tensor:
+        """The trace so far as a [steps, 2] fp32 CPU tensor, read in one copy: per projected step the total |theta - theta0|^2
+        before the projection (of the whole ball in global scope, of this optimizer in tensor scope) and the smallest
+        coefficient applied (1.0: nothing was projected)."""
+        self._md_needs("max_drift_trace()")
+        return self._md_trace[:min(self._md_steps, self._md_trace.shape[0])].cpu()
 
     def _init_accum(self, grad_accum: int) -> None:
         """Zeroed fp32 accumulators (+4 B / parameter) when `grad_accum` > 1; nothing at 1."""
@@ -508,7 +610,12 @@ class FusedAdamWClip:
                      *((1 if self.f32 else 0,) if param_f32 else ()), coef,
                      *self._hyper(), *((1 if self.grad_accum > 1 else 0,) if grad_f32 else ()), _stream())
         self._have_coef = False
-        if self.weight_ema is not None:  # the average follows the masters this step left (include/lcv_hip_ema.h)
+        # the average follows the masters this step left (include/lcv_hip_ema.h); under enable_max_drift() those are the
+        # projected ones, so the update is left to the project_max_drift() that must follow: it runs it after its projection,
+        # for the optimizers that stepped
+        if self.max_drift is not None:
+            self._md_stepped = True
+        elif self.weight_ema is not None:
             self._ema_update()
         ops.PARAM_EPOCH += 1
 
@@ -547,3 +654,72 @@ class FusedSGDClip(FusedAdamWClip):
 
     def state_bytes(self) -> int:
         return 0
+
+
+# ===================================================================== the trust region over several optimizers
+def _max_drift_group(opts, training: bool = False):
+    """The optimizers of one ball; `training`: refuse while one of them holds its weight average in the parameters (measuring
+    the drift of the average is fine, projecting it is not)."""
+    opts = list(opts)
+    if not opts:
+        raise _lib.LcvError("project_max_drift: no optimizer")
+    for o in opts:
+        o._md_needs("project_max_drift()")
+        if training:
+            o._ema_guard("project_max_drift()")
+    if len({(o.max_drift, o._md_scope) for o in opts}) != 1:
+        raise _lib.LcvError("project_max_drift: every optimizer of one ball takes the same radius and scope")
+    return opts
+
+
+def project_max_drift(opts) -> None:
+    """What follows the optimizers' `step()`s under enable_max_drift() (include/lcv_hip_trust.h), with no host sync: every
+    optimizer's lcv_trust_sumsq; in global scope the optimizers' totals added on the device in the optimizers' order in fp32 into
+    the ball's total, over N = all their elements; every optimizer's lcv_trust_project against it (in tensor scope against its
+    own per-tensor sums); the trace slot moves on; then the weight averages of the optimizers that stepped since the last call
+    take the projected masters (`_ema_update`, which their `step()` left to this call: with both features on, a `step()` that
+    is not followed by this call leaves the average one update behind) and `ops.PARAM_EPOCH` is bumped."""
+    opts = _max_drift_group(opts, training=True)
+    totals = [o.drift_sumsq() for o in opts]
+    numel = sum(o._md_numel for o in opts)
+    joint = totals[0]
+    if len(opts) > 1 and opts[0]._md_scope == "global":
+        joint = totals[0].clone()
+        for t in totals[1:]:
+            joint += t
+    for o, own in zip(opts, totals):
+        if o._md_scope == "global":
+            o._trust_project(joint, numel)
+        else:
+            o._trust_project(own, o._md_numel)
+    for o in opts:                   # an optimizer that was not stepped (no gradient) keeps its average, as without the ball
+        if o.weight_ema is not None and o._md_stepped:
+            o._ema_update()
+        o._md_stepped = False
+    ops.PARAM_EPOCH += 1
+
+
+def max_drift_norm(opts) -> float:
+    """|theta - theta0| over every optimizer of `opts` now (one lcv_trust_sumsq each, then one read per optimizer): the
+    `drift_norm` of a result row."""
+    opts = _max_drift_group(opts)
+    return float(sum(float(o.drift_sumsq().item()) for o in opts)) ** 0.5
+
+
+def max_drift_stats(opts) -> dict:
+    """The `max_drift` entry of a result row from the optimizers' traces (one copy each, after the loop): radius, scope, the
+    number of recorded steps, how many of them projected (a coefficient below 1 somewhere), the first such step (counted from 1,
+    None when there is none), the smallest coefficient, and per step the drift in RMS per element before the projection."""
+    opts = _max_drift_group(opts)
+    traces = [o.max_drift_trace().double() for o in opts]
+    steps = min(t.shape[0] for t in traces)
+    numel = sum(o._md_numel for o in opts)
+    if opts[0]._md_scope == "global":       # every optimizer recorded the ball's total
+        total = traces[0][:steps, 0]
+    else:
+        total = sum(t[:steps, 0] for t in traces)
+    coef = torch.stack([t[:steps, 1] for t in traces]).min(0).values if steps else torch.ones(0, dtype=torch.float64)
+    hit = (coef < 1.0).nonzero().flatten().tolist()
+    return {"radius": opts[0].max_drift, "scope": opts[0]._md_scope, "steps": steps, "projections": len(hit),
+            "first_projected_step": hit[0] + 1 if hit else None, "min_coef": float(coef.min().item()) if steps else 1.0,
+            "drift_rms_trace": (total / numel).sqrt().tolist()}

@@ -65,7 +65,7 @@ def full_method(args) -> R.TTAMethod:
                              "weight_decay": args.weight_decay, "max_grad_norm": args.max_grad_norm, "optimizer": args.optimizer,
                              "master_weights": args.master_weights, "adam_8bit": args.adam_8bit,
                              "grad_accum": args.grad_accum, **({"decay_to_base": True} if args.decay_to_base else {}),
-                             **C.weight_ema_record(args), **C.stochastic_rounding_record(args),
+                             **C.weight_ema_record(args), **C.stochastic_rounding_record(args), **C.max_drift_record(args),
                              "total_params": job["total_params"], "trainable_params": trainable_params},
                 "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                                "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
@@ -86,12 +86,13 @@ def full_method(args) -> R.TTAMethod:
                                              max_grad_norm=args.max_grad_norm, device=device, dtype=torch.bfloat16,
                                              early_stopper=es, optimizer_type=args.optimizer, train_latents_variants=variants,
                                              # the anchors are the reset's base copy: nothing more is allocated
-                                             **({"base_state": job["base_state"]} if args.decay_to_base else {}),
+                                             **({"base_state": job["base_state"]} if args.decay_to_base or args.max_drift is not None
+                                                else {}),
                                              **C.optimizer_kwargs(args))
 
     def row_extra(tr, variants, blob):
         return {"num_train_steps": len(tr["losses"]), **({"drift_norm": tr["drift_norm"]} if args.decay_to_base else {}),
-                **C.stochastic_rounding_record(args)}
+                **C.stochastic_rounding_record(args), **C.max_drift_result(tr)}
 
     def summary_extra(merged, ok):
         return {"learning_rate": args.learning_rate, "num_steps": args.num_steps, "batch_videos": args.batch_videos,

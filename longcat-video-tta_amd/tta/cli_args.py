@@ -161,7 +161,7 @@ def optimizer_kwargs(args) -> dict:
     kw = {"master_weights": args.master_weights, "moments_8bit": args.adam_8bit, "grad_accum": args.grad_accum}
     if hasattr(args, "decay_to_base"):
         kw["decay_to_base"] = args.decay_to_base
-    return {**kw, **weight_ema_kwargs(args), **stochastic_rounding_record(args)}
+    return {**kw, **weight_ema_kwargs(args), **stochastic_rounding_record(args), **max_drift_kwargs(args)}
 
 
 def weight_ema_kwargs(args) -> dict:
@@ -219,6 +219,7 @@ def parse_with_step_cache(parser, argv=None, parse=None):
         parser.error("--step-cache-max-skip needs --step-cache THRESH")
     check_cfg_reuse_args(parser, args)
     check_apg_args(parser, args)
+    check_max_drift_args(parser, args)
     return args
 
 
@@ -394,6 +395,58 @@ def apg_result(blob) -> dict:
     """The per-video `apg` entry (`ProjectedGuidance.stats()`, left in the blob by generate_continuation); nothing without the
     flag."""
     return {"apg": blob["_apg"]} if "_apg" in blob else {}
+
+
+def add_max_drift_args(parser):
+    parser.add_argument("--max-drift", type=float, default=None, metavar="R",
+                        help="trust-region cap on how far the adapted parameters travel (include/lcv_hip_trust.h): after every "
+                             "optimizer step, if the drift from the values the video's adaptation started at exceeds R (RMS per "
+                             "trained element, so one value serves 512 parameters and 13.6 G), it is scaled back onto that ball, "
+                             "on the device; bf16 parameters need --master-weights; inf changes nothing and records the drift "
+                             "trace (calibration); no radius is recommended")
+    parser.add_argument("--max-drift-scope", choices=["global", "tensor"], default=None,
+                        help="with --max-drift: one ball over all trained elements (global, the default) or one per parameter "
+                             "tensor, so that no layer can spend the whole budget (tensor)")
+
+
+def check_max_drift_args(parser, args) -> None:
+    """The refusals of --max-drift as the parser's own one-line error (exit status 2).  Called from `parse_with_step_cache`,
+    which every runner parses through; a parser without the flags is left alone."""
+    radius = getattr(args, "max_drift", None)
+    if radius is None:
+        if getattr(args, "max_drift_scope", None) is not None:
+            parser.error("--max-drift-scope needs --max-drift R")
+        return
+    if not radius > 0.0:                                                  # a NaN fails too
+        parser.error(f"--max-drift R must be > 0 (inf is allowed), got {radius}")
+    if getattr(args, "stochastic_rounding", False):
+        parser.error("--max-drift cannot be combined with --stochastic-rounding (the ball needs --master-weights: a contraction "
+                     "below half a bf16 ulp rounds back to the same word)")
+    if getattr(args, "lora_dora", False):
+        parser.error("--max-drift cannot be combined with --lora-dora (its bf16 adapters train without --master-weights)")
+    if hasattr(args, "master_weights") and not args.master_weights:       # the runners that train bf16 parameters
+        parser.error("--max-drift needs --master-weights (a contraction (1 - c) * |d| below half a bf16 ulp rounds back to the "
+                     "same word, so the bound would not hold for plain bf16 parameters)")
+
+
+def max_drift_kwargs(args) -> dict:
+    """The loop functions' keywords for --max-drift; nothing when the flag is absent (then nothing is imported, allocated or
+    launched)."""
+    if getattr(args, "max_drift", None) is None:
+        return {}
+    return {"max_drift": args.max_drift, "max_drift_scope": args.max_drift_scope or "global"}
+
+
+def max_drift_record(args) -> dict:
+    """What config.json (`training`) and the flat summary.json of the runners without one record of --max-drift; nothing when
+    the flag is absent."""
+    return max_drift_kwargs(args)
+
+
+def max_drift_result(loop) -> dict:
+    """The per-video `drift_norm` and `max_drift` entry ({radius, scope, steps, projections, first_projected_step, min_coef,
+    drift_rms_trace}) the loop left in its result; nothing without the flag."""
+    return {"drift_norm": loop["drift_norm"], "max_drift": loop["max_drift"]} if "max_drift" in loop else {}
 
 
 def normalize_tta_frame_args(args):

@@ -21,8 +21,8 @@ import torch.nn as nn
 from lcv_hip.ops import FusedAdamWClip, FusedSGDClip
 
 from .early_stopping import AnchoredEarlyStopper
-from .inner_loop import (_OneVideo, _RoundRobin, _fm_loss, _single_optimizer_step, refuse_stochastic_rounding_under_sp,
-                         run_adaptation)
+from .inner_loop import (_OneVideo, _RoundRobin, _fm_loss, _single_optimizer_step, max_drift_hook,
+                         refuse_stochastic_rounding_under_sp, run_adaptation)
 
 
 def snapshot_base_state(dit: nn.Module) -> Dict[str, torch.Tensor]:
@@ -90,12 +90,14 @@ def _anchors(dit: nn.Module, base_state: Optional[Dict[str, torch.Tensor]]) -> L
 
 def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper, optimizer_type,
          *, master_weights, moments_8bit, grad_accum, decay_to_base, base_state, weight_ema, ema_warmup,
-         stochastic_rounding=False):
+         stochastic_rounding=False, max_drift=None, max_drift_scope="global"):
     params = _trainable(dit)
     refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
     # `decay_to_base`: the weight decay pulls toward the base words (include/lcv_hip_anchor.h), which are the caller's
     # `base_state` entries or, without one, +2 B / parameter of clones; a `base_state` alone only measures the drift
-    want_drift = bool(decay_to_base) or base_state is not None
+    # `max_drift`: after every step the weights are projected onto a ball of that RMS radius around the same base words
+    # (include/lcv_hip_trust.h); with the per-video `base_state` nothing more is allocated
+    want_drift = bool(decay_to_base) or base_state is not None or max_drift is not None
     anchor = _anchors(dit, base_state) if want_drift else None
     # made per call, so per video: the per-video reset writes the bf16 words, and the low words of `master_weights`
     # (+2 B / parameter; AdamW: +8 B of fp32 moments, or +2.016 B of 8-bit ones under `moments_8bit`) start at zero next to them;
@@ -109,10 +111,13 @@ def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, de
                               anchor=anchor if decay_to_base else None)
     if weight_ema is not None:                 # +4 B / parameter of fp32 average (54 GB for the whole model: a memory decision);
         opt.enable_weight_ema(weight_ema, ema_warmup)   # run_adaptation scores it and leaves it in the parameters
+    ball = max_drift_hook([opt], max_drift, max_drift_scope, num_steps, [anchor])
     out = run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
-                         num_steps, lr, warmup_steps, early_stopper, grad_accum=grad_accum)
+                         num_steps, lr, warmup_steps, early_stopper, after_step=ball, grad_accum=grad_accum)
     opt.zero_grad(set_to_none=True)            # the gradients of 13.6 B parameters are dead weight during generation
-    if want_drift:                             # |theta - theta0| over the trainable parameters, read once per video (after the
+    if ball is not None:                       # |theta - theta0| from the ball's own fixed-order sum (lcv_trust_sumsq) and the
+        ball.finish(out)                       # trace's summary: one pass, not a second one through lcv_master_drift_sumsq
+    elif want_drift:                           # |theta - theta0| over the trainable parameters, read once per video (after the
         # final swap of a weight average: the drift of the weights that generate)
         out["drift_norm"] = float(opt.drift_norm(anchor).item())
     return out
@@ -124,7 +129,8 @@ def finetune_full_on_conditioning(dit: nn.Module, cond_latents: torch.Tensor, tr
                                   max_grad_norm: float = 1.0, device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                                   early_stopper: Optional[AnchoredEarlyStopper] = None,
                                   train_latents_variants: Optional[List[Dict]] = None, optimizer_type: str = "sgd",
-                                  stochastic_rounding: bool = False,
+                                  stochastic_rounding: bool = False, max_drift: Optional[float] = None,
+                                  max_drift_scope: str = "global",
                                   *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                                   decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
                                   grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
@@ -132,12 +138,13 @@ def finetune_full_on_conditioning(dit: nn.Module, cond_latents: torch.Tensor, tr
     return _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper,
                 optimizer_type, master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
                 decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup,
-                stochastic_rounding=stochastic_rounding)
+                stochastic_rounding=stochastic_rounding, max_drift=max_drift, max_drift_scope=max_drift_scope)
 
 
 def finetune_full_batch(dit: nn.Module, batch_data: List[Dict], num_steps: int = 10, lr: float = 1e-5, warmup_steps: int = 2,
                         weight_decay: float = 0.01, max_grad_norm: float = 1.0, device: str = "cuda",
                         dtype: torch.dtype = torch.bfloat16, optimizer_type: str = "sgd", stochastic_rounding: bool = False,
+                        max_drift: Optional[float] = None, max_drift_scope: str = "global",
                         *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                         decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
@@ -145,4 +152,4 @@ def finetune_full_batch(dit: nn.Module, batch_data: List[Dict], num_steps: int =
     return _run(dit, _RoundRobin(batch_data, device), num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype,
                 None, optimizer_type, master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
                 decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup,
-                stochastic_rounding=stochastic_rounding)
+                stochastic_rounding=stochastic_rounding, max_drift=max_drift, max_drift_scope=max_drift_scope)

@@ -78,13 +78,17 @@ def _variant_pool(train_latents, variants) -> List[torch.Tensor]:
 def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers: Sequence, loss_at: Callable[[int], torch.Tensor],
                    clip_and_step: Callable[[], None], num_steps: int, lr: float = 0.0, warmup_steps: int = 0,
                    early_stopper: Optional[AnchoredEarlyStopper] = None, grad_sync: Optional[Callable[[], None]] = None,
-                   finish_eval: bool = True, grad_accum: int = 1) -> Dict:
+                   after_step: Optional[Callable[[], None]] = None, finish_eval: bool = True, grad_accum: int = 1) -> Dict:
     """`loss_at(step)` returns the differentiable loss of that step; `clip_and_step()` owns clipping + the update.
 
     `grad_accum=N` with N > 1 puts N micro-steps behind every optimizer step: `loss_at(step * N + k)`, backward, `grad_sync()`
     and `opt.accumulate()` (fp32 accumulators, include/lcv_hip_accum.h) for k = 0 .. N-1, then `clip_and_step()`.  The step's
     logged loss is the micro losses added in order in fp32, times fp32(1/N), on the device.  `num_steps`, the warm-up and the
     early stopper's `check_every` count optimizer steps.
+
+    `after_step()` runs right after every `clip_and_step()` - after the optimizer step only, never after a micro-step - and
+    before the stopper looks at the parameters: the projection of `--max-drift` (`_MaxDrift`, include/lcv_hip_trust.h), so that
+    what the stopper scores and snapshots are projected iterates.
 
     Optimizers that keep a weight average (`opt.weight_ema is not None`, include/lcv_hip_ema.h) have it swapped into the
     parameters around every due check of the stopper - so the average is what is scored and what `keeper.capture` snapshots,
@@ -118,6 +122,8 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
             if grad_sync is not None:
                 grad_sync()
         clip_and_step()
+        if after_step is not None:
+            after_step()
         log.push(loss)
         del loss
         if early_stopper is None:
@@ -154,6 +160,34 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
         module.eval()
     return {"losses": log.to_list(), "train_time": elapsed, "es_check_time": es_seconds,
             "early_stopping_info": early_stopper.state if early_stopper is not None else None}
+
+
+class _MaxDrift:
+    """`--max-drift R` for one adaptation (include/lcv_hip_trust.h): puts the ball on every optimizer of the loop (one global
+    ball over all of them, or one per tensor), is the loop's `after_step`, and afterwards adds `drift_norm` and the `max_drift`
+    entry (the trace's summary) to the loop's result.  `anchors`: per optimizer its base values, or None for "its own anchor,
+    else zeros" (fp32 vectors that start at zero)."""
+
+    def __init__(self, opts, radius: float, scope: str, num_steps: int, anchors=None):
+        from lcv_hip import optim
+        self._optim, self.opts = optim, list(opts)
+        for i, opt in enumerate(self.opts):
+            opt.enable_max_drift(radius, scope, anchor=None if anchors is None else anchors[i], trace_len=max(int(num_steps), 1))
+
+    def __call__(self) -> None:
+        self._optim.project_max_drift(self.opts)
+
+    def finish(self, out: Dict) -> Dict:
+        """After the loop (after the stopper's restore and the final swap of a weight average): the drift of the weights that
+        generate, and the trace in one copy per optimizer."""
+        out["drift_norm"] = self._optim.max_drift_norm(self.opts)
+        out["max_drift"] = self._optim.max_drift_stats(self.opts)
+        return out
+
+
+def max_drift_hook(opts, radius: Optional[float], scope: str, num_steps: int, anchors=None) -> Optional[_MaxDrift]:
+    """A `_MaxDrift` over `opts`, or None without a radius (then nothing is imported, allocated or launched)."""
+    return None if radius is None else _MaxDrift(opts, radius, scope, num_steps, anchors)
 
 
 def _accumulate_micro_steps(optimizers, loss_at, grad_sync, step: int, n: int) -> torch.Tensor:
@@ -259,6 +293,18 @@ def _dora_optimizer(dit, dora_magnitudes, lr: float, **refused) -> Optional[Fuse
     return FusedAdamWClip(list(dora_magnitudes), lr=lr, betas=(0.9, 0.999), weight_decay=0.0, eps=1e-8)
 
 
+def _refuse_max_drift_with_dora(max_drift, dora_magnitudes) -> None:
+    if max_drift is not None and dora_magnitudes:
+        raise ValueError("max_drift cannot be combined with DoRA magnitudes (their bf16 adapters train without master weights, "
+                         "which the ball needs)")
+
+
+def _clones(params, max_drift):
+    """The base words of a ball around what `params` hold now, as the one-optimizer `anchors` of `max_drift_hook`; None without a
+    radius."""
+    return None if max_drift is None else [[p.detach().clone() for p in params]]
+
+
 def _joint_optimizer_step(opts, max_grad_norm: float) -> Callable[[], None]:
     """One clip coefficient over both optimizers' gradients, as the norm + delta tuning loop has it (tta/delta.py)."""
     def go():
@@ -284,13 +330,18 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
                                   early_stopper: Optional[AnchoredEarlyStopper] = None, lora_param_fn=None,
                                   train_latents_variants: Optional[List[Dict]] = None, stochastic_rounding: bool = False,
                                   dora_magnitudes: Optional[Sequence[torch.Tensor]] = None,
+                                  max_drift: Optional[float] = None, max_drift_scope: str = "global",
                                   *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                                   grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """`stochastic_rounding`: the bf16 adapters and moments take the fp32 step with stochastically rounded stores
     (include/lcv_hip_sr.h); no state beside them, so the stopper's snapshot and restore are the plain form's.
     `dora_magnitudes`: the fp32 magnitudes of DoRA adapters (tta.lora.get_dora_magnitudes), stepped by an optimizer of their own
-    under one joint clip; the stopper's snapshot covers both lists."""
+    under one joint clip; the stopper's snapshot covers both lists.
+    `max_drift` (with `master_weights`): after every step the adapters are projected onto a ball of that RMS radius around bf16
+    clones of their freshly initialised values (+2 B / adapter parameter; include/lcv_hip_trust.h); the result gains
+    `drift_norm` and `max_drift`."""
     params = _adapter_params(lora_modules, lora_param_fn)
+    _refuse_max_drift_with_dora(max_drift, dora_magnitudes)
     refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
     dora_opt = _dora_optimizer(dit, dora_magnitudes, lr, master_weights=master_weights, moments_8bit=moments_8bit,
                                stochastic_rounding=stochastic_rounding, weight_ema=weight_ema is not None,
@@ -306,21 +357,26 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
         opts = [opt, dora_opt]
         return run_adaptation(dit, params + list(dora_magnitudes), opts, _fm_loss(dit, feed, device, dtype),
                               _joint_optimizer_step(opts, max_grad_norm), num_steps, lr, warmup_steps, early_stopper)
-    return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
-                          num_steps, lr, warmup_steps, early_stopper, grad_sync=_sp_sync(dit, opt), grad_accum=grad_accum)
+    ball = max_drift_hook([opt], max_drift, max_drift_scope, num_steps, _clones(params, max_drift))
+    out = run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
+                         num_steps, lr, warmup_steps, early_stopper, grad_sync=_sp_sync(dit, opt), after_step=ball,
+                         grad_accum=grad_accum)
+    return out if ball is None else ball.finish(out)
 
 
 def finetune_lora_batch(dit: nn.Module, lora_modules, batch_data: List[Dict], num_steps: int = 20, lr: float = 2e-4,
                         warmup_steps: int = 3, weight_decay: float = 0.01, max_grad_norm: float = 1.0,
                         device: str = "cuda", dtype: torch.dtype = torch.bfloat16, lora_param_fn=None,
                         stochastic_rounding: bool = False, dora_magnitudes: Optional[Sequence[torch.Tensor]] = None,
+                        max_drift: Optional[float] = None, max_drift_scope: str = "global",
                         *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Shared adapters trained round-robin over the eval video and its neighbours; no early stopping (:558-634).  The feed
     receives the micro-step index, so `grad_accum` = number of videos puts every video behind each update.  `weight_ema`: the
     adapters end as their fp32 average over the steps.  `stochastic_rounding` and `dora_magnitudes`: as in
-    `finetune_lora_on_conditioning`."""
+    `finetune_lora_on_conditioning`; `max_drift` likewise."""
     params = _adapter_params(lora_modules, lora_param_fn)
+    _refuse_max_drift_with_dora(max_drift, dora_magnitudes)
     refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
     dora_opt = _dora_optimizer(dit, dora_magnitudes, lr, master_weights=master_weights, moments_8bit=moments_8bit,
                                stochastic_rounding=stochastic_rounding, weight_ema=weight_ema is not None,
@@ -335,5 +391,7 @@ def finetune_lora_batch(dit: nn.Module, lora_modules, batch_data: List[Dict], nu
         opts = [opt, dora_opt]
         return run_adaptation(dit, params + list(dora_magnitudes), opts, _fm_loss(dit, feed, device, dtype),
                               _joint_optimizer_step(opts, max_grad_norm), num_steps, lr, warmup_steps, None)
-    return run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
-                          num_steps, lr, warmup_steps, None, grad_sync=_sp_sync(dit, opt), grad_accum=grad_accum)
+    ball = max_drift_hook([opt], max_drift, max_drift_scope, num_steps, _clones(params, max_drift))
+    out = run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
+                         num_steps, lr, warmup_steps, None, grad_sync=_sp_sync(dit, opt), after_step=ball, grad_accum=grad_accum)
+    return out if ball is None else ball.finish(out)
