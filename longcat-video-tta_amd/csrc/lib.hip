@@ -13,7 +13,7 @@ void lcv_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int lcv_version(void) { return 16; }
+extern "C" int lcv_version(void) { return 17; }
 
 extern "C" const char* lcv_last_error(void) { return g_err; }
 

@@ -35,7 +35,8 @@ def main(argv=None):
         make_wrapper=lambda dit: DeltaAWrapper(dit, adaln_tembed_dim=dit.config.adaln_tembed_dim),
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_delta_a(
             w, cond, train, pe, pm, num_steps=args.delta_steps, lr=args.delta_lr, device=device, dtype=torch.bfloat16,
-            early_stopper=es, train_latents_variants=tv, **R.C.max_drift_kwargs(args)),
+            early_stopper=es, train_latents_variants=tv, **R.C.max_drift_kwargs(args),
+            **R.C.sam_kwargs(args)),
         result_extra=lambda opt: {"delta_norm": opt["delta_norm"]},
         summary_head={"delta_steps": args.delta_steps, "delta_lr": args.delta_lr, "batch_videos": args.batch_videos,
                       "retrieval_pool_dir": args.retrieval_pool_dir},

@@ -36,7 +36,8 @@ def main(argv=None):
                                                delta_dim=args.delta_dim, target_blocks=args.delta_target_blocks),
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_delta_b(
             w, cond, train, pe, pm, num_steps=args.delta_steps, lr=args.delta_lr, device=device, dtype=torch.bfloat16,
-            early_stopper=es, train_latents_variants=tv, **R.C.max_drift_kwargs(args)),
+            early_stopper=es, train_latents_variants=tv, **R.C.max_drift_kwargs(args),
+            **R.C.sam_kwargs(args)),
         result_extra=lambda opt: {"delta_norms": opt["delta_norms"]},
         summary_head={"delta_target": args.delta_target, "delta_target_blocks": args.delta_target_blocks,
                       "num_groups": args.num_groups, "delta_steps": args.delta_steps, "delta_lr": args.delta_lr},

@@ -34,7 +34,8 @@ def main(argv=None):
                                                     film_mode=args.film_mode),
         optimize_fn=lambda w, cond, train, pe, pm, device, es, tv=None: optimize_film_adapter(
             w, cond, train, pe, pm, num_steps=args.film_steps, lr=args.film_lr, device=device, dtype=torch.bfloat16,
-            early_stopper=es, train_latents_variants=tv, **R.C.max_drift_kwargs(args)),
+            early_stopper=es, train_latents_variants=tv, **R.C.max_drift_kwargs(args),
+            **R.C.sam_kwargs(args)),
         result_extra=lambda opt: {"correction_norm": opt["correction_norm"]},
         summary_head={"film_mode": args.film_mode, "num_groups": args.num_groups, "film_steps": args.film_steps,
                       "film_lr": args.film_lr},

@@ -36,7 +36,8 @@ EXTRA = {"attn_fwd.hip": _ATTN_FLAGS, "attn_fwd_pipe.hip": _ATTN_FLAGS, "attn_bw
          "optim_ema.hip": ["-ffp-contract=off"], "step_cache.hip": ["-ffp-contract=off"],
          "solver_step.hip": ["-ffp-contract=off"], "cfg_reuse.hip": ["-ffp-contract=off"],
          "optim_sr.hip": ["-ffp-contract=off"], "cfg_apg.hip": ["-ffp-contract=off"],
-         "dora.hip": ["-ffp-contract=off"], "optim_trust.hip": ["-ffp-contract=off"]}
+         "dora.hip": ["-ffp-contract=off"], "optim_trust.hip": ["-ffp-contract=off"],
+         "optim_sam.hip": ["-ffp-contract=off"]}
 
 
 def _compile(src: Path, hdr_mtime: float) -> Path:

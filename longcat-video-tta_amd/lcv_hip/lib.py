@@ -191,6 +191,16 @@ _SIGNATURES_TRUST = {
 }
 LCV_TRUST_GLOBAL, LCV_TRUST_TENSOR = 0, 1
 
+# include/lcv_hip_sam.h (a header of its own: the sharpness-aware adaptation step): sumsq takes (tensors, low, n_tensors,
+# total_chunks, int param_f32, int adaptive, double eta, partials, partials_bytes, per_tensor, out), perturb (tensors, low, save,
+# n_tensors, total_chunks, int param_f32, int adaptive, double eta, double rho, sumsq, partials, partials_bytes, per_tensor, realized,
+# trace_slot), restore (tensors, save, n_tensors, total_chunks, int param_f32); all return int
+_SIGNATURES_SAM = {
+    "lcv_sam_sumsq": [P, P, I64, I64, I, I, F64, P, I64, P, P, P],
+    "lcv_sam_perturb": [P, P, P, I64, I64, I, I, F64, F64, P, P, I64, P, P, P, P],
+    "lcv_sam_restore": [P, P, I64, I64, I, P],
+}
+
 LCV_EPI_NONE, LCV_EPI_SWIGLU, LCV_EPI_GATE_RESIDUAL, LCV_EPI_GELU_TANH, LCV_EPI_SILU = 0, 1, 2, 3, 4
 
 
@@ -253,7 +263,8 @@ def load():
                        + list(_SIGNATURES_ACCUM.items()) + list(_SIGNATURES_ANCHOR.items()) + list(_SIGNATURES_EMA.items())
                        + list(_SIGNATURES_STEPCACHE.items()) + list(_SIGNATURES_SOLVER.items())
                        + list(_SIGNATURES_CFGREUSE.items()) + list(_SIGNATURES_SR.items()) + list(_SIGNATURES_APG.items())
-                       + list(_SIGNATURES_DORA.items()) + list(_SIGNATURES_TRUST.items())):
+                       + list(_SIGNATURES_DORA.items()) + list(_SIGNATURES_TRUST.items())
+                       + list(_SIGNATURES_SAM.items())):
         fn = getattr(lib, name, None)
         if fn is None:
             continue  # export coverage is asserted by tests/test_abi.py against include/lcv_hip.h

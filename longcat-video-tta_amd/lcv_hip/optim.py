@@ -70,6 +70,12 @@ class FusedAdamWClip:
     the drift back onto the ball where it has left it, on the device, with no host sync; a weight average then takes the
     projected masters.
 
+    `enable_sam(rho, adaptive, eta)` (any parameter form; once, before the first step) prepares the sharpness-aware step
+    (include/lcv_hip_sam.h, +2 B per bf16 parameter and +4 B per fp32 one of saved words): between a first and a second
+    backward the module-level `sam_perturb([...])` moves the parameters to w + rho * g / |g| (one norm over every optimizer
+    handed to it) and `sam_restore([...])` puts every word back, so `step()` takes the second gradient on bit-identical
+    parameters.  While the parameters are perturbed (`sam_perturbed`) the optimizer refuses to clip, step, swap or project.
+
     A subclass supplies its `param_groups` entry (through `_init`), its moment storage (`_init_moments`), its hyper-parameter
     tuple (`_hyper`) and its `STEPS`."""
     CHUNK = 2048
@@ -79,6 +85,8 @@ class FusedAdamWClip:
     ema_in_params = False    # True between an ema_swap() and the next: the parameters hold the average
     _ema = ()
     max_drift = None         # the RMS radius of enable_max_drift(), or None: no ball is kept
+    sam_rho = None           # the rho of enable_sam(), or None: no sharpness-aware step is prepared
+    sam_perturbed = False    # True between a sam_perturb() and its sam_restore(): the parameters hold the perturbed point
 
     # The step entry points as the headers list them (lcv_hip.h, lcv_hip_master.h, lcv_hip_accum.h, lcv_hip_moments8.h,
     # lcv_hip_anchor.h).  (anchor, moments_8bit, grad_accum > 1, master_weights) -> the entry point, the pointer tables that
@@ -336,6 +344,7 @@ class FusedAdamWClip:
         """Exchange the average and the masters (lcv_master_ema_swap) and toggle `ema_in_params`: after one call the parameters
         are the average in valid master format (bf16 word = its round-to-nearest), after two every bit is back."""
         self._ema_needs("ema_swap()")
+        self._sam_guard("ema_swap()")
         ops.call("lcv_master_ema_swap", *self._ema_table(), _stream())
         self.ema_in_params = not self.ema_in_params
         ops.PARAM_EPOCH += 1         # the parameters changed under cached copies of them, as after a step
@@ -432,6 +441,104 @@ class FusedAdamWClip:
         coefficient applied (1.0: nothing was projected)."""
         self._md_needs("max_drift_trace()")
         return self._md_trace[:min(self._md_steps, self._md_trace.shape[0])].cpu()
+
+    # ------------------------------------------------------------------------------------------------ the sharpness-aware step
+    def enable_sam(self, rho: float, adaptive: bool = False, eta: float = 0.01, trace_len: int = 4096) -> None:
+        """Prepare the sharpness-aware step (include/lcv_hip_sam.h): `sam_perturb([...])` after a first backward moves the
+        parameters that hold a gradient to w + rho * g / |g| (`adaptive`: ASAM's |w| + eta scaling) and `sam_restore([...])`
+        after the second backward puts every word back.  `rho` >= 0 and finite (0: both passes run, nothing is written, the
+        gradient-norm trace is recorded).  For every parameter form; bf16 parameters take bf16 gradients, so not with
+        `grad_accum` > 1.  Once, before the first `step()`.  Allocates the saved words of all non-empty parameters (+2 B per bf16
+        parameter, +4 B per fp32 one), one float per chunk and per tensor, and `trace_len` pairs of floats for the per-step
+        trace; steps past `trace_len` are perturbed and not recorded."""
+        name = type(self).__name__
+        if self.sam_rho is not None:
+            raise _lib.LcvError(f"{name}: enable_sam() was already called")
+        rho, eta = float(rho), float(eta)
+        if not 0.0 <= rho < float("inf"):     # a NaN fails too
+            raise _lib.LcvError(f"{name}: the rho of enable_sam() must be finite and >= 0, got {rho}")
+        if not 0.0 <= eta < float("inf"):
+            raise _lib.LcvError(f"{name}: the eta of enable_sam() must be finite and >= 0, got {eta}")
+        if self.grad_accum > 1:
+            raise _lib.LcvError(f"{name}: enable_sam() cannot be combined with grad_accum > 1 (a perturbation per micro-step is a "
+                                "different algorithm)")
+        if self.step_count:
+            raise _lib.LcvError(f"{name}: enable_sam() comes before the first step(), not after {self.step_count}")
+        if int(trace_len) < 1:
+            raise _lib.LcvError(f"{name}: trace_len must be at least 1, got {trace_len}")
+        if any(not p.is_cuda or not p.is_contiguous() for p in self.params):
+            raise _lib.LcvError(f"{name}: enable_sam() needs contiguous parameters on the GPU (no CPU path exists)")
+        sel = self._nonempty()
+        if not sel:
+            raise _lib.LcvError(f"{name}: a perturbation over no elements")
+        dev = self.params[0].device
+        chunks = sum((self.params[i].numel() + self.CHUNK - 1) // self.CHUNK for i in sel)
+        self._sam_adaptive, self._sam_eta = bool(adaptive), eta
+        self._sam_save = [torch.empty_like(p) for p in self.params]      # the words the forward reads, saved exactly
+        self._sam_part = torch.empty((chunks,), dtype=F32, device=dev)
+        self._sam_per = torch.empty((len(sel),), dtype=F32, device=dev)
+        self._sam_out = torch.zeros(2, dtype=F32, device=dev)
+        self._sam_real = torch.zeros(2, dtype=F32, device=dev)
+        self._sam_trace = torch.zeros((int(trace_len), 2), dtype=F32, device=dev)
+        self._sam_steps = 0
+        self._sam_live = None                # the table of the perturbation under way, kept for its restore
+        self.sam_rho = rho
+
+    def _sam_needs(self, what: str) -> None:
+        if self.sam_rho is None:
+            raise _lib.LcvError(f"{type(self).__name__}: {what} needs enable_sam()")
+
+    def _sam_guard(self, what: str) -> None:
+        """Nobody steps, clips, swaps or projects the perturbed point by accident."""
+        if self.sam_perturbed:
+            raise _lib.LcvError(f"{type(self).__name__}: {what} while the parameters are perturbed (sam_perturbed); call "
+                                "sam_restore() to put them back first")
+
+    def _sam_measure(self) -> bool:
+        """lcv_sam_sumsq over the parameters that hold a gradient, into `_sam_out`; False (and nothing launched) when none does.
+        The table is kept in `_sam_live` for the perturbation and its restore."""
+        sel, grads = [], []
+        for i, g in zip(*self._with_grad()):
+            if self.params[i].numel():
+                sel.append(i)
+                grads.append(g)
+        if not sel:
+            self._sam_live = None
+            return False
+        if any(g.dtype != self.params[0].dtype for g in grads):
+            raise _lib.LcvError(f"{type(self).__name__}: sam_perturb() takes gradients of the parameters' dtype")
+        self._sam_grads = grads              # keep alive until the perturbation is launched
+        sides = {k: ts for k, ts in (("low", self._low), ("save", self._sam_save)) if ts}
+        key = tuple(g.data_ptr() for g in grads) + tuple(sel) + tuple(t.data_ptr() for ts in (self.params, *sides.values()) for t in ts)
+        t = self._sam_live = self._cached("sam", key, lambda: self._build_table(sel, [(g.data_ptr(), 0, 0) for g in grads], **sides))
+        ops.call("lcv_sam_sumsq", _ptr(t.desc), _ptr(t.sides.get("low")), t.n, t.chunks, 1 if self.f32 else 0,
+                 1 if self._sam_adaptive else 0, self._sam_eta, _ptr(self._sam_part), self._sam_part.numel() * 4,
+                 _ptr(self._sam_per), _ptr(self._sam_out), _stream())
+        return True
+
+    def _sam_perturb(self, sumsq: torch.Tensor) -> None:
+        """Launch this optimizer's perturbation against the total `sumsq` (a device tensor) and record the step in the trace
+        while it has room."""
+        t = self._sam_live
+        slot = self._sam_trace[self._sam_steps] if self._sam_steps < self._sam_trace.shape[0] else None
+        ops.call("lcv_sam_perturb", _ptr(t.desc), _ptr(t.sides.get("low")), _ptr(t.sides["save"]), t.n, t.chunks,
+                 1 if self.f32 else 0, 1 if self._sam_adaptive else 0, self._sam_eta, self.sam_rho, _ptr(sumsq),
+                 _ptr(self._sam_part), self._sam_part.numel() * 4, _ptr(self._sam_per), _ptr(self._sam_real), _ptr(slot), _stream())
+        self._sam_grads = None
+        self.sam_perturbed = True
+
+    def _sam_restore(self) -> None:
+        t = self._sam_live
+        ops.call("lcv_sam_restore", _ptr(t.desc), _ptr(t.sides["save"]), t.n, t.chunks, 1 if self.f32 else 0, _stream())
+        self.sam_perturbed = False
+
+    def sam_trace(self) -> torch.Tensor:
+        """The trace so far as a [steps, 2] fp32 CPU tensor, read in one copy: per perturbed step the total sum of squares of
+        the (scaled) gradient the perturbation was normalised by (of every optimizer perturbed together) and the sum of squares
+        of what this optimizer's stored words really moved by; a step in which this optimizer held no gradient is a row of
+        zeros."""
+        self._sam_needs("sam_trace()")
+        return self._sam_trace[:min(self._sam_steps, self._sam_trace.shape[0])].cpu()
 
     def _init_accum(self, grad_accum: int) -> None:
         """Zeroed fp32 accumulators (+4 B / parameter) when `grad_accum` > 1; nothing at 1."""
@@ -559,6 +666,7 @@ class FusedAdamWClip:
 
     def clip_grad_norm_(self, max_norm: float) -> torch.Tensor:
         self._ema_guard("clip_grad_norm_()")
+        self._sam_guard("clip_grad_norm_()")
         t = self._step_table()
         head = (_ptr(t.desc), t.n, t.chunks, 1 if self._grad_f32 else 0, float(max_norm), _ptr(self._ws), _ptr(self._norm_coef))
         if ops.is_deterministic():   # one fp32 partial per chunk for the fixed-order clip
@@ -596,6 +704,7 @@ class FusedAdamWClip:
 
     def step(self):
         self._ema_guard("step()")
+        self._sam_guard("step()")
         t = self._step_table()
         self.step_count += 1
         coef = _ptr(self._norm_coef) if self._have_coef else None
@@ -667,6 +776,7 @@ def _max_drift_group(opts, training: bool = False):
         o._md_needs("project_max_drift()")
         if training:
             o._ema_guard("project_max_drift()")
+            o._sam_guard("project_max_drift()")
     if len({(o.max_drift, o._md_scope) for o in opts}) != 1:
         raise _lib.LcvError("project_max_drift: every optimizer of one ball takes the same radius and scope")
     return opts
@@ -723,3 +833,67 @@ def max_drift_stats(opts) -> dict:
     return {"radius": opts[0].max_drift, "scope": opts[0]._md_scope, "steps": steps, "projections": len(hit),
             "first_projected_step": hit[0] + 1 if hit else None, "min_coef": float(coef.min().item()) if steps else 1.0,
             "drift_rms_trace": (total / numel).sqrt().tolist()}
+
+
+# ===================================================================== the sharpness-aware step over several optimizers
+def _sam_group(opts, what: str):
+    """The optimizers of one perturbation: all prepared by enable_sam() with the same rho, form and eta."""
+    opts = list(opts)
+    if not opts:
+        raise _lib.LcvError(f"{what}: no optimizer")
+    for o in opts:
+        o._sam_needs(f"{what}()")
+    if len({(o.sam_rho, o._sam_adaptive, o._sam_eta) for o in opts}) != 1:
+        raise _lib.LcvError(f"{what}: every optimizer of one perturbation takes the same rho, adaptive and eta")
+    return opts
+
+
+def sam_perturb(opts) -> None:
+    """Between the two backward passes of a sharpness-aware step (include/lcv_hip_sam.h), with no host sync: lcv_sam_sumsq of
+    every optimizer that holds a gradient; their totals added on the device in the optimizers' order in fp32 into one norm;
+    every such optimizer's lcv_sam_perturb against it, which saves the words the forward reads and stores the perturbed ones;
+    the trace slot moves on and `ops.PARAM_EPOCH` is bumped (the kernels write through raw pointers, so `_version` does not
+    move; the cached weight copies key on the epoch).  The caller drops the gradients next; the table of what was touched is
+    kept for `sam_restore`."""
+    opts = _sam_group(opts, "sam_perturb")
+    for o in opts:
+        o._sam_guard("sam_perturb()")
+        o._ema_guard("sam_perturb()")
+    live = [o for o in opts if o._sam_measure()]
+    if not live:
+        raise _lib.LcvError("sam_perturb: no parameter has a gradient")
+    joint = live[0]._sam_out[0]
+    if len(live) > 1:
+        joint = joint.clone()
+        for o in live[1:]:
+            joint += o._sam_out[0]
+    for o in live:
+        o._sam_perturb(joint)
+    for o in opts:                   # an optimizer without a gradient leaves a row of zeros: the traces stay step-aligned
+        o._sam_steps += 1
+    ops.PARAM_EPOCH += 1
+
+
+def sam_restore(opts) -> None:
+    """Put back, word for word, exactly the tensors the last `sam_perturb` touched (lcv_sam_restore; their `.grad` may be gone,
+    the table was kept) and bump `ops.PARAM_EPOCH`.  Refuses to run without a perturbation, so also twice."""
+    opts = _sam_group(opts, "sam_restore")
+    live = [o for o in opts if o.sam_perturbed]
+    if not live:
+        raise _lib.LcvError("sam_restore: the parameters are not perturbed (no sam_perturb() since the last restore)")
+    for o in live:
+        o._sam_restore()
+    ops.PARAM_EPOCH += 1
+
+
+def sam_stats(opts) -> dict:
+    """The `sam` entry of a result row from the optimizers' traces (one copy each, after the loop): rho, adaptive, eta, the
+    number of recorded steps, and per step the norm of the (scaled) gradient the perturbation was normalised by and the norm of
+    what the stored words really moved by - for bf16 words far below rho, see the header."""
+    opts = _sam_group(opts, "sam_stats")
+    traces = [o.sam_trace().double() for o in opts]
+    steps = min(t.shape[0] for t in traces)
+    total = torch.stack([t[:steps, 0] for t in traces]).max(0).values if steps else torch.zeros(0, dtype=torch.float64)
+    moved = sum(t[:steps, 1] for t in traces)
+    return {"rho": opts[0].sam_rho, "adaptive": opts[0]._sam_adaptive, "eta": opts[0]._sam_eta, "steps": steps,
+            "grad_norm_trace": total.sqrt().tolist(), "realized_norm_trace": moved.sqrt().tolist()}

@@ -66,6 +66,7 @@ def full_method(args) -> R.TTAMethod:
                              "master_weights": args.master_weights, "adam_8bit": args.adam_8bit,
                              "grad_accum": args.grad_accum, **({"decay_to_base": True} if args.decay_to_base else {}),
                              **C.weight_ema_record(args), **C.stochastic_rounding_record(args), **C.max_drift_record(args),
+                             **C.sam_record(args),
                              "total_params": job["total_params"], "trainable_params": trainable_params},
                 "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                                "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
@@ -92,7 +93,7 @@ def full_method(args) -> R.TTAMethod:
 
     def row_extra(tr, variants, blob):
         return {"num_train_steps": len(tr["losses"]), **({"drift_norm": tr["drift_norm"]} if args.decay_to_base else {}),
-                **C.stochastic_rounding_record(args), **C.max_drift_result(tr)}
+                **C.stochastic_rounding_record(args), **C.max_drift_result(tr), **C.sam_result(tr)}
 
     def summary_extra(merged, ok):
         return {"learning_rate": args.learning_rate, "num_steps": args.num_steps, "batch_videos": args.batch_videos,

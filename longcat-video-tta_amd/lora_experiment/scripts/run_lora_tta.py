@@ -129,7 +129,8 @@ def lora_method(args) -> R.TTAMethod:
                              "warmup_steps": args.warmup_steps, "weight_decay": args.weight_decay,
                              "max_grad_norm": args.max_grad_norm, "master_weights": args.master_weights,
                              "adam_8bit": args.adam_8bit, "grad_accum": args.grad_accum, **C.weight_ema_record(args),
-                             **C.stochastic_rounding_record(args), **C.max_drift_record(args)},
+                             **C.stochastic_rounding_record(args), **C.max_drift_record(args),
+                             **C.sam_record(args)},
                 "generation": {"num_cond_frames": args.num_cond_frames, "num_frames": args.num_frames,
                                "num_inference_steps": args.num_inference_steps, "guidance_scale": args.guidance_scale,
                                "resolution": args.resolution, **C.step_cache_record(args),
@@ -151,7 +152,7 @@ def lora_method(args) -> R.TTAMethod:
         return {"num_train_steps": len(tr["losses"]),
                 **({"aug_variants": [v["name"] for v in variants]} if variants is not None else {}),
                 **({} if args.skip_generation else {"cond_source": blob.get("_cond_source")}),
-                **C.stochastic_rounding_record(args), **C.max_drift_result(tr)}
+                **C.stochastic_rounding_record(args), **C.max_drift_result(tr), **C.sam_result(tr)}
 
     def summary_extra(merged, ok):
         return {"lora_rank": args.lora_rank, "lora_alpha": args.lora_alpha, "learning_rate": args.learning_rate,

@@ -161,7 +161,8 @@ def optimizer_kwargs(args) -> dict:
     kw = {"master_weights": args.master_weights, "moments_8bit": args.adam_8bit, "grad_accum": args.grad_accum}
     if hasattr(args, "decay_to_base"):
         kw["decay_to_base"] = args.decay_to_base
-    return {**kw, **weight_ema_kwargs(args), **stochastic_rounding_record(args), **max_drift_kwargs(args)}
+    return {**kw, **weight_ema_kwargs(args), **stochastic_rounding_record(args), **max_drift_kwargs(args),
+            **sam_kwargs(args)}
 
 
 def weight_ema_kwargs(args) -> dict:
@@ -220,6 +221,7 @@ def parse_with_step_cache(parser, argv=None, parse=None):
     check_cfg_reuse_args(parser, args)
     check_apg_args(parser, args)
     check_max_drift_args(parser, args)
+    check_sam_args(parser, args)
     return args
 
 
@@ -447,6 +449,69 @@ def max_drift_result(loop) -> dict:
     """The per-video `drift_norm` and `max_drift` entry ({radius, scope, steps, projections, first_projected_step, min_coef,
     drift_rms_trace}) the loop left in its result; nothing without the flag."""
     return {"drift_norm": loop["drift_norm"], "max_drift": loop["max_drift"]} if "max_drift" in loop else {}
+
+
+def add_sam_args(parser):
+    parser.add_argument("--sam-rho", type=float, default=None, metavar="RHO",
+                        help="sharpness-aware adaptation steps (SAM, include/lcv_hip_sam.h): every optimizer step takes its "
+                             "gradient at w + RHO * g / |g|, one norm over all trained parameters, on the device; two "
+                             "forward/backward passes per step under the same noise, sigma, variant and dropout draws; 0 runs "
+                             "both passes, changes no bit of the run and records the gradient-norm trace (calibration); not with "
+                             "--grad-accum above 1 or --lora-dora; no rho is recommended")
+    parser.add_argument("--sam-adaptive", action="store_true",
+                        help="with --sam-rho: the adaptive form (ASAM), the perturbation of an element scaled by (|w| + ETA)^2 "
+                             "and RHO measured in the (|w| + ETA)-scaled norm")
+    parser.add_argument("--sam-eta", type=float, default=None, metavar="ETA",
+                        help="with --sam-adaptive: the ETA of |w| + ETA (default 0.01)")
+
+
+SAM_ETA_DEFAULT = 0.01
+
+
+def check_sam_args(parser, args) -> None:
+    """The refusals of --sam-rho as the parser's own one-line error (exit status 2).  Called from `parse_with_step_cache`, which
+    every runner parses through; a parser without the flags is left alone."""
+    rho, eta = getattr(args, "sam_rho", None), getattr(args, "sam_eta", None)
+    adaptive = getattr(args, "sam_adaptive", False)
+    if rho is None:
+        if adaptive:
+            parser.error("--sam-adaptive needs --sam-rho RHO")
+        if eta is not None:
+            parser.error("--sam-eta needs --sam-rho RHO")
+        return
+    if not 0.0 <= rho < float("inf"):                                     # a NaN fails too
+        parser.error(f"--sam-rho RHO must be finite and >= 0, got {rho}")
+    if eta is not None and not adaptive:
+        parser.error("--sam-eta needs --sam-adaptive")
+    if eta is not None and not 0.0 <= eta < float("inf"):
+        parser.error(f"--sam-eta ETA must be finite and >= 0, got {eta}")
+    if getattr(args, "grad_accum", 1) > 1:
+        parser.error("--sam-rho cannot be combined with --grad-accum above 1 (a perturbation per micro-step is a different "
+                     "algorithm)")
+    if getattr(args, "lora_dora", False):
+        parser.error("--sam-rho cannot be combined with --lora-dora (the row norm is held constant in the backward and the "
+                     "forward caches it)")
+
+
+def sam_kwargs(args) -> dict:
+    """The loop functions' keywords for --sam-rho; nothing when the flag is absent (then nothing is imported, allocated or
+    launched)."""
+    if getattr(args, "sam_rho", None) is None:
+        return {}
+    eta = args.sam_eta if args.sam_eta is not None else SAM_ETA_DEFAULT
+    return {"sam_rho": args.sam_rho, "sam_adaptive": bool(args.sam_adaptive), "sam_eta": eta}
+
+
+def sam_record(args) -> dict:
+    """What config.json (`training`) and the flat summary.json of the runners without one record of --sam-rho; nothing when the
+    flag is absent."""
+    return sam_kwargs(args)
+
+
+def sam_result(loop) -> dict:
+    """The per-video `sam` entry ({rho, adaptive, eta, steps, grad_norm_trace, realized_norm_trace, perturbed_loss_trace}) the
+    loop left in its result; nothing without the flag."""
+    return {"sam": loop["sam"]} if "sam" in loop else {}
 
 
 def normalize_tta_frame_args(args):

@@ -21,7 +21,8 @@ import torch.nn.functional as F
 from lcv_hip.ops import FusedAdamWClip
 
 from .early_stopping import AnchoredEarlyStopper
-from .inner_loop import _OneVideo, _fm_loss, max_drift_hook, refuse_stochastic_rounding_under_sp, run_adaptation
+from .inner_loop import (_OneVideo, _fm_loss, max_drift_hook, refuse_sam, refuse_stochastic_rounding_under_sp, run_adaptation,
+                         sam_hook)
 from .lora import _parse_target_blocks
 
 
@@ -220,7 +221,8 @@ class FiLMAdapterWrapper(_HookedWrapper):
 def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bool, cond_latents, train_latents,
               prompt_embeds, prompt_mask, num_steps, lr, device, dtype, early_stopper, train_latents_variants,
               master_weights=False, moments_8bit=False, grad_accum=1, decay_to_base=False, info=None,
-              weight_ema=None, ema_warmup=False, stochastic_rounding=False, max_drift=None, max_drift_scope="global"):
+              weight_ema=None, ema_warmup=False, stochastic_rounding=False, max_drift=None, max_drift_scope="global",
+              sam_rho=None, sam_adaptive=False, sam_eta=0.01):
     """AdamW(0.9, 0.999, wd 0.01, eps 1e-15), clip at 1.0, no warm-up (run_delta_a.py:224-305 and its siblings) on the
     shared engine.  Clipping comes in the three shapes the reference scripts use: per parameter (delta-B,
     run_delta_b.py:386-388), one global norm, or — bf16 norm weights tuned together with an fp32 delta vector — one fused
@@ -240,8 +242,11 @@ def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bo
     around where they started (include/lcv_hip_trust.h): zero for the fp32 vectors, the `decay_to_base` clones (or clones taken
     here) for bf16 norm weights; `max_drift_scope` "global" is one ball over every optimizer made here (delta-B's one per
     parameter, the bf16 and the fp32 one of norm + delta tuning), "tensor" one per parameter tensor.  `info` then receives
-    `drift_norm` and `max_drift`."""
+    `drift_norm` and `max_drift`.
+    `sam_rho` (>= 0; `sam_adaptive`, `sam_eta`) makes every step a sharpness-aware one (include/lcv_hip_sam.h): two
+    forward/backward passes, one perturbation norm over every optimizer made here; `info` then receives `sam`."""
     refuse_stochastic_rounding_under_sp(wrapper, stochastic_rounding)
+    refuse_sam(wrapper, sam_rho, grad_accum)
     if stochastic_rounding and any(p.dtype != torch.bfloat16 for p in params):
         raise ValueError("stochastic_rounding cannot train fp32 parameters (the delta vector of --also-tune-delta): an fp32 "
                          "step rounds nothing to bf16")
@@ -284,7 +289,10 @@ def _optimize(wrapper: nn.Module, params: List[nn.Parameter], per_param_clip: bo
                               [None if o.f32 or o._anchor else [p.detach().clone() for p in o.params] for o in opts])
     feed = _OneVideo(cond_latents, train_latents, prompt_embeds, prompt_mask, train_latents_variants)
     out = run_adaptation(wrapper, params, opts, _fm_loss(wrapper, feed, device, dtype), clip_and_step, num_steps,
-                         early_stopper=early_stopper, after_step=ball, finish_eval=False, grad_accum=grad_accum)
+                         early_stopper=early_stopper, sam=sam_hook(opts, sam_rho, sam_adaptive, sam_eta, num_steps),
+                         after_step=ball, finish_eval=False, grad_accum=grad_accum)
+    if "sam" in out and info is not None:
+        info["sam"] = out["sam"]
     if decay_to_base and info is not None:
         sq = [o.drift_norm() ** 2 for o in opts if o._anchor]
         info["drift_norm"] = float(torch.stack(sq).sum().sqrt().item()) if sq else 0.0
@@ -297,11 +305,13 @@ def optimize_delta_a(wrapper: DeltaAWrapper, cond_latents, train_latents, prompt
                      lr: float = 1e-3, device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                      early_stopper: Optional[AnchoredEarlyStopper] = None,
                      train_latents_variants: Optional[List[Dict]] = None, max_drift: Optional[float] = None,
-                     max_drift_scope: str = "global") -> Dict:
+                     max_drift_scope: str = "global", sam_rho: Optional[float] = None, sam_adaptive: bool = False,
+                     sam_eta: float = 0.01) -> Dict:
     info: Dict = {}
     losses, est, es_state = _optimize(wrapper, [wrapper.delta], False, cond_latents, train_latents, prompt_embeds,
                                       prompt_mask, num_steps, lr, device, dtype, early_stopper, train_latents_variants,
-                                      info=info, max_drift=max_drift, max_drift_scope=max_drift_scope)
+                                      info=info, max_drift=max_drift, max_drift_scope=max_drift_scope,
+                                      sam_rho=sam_rho, sam_adaptive=sam_adaptive, sam_eta=sam_eta)
     return {"losses": losses, "delta_norm": wrapper.delta.detach().norm().item(), "es_check_time": est,
             "early_stopping_info": es_state, **info}
 
@@ -310,12 +320,14 @@ def optimize_delta_b(wrapper: DeltaBWrapper, cond_latents, train_latents, prompt
                      lr: float = 1e-3, device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                      early_stopper: Optional[AnchoredEarlyStopper] = None,
                      train_latents_variants: Optional[List[Dict]] = None, max_drift: Optional[float] = None,
-                     max_drift_scope: str = "global") -> Dict:
+                     max_drift_scope: str = "global", sam_rho: Optional[float] = None, sam_adaptive: bool = False,
+                     sam_eta: float = 0.01) -> Dict:
     params = list(wrapper.deltas) + ([wrapper.delta_final] if wrapper.delta_final is not None else [])
     info: Dict = {}
     losses, est, es_state = _optimize(wrapper, params, True, cond_latents, train_latents, prompt_embeds, prompt_mask,
                                       num_steps, lr, device, dtype, early_stopper, train_latents_variants,
-                                      info=info, max_drift=max_drift, max_drift_scope=max_drift_scope)
+                                      info=info, max_drift=max_drift, max_drift_scope=max_drift_scope,
+                                      sam_rho=sam_rho, sam_adaptive=sam_adaptive, sam_eta=sam_eta)
     delta_norms = [d.detach().norm().item() for d in wrapper.deltas]
     if wrapper.delta_final is not None:   # run_delta_b.py:413-415
         delta_norms.append(wrapper.delta_final.detach().norm().item())
@@ -326,11 +338,13 @@ def optimize_delta_c(wrapper: DeltaCWrapper, cond_latents, train_latents, prompt
                      lr: float = 1e-3, device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                      early_stopper: Optional[AnchoredEarlyStopper] = None,
                      train_latents_variants: Optional[List[Dict]] = None, max_drift: Optional[float] = None,
-                     max_drift_scope: str = "global") -> Dict:
+                     max_drift_scope: str = "global", sam_rho: Optional[float] = None, sam_adaptive: bool = False,
+                     sam_eta: float = 0.01) -> Dict:
     info: Dict = {}
     losses, est, es_state = _optimize(wrapper, [wrapper.delta_out], False, cond_latents, train_latents, prompt_embeds,
                                       prompt_mask, num_steps, lr, device, dtype, early_stopper, train_latents_variants,
-                                      info=info, max_drift=max_drift, max_drift_scope=max_drift_scope)
+                                      info=info, max_drift=max_drift, max_drift_scope=max_drift_scope,
+                                      sam_rho=sam_rho, sam_adaptive=sam_adaptive, sam_eta=sam_eta)
     return {"losses": losses, "delta_out_norm": wrapper.delta_out.detach().norm().item(),           # run_delta_c.py:240-246
             "delta_out_values": wrapper.delta_out.detach().cpu().tolist(), "es_check_time": est, "early_stopping_info": es_state,
             **info}
@@ -340,13 +354,15 @@ def optimize_film_adapter(wrapper: FiLMAdapterWrapper, cond_latents, train_laten
                           num_steps: int = 20, lr: float = 1e-3, device: str = "cuda", dtype: torch.dtype = torch.bfloat16,
                           early_stopper: Optional[AnchoredEarlyStopper] = None,
                           train_latents_variants: Optional[List[Dict]] = None, max_drift: Optional[float] = None,
-                          max_drift_scope: str = "global") -> Dict:
+                          max_drift_scope: str = "global", sam_rho: Optional[float] = None, sam_adaptive: bool = False,
+                          sam_eta: float = 0.01) -> Dict:
     """run_film_tta.py:266-341: AdamW(eps 1e-15) over all corrections, one global clip at 1.0."""
     params = list(wrapper.corrections)
     info: Dict = {}
     losses, est, es_state = _optimize(wrapper, params, False, cond_latents, train_latents, prompt_embeds, prompt_mask,
                                       num_steps, lr, device, dtype, early_stopper, train_latents_variants,
-                                      info=info, max_drift=max_drift, max_drift_scope=max_drift_scope)
+                                      info=info, max_drift=max_drift, max_drift_scope=max_drift_scope,
+                                      sam_rho=sam_rho, sam_adaptive=sam_adaptive, sam_eta=sam_eta)
     return {"losses": losses, "correction_norm": sum(c.detach().norm().item() for c in wrapper.corrections),
             "es_check_time": est, "early_stopping_info": es_state, **info}
 
@@ -436,6 +452,7 @@ def optimize_norm_params(wrapper: NormTuneForward, norm_params: List[nn.Paramete
                          dtype: torch.dtype = torch.bfloat16, early_stopper: Optional[AnchoredEarlyStopper] = None,
                          train_latents_variants: Optional[List[Dict]] = None, stochastic_rounding: bool = False,
                          max_drift: Optional[float] = None, max_drift_scope: str = "global",
+                         sam_rho: Optional[float] = None, sam_adaptive: bool = False, sam_eta: float = 0.01,
                          *, weight_ema: Optional[float] = None,
                          ema_warmup: bool = False, decay_to_base: bool = False, grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """run_norm_tune_tta.py:215-283 (same positional order: the parameter list is the second argument): AdamW(eps 1e-15) over
@@ -449,7 +466,8 @@ def optimize_norm_params(wrapper: NormTuneForward, norm_params: List[nn.Paramete
     `stochastic_rounding` (without `master_weights`): the fp32 step with stochastically rounded bf16 stores
     (include/lcv_hip_sr.h); with the fp32 delta vector in the list it raises too.
     `max_drift` (with `master_weights`): the ball of `_optimize` over the norm weights and, when it is in the list, the delta
-    vector; adds `drift_norm` (over all of them) and `max_drift`."""
+    vector; adds `drift_norm` (over all of them) and `max_drift`.
+    `sam_rho`: the sharpness-aware step of `_optimize`, one norm over the norm weights and the delta vector; adds `sam`."""
     norm_params = list(norm_params)
     info: Dict = {}
     losses, est, es_state = _optimize(wrapper, norm_params, False, cond_latents, train_latents, prompt_embeds,
@@ -457,7 +475,7 @@ def optimize_norm_params(wrapper: NormTuneForward, norm_params: List[nn.Paramete
                                       master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
                                       decay_to_base=decay_to_base, info=info, weight_ema=weight_ema, ema_warmup=ema_warmup,
                                       stochastic_rounding=stochastic_rounding, max_drift=max_drift,
-                                      max_drift_scope=max_drift_scope)
+                                      max_drift_scope=max_drift_scope, sam_rho=sam_rho, sam_adaptive=sam_adaptive, sam_eta=sam_eta)
     out = {"losses": losses, "early_stopping_info": es_state, "es_check_time": est}
     out.update(info)
     if getattr(wrapper, "_orig", None) and len(wrapper._orig) == len(wrapper.norm_params):

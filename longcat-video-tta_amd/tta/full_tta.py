@@ -21,8 +21,8 @@ import torch.nn as nn
 from lcv_hip.ops import FusedAdamWClip, FusedSGDClip
 
 from .early_stopping import AnchoredEarlyStopper
-from .inner_loop import (_OneVideo, _RoundRobin, _fm_loss, _single_optimizer_step, max_drift_hook,
-                         refuse_stochastic_rounding_under_sp, run_adaptation)
+from .inner_loop import (_OneVideo, _RoundRobin, _fm_loss, _single_optimizer_step, max_drift_hook, refuse_sam,
+                         refuse_stochastic_rounding_under_sp, run_adaptation, sam_hook)
 
 
 def snapshot_base_state(dit: nn.Module) -> Dict[str, torch.Tensor]:
@@ -90,9 +90,12 @@ def _anchors(dit: nn.Module, base_state: Optional[Dict[str, torch.Tensor]]) -> L
 
 def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper, optimizer_type,
          *, master_weights, moments_8bit, grad_accum, decay_to_base, base_state, weight_ema, ema_warmup,
-         stochastic_rounding=False, max_drift=None, max_drift_scope="global"):
+         stochastic_rounding=False, max_drift=None, max_drift_scope="global", sam_rho=None, sam_adaptive=False, sam_eta=0.01):
     params = _trainable(dit)
     refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
+    # `sam_rho`: every step is a sharpness-aware one (include/lcv_hip_sam.h): two forward/backward passes, +2 B / parameter of
+    # saved words (27 GB for the whole model: a memory decision)
+    refuse_sam(dit, sam_rho, grad_accum)
     # `decay_to_base`: the weight decay pulls toward the base words (include/lcv_hip_anchor.h), which are the caller's
     # `base_state` entries or, without one, +2 B / parameter of clones; a `base_state` alone only measures the drift
     # `max_drift`: after every step the weights are projected onto a ball of that RMS radius around the same base words
@@ -113,7 +116,8 @@ def _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, de
         opt.enable_weight_ema(weight_ema, ema_warmup)   # run_adaptation scores it and leaves it in the parameters
     ball = max_drift_hook([opt], max_drift, max_drift_scope, num_steps, [anchor])
     out = run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
-                         num_steps, lr, warmup_steps, early_stopper, after_step=ball, grad_accum=grad_accum)
+                         num_steps, lr, warmup_steps, early_stopper,
+                         sam=sam_hook([opt], sam_rho, sam_adaptive, sam_eta, num_steps), after_step=ball, grad_accum=grad_accum)
     opt.zero_grad(set_to_none=True)            # the gradients of 13.6 B parameters are dead weight during generation
     if ball is not None:                       # |theta - theta0| from the ball's own fixed-order sum (lcv_trust_sumsq) and the
         ball.finish(out)                       # trace's summary: one pass, not a second one through lcv_master_drift_sumsq
@@ -130,7 +134,8 @@ def finetune_full_on_conditioning(dit: nn.Module, cond_latents: torch.Tensor, tr
                                   early_stopper: Optional[AnchoredEarlyStopper] = None,
                                   train_latents_variants: Optional[List[Dict]] = None, optimizer_type: str = "sgd",
                                   stochastic_rounding: bool = False, max_drift: Optional[float] = None,
-                                  max_drift_scope: str = "global",
+                                  max_drift_scope: str = "global", sam_rho: Optional[float] = None,
+                                  sam_adaptive: bool = False, sam_eta: float = 0.01,
                                   *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                                   decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
                                   grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
@@ -138,13 +143,15 @@ def finetune_full_on_conditioning(dit: nn.Module, cond_latents: torch.Tensor, tr
     return _run(dit, feed, num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype, early_stopper,
                 optimizer_type, master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
                 decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup,
-                stochastic_rounding=stochastic_rounding, max_drift=max_drift, max_drift_scope=max_drift_scope)
+                stochastic_rounding=stochastic_rounding, max_drift=max_drift, max_drift_scope=max_drift_scope,
+                sam_rho=sam_rho, sam_adaptive=sam_adaptive, sam_eta=sam_eta)
 
 
 def finetune_full_batch(dit: nn.Module, batch_data: List[Dict], num_steps: int = 10, lr: float = 1e-5, warmup_steps: int = 2,
                         weight_decay: float = 0.01, max_grad_norm: float = 1.0, device: str = "cuda",
                         dtype: torch.dtype = torch.bfloat16, optimizer_type: str = "sgd", stochastic_rounding: bool = False,
                         max_drift: Optional[float] = None, max_drift_scope: str = "global",
+                        sam_rho: Optional[float] = None, sam_adaptive: bool = False, sam_eta: float = 0.01,
                         *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                         decay_to_base: bool = False, base_state: Optional[Dict[str, torch.Tensor]] = None,
                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
@@ -152,4 +159,5 @@ def finetune_full_batch(dit: nn.Module, batch_data: List[Dict], num_steps: int =
     return _run(dit, _RoundRobin(batch_data, device), num_steps, lr, warmup_steps, weight_decay, max_grad_norm, device, dtype,
                 None, optimizer_type, master_weights=master_weights, moments_8bit=moments_8bit, grad_accum=grad_accum,
                 decay_to_base=decay_to_base, base_state=base_state, weight_ema=weight_ema, ema_warmup=ema_warmup,
-                stochastic_rounding=stochastic_rounding, max_drift=max_drift, max_drift_scope=max_drift_scope)
+                stochastic_rounding=stochastic_rounding, max_drift=max_drift, max_drift_scope=max_drift_scope,
+                sam_rho=sam_rho, sam_adaptive=sam_adaptive, sam_eta=sam_eta)

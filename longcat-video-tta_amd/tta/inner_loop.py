@@ -78,7 +78,8 @@ def _variant_pool(train_latents, variants) -> List[torch.Tensor]:
 def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers: Sequence, loss_at: Callable[[int], torch.Tensor],
                    clip_and_step: Callable[[], None], num_steps: int, lr: float = 0.0, warmup_steps: int = 0,
                    early_stopper: Optional[AnchoredEarlyStopper] = None, grad_sync: Optional[Callable[[], None]] = None,
-                   after_step: Optional[Callable[[], None]] = None, finish_eval: bool = True, grad_accum: int = 1) -> Dict:
+                   sam: Optional["_Sam"] = None, after_step: Optional[Callable[[], None]] = None, finish_eval: bool = True,
+                   grad_accum: int = 1) -> Dict:
     """`loss_at(step)` returns the differentiable loss of that step; `clip_and_step()` owns clipping + the update.
 
     `grad_accum=N` with N > 1 puts N micro-steps behind every optimizer step: `loss_at(step * N + k)`, backward, `grad_sync()`
@@ -90,12 +91,18 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
     before the stopper looks at the parameters: the projection of `--max-drift` (`_MaxDrift`, include/lcv_hip_trust.h), so that
     what the stopper scores and snapshots are projected iterates.
 
+    `sam` (a `_Sam`, `--sam-rho`, include/lcv_hip_sam.h) makes every optimizer step a sharpness-aware one: two forward/backward
+    passes under the same generator states with the parameters perturbed in between and restored before `clip_and_step()`,
+    which is unchanged.  The logged loss is the first pass's; the result gains the `sam` entry.  Not with `grad_accum` > 1.
+
     Optimizers that keep a weight average (`opt.weight_ema is not None`, include/lcv_hip_ema.h) have it swapped into the
     parameters around every due check of the stopper - so the average is what is scored and what `keeper.capture` snapshots,
     while training goes on from the raw masters, untouched bit for bit - and, without a stopper, once at the end, so that
     generation reads the average."""
     if grad_accum < 1:
         raise ValueError(f"grad_accum must be at least 1, got {grad_accum}")
+    if sam is not None and grad_accum > 1:
+        raise ValueError(SAM_REFUSALS["grad_accum"])
     averaged = [opt for opt in optimizers if getattr(opt, "weight_ema", None) is not None]
     device = params[0].device
     log = _LossLog(num_steps, device)
@@ -116,6 +123,8 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
                     group["lr"] = lr * (step + 1) / warmup_steps
         if grad_accum > 1:
             loss = _accumulate_micro_steps(optimizers, loss_at, grad_sync, step, grad_accum)
+        elif sam is not None:
+            loss = sam.two_passes(loss_at, step, grad_sync)
         else:
             loss = loss_at(step)
             loss.backward()
@@ -159,7 +168,94 @@ def run_adaptation(module: nn.Module, params: Sequence[torch.Tensor], optimizers
     if finish_eval:
         module.eval()
     return {"losses": log.to_list(), "train_time": elapsed, "es_check_time": es_seconds,
-            "early_stopping_info": early_stopper.state if early_stopper is not None else None}
+            "early_stopping_info": early_stopper.state if early_stopper is not None else None,
+            **({} if sam is None else {"sam": sam.finish()})}
+
+
+SAM_REFUSALS = {
+    "grad_accum": "sam_rho cannot be combined with grad_accum > 1 (a perturbation per micro-step is a different algorithm)",
+    "dora": "sam_rho cannot be combined with DoRA magnitudes (the row norm is held constant in the backward and the forward "
+            "caches it)",
+    "sp": "sam_rho cannot be combined with sequence parallelism (not exercised)",
+}
+
+
+def _rng_capture(device):
+    """The host generator's state and, for a GPU, its default generator's: both live on the host, nothing waits for the device."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        return torch.get_rng_state(), None, None
+    gen = torch.cuda.default_generators[device.index if device.index is not None else torch.cuda.current_device()]
+    return torch.get_rng_state(), gen, gen.get_state()
+
+
+def _rng_replay(captured) -> None:
+    host, gen, state = captured
+    torch.set_rng_state(host)
+    if gen is not None:
+        gen.set_state(state)
+
+
+def sam_two_passes(optimizers, loss_at, step: int, grad_sync, perturb, restore, device):
+    """One sharpness-aware step up to the optimizer's: first pass, `perturb(optimizers)`, gradients dropped, generators put
+    back, second pass, `restore(optimizers)`.  The second pass sees the sigma, noise, augmentation variant and dropout masks of
+    the first and leaves the generators exactly where a plain step would.  Returns (first loss, perturbed loss)."""
+    captured = _rng_capture(device)
+    loss = loss_at(step)
+    loss.backward()
+    if grad_sync is not None:
+        grad_sync()
+    perturb(optimizers)
+    for opt in optimizers:
+        opt.zero_grad(set_to_none=True)
+    _rng_replay(captured)
+    loss_p = loss_at(step)
+    loss_p.backward()
+    if grad_sync is not None:
+        grad_sync()
+    restore(optimizers)
+    return loss, loss_p
+
+
+class _Sam:
+    """`--sam-rho RHO` for one adaptation (include/lcv_hip_sam.h): prepares every optimizer of the loop for one joint
+    perturbation, runs the loop's two passes per step, keeps the perturbed losses in a device-side log of their own and
+    afterwards gives the loop's result its `sam` entry."""
+
+    def __init__(self, opts, rho: float, adaptive: bool, eta: float, num_steps: int):
+        from lcv_hip import optim
+        self._optim, self.opts = optim, list(opts)
+        for opt in self.opts:
+            opt.enable_sam(rho, adaptive, eta, trace_len=max(int(num_steps), 1))
+        self._device = self.opts[0].params[0].device
+        self._log = _LossLog(num_steps, self._device)
+
+    def two_passes(self, loss_at, step: int, grad_sync) -> torch.Tensor:
+        loss, loss_p = sam_two_passes(self.opts, loss_at, step, grad_sync, self._optim.sam_perturb, self._optim.sam_restore,
+                                      self._device)
+        self._log.push(loss_p)
+        return loss
+
+    def finish(self) -> Dict:
+        """After the loop (after the stopper's restore): the traces in one copy per optimizer and the perturbed losses in one."""
+        return {**self._optim.sam_stats(self.opts), "perturbed_loss_trace": self._log.to_list()}
+
+
+def sam_hook(opts, rho: Optional[float], adaptive: bool, eta: float, num_steps: int) -> Optional[_Sam]:
+    """A `_Sam` over `opts`, or None without a rho (then nothing is imported, allocated or launched)."""
+    return None if rho is None else _Sam(opts, rho, adaptive, eta, num_steps)
+
+
+def refuse_sam(module, sam_rho, grad_accum: int = 1, dora_magnitudes=None) -> None:
+    """What the sharpness-aware step is not combined with, each with its one-line reason; nothing without a rho."""
+    if sam_rho is None:
+        return
+    if grad_accum > 1:
+        raise ValueError(SAM_REFUSALS["grad_accum"])
+    if dora_magnitudes:
+        raise ValueError(SAM_REFUSALS["dora"])
+    if getattr(getattr(module, "dit", module), "_sp_group", None) is not None:
+        raise ValueError(SAM_REFUSALS["sp"])
 
 
 class _MaxDrift:
@@ -331,6 +427,7 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
                                   train_latents_variants: Optional[List[Dict]] = None, stochastic_rounding: bool = False,
                                   dora_magnitudes: Optional[Sequence[torch.Tensor]] = None,
                                   max_drift: Optional[float] = None, max_drift_scope: str = "global",
+                                  sam_rho: Optional[float] = None, sam_adaptive: bool = False, sam_eta: float = 0.01,
                                   *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                                   grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """`stochastic_rounding`: the bf16 adapters and moments take the fp32 step with stochastically rounded stores
@@ -339,9 +436,13 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
     under one joint clip; the stopper's snapshot covers both lists.
     `max_drift` (with `master_weights`): after every step the adapters are projected onto a ball of that RMS radius around bf16
     clones of their freshly initialised values (+2 B / adapter parameter; include/lcv_hip_trust.h); the result gains
-    `drift_norm` and `max_drift`."""
+    `drift_norm` and `max_drift`.
+    `sam_rho` (>= 0; `sam_adaptive`, `sam_eta`): every step is a sharpness-aware one (include/lcv_hip_sam.h, two
+    forward/backward passes, +2 B / adapter parameter of saved words); the result gains `sam`.  Not with `grad_accum` > 1, DoRA
+    magnitudes or sequence parallelism."""
     params = _adapter_params(lora_modules, lora_param_fn)
     _refuse_max_drift_with_dora(max_drift, dora_magnitudes)
+    refuse_sam(dit, sam_rho, grad_accum, dora_magnitudes)
     refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
     dora_opt = _dora_optimizer(dit, dora_magnitudes, lr, master_weights=master_weights, moments_8bit=moments_8bit,
                                stochastic_rounding=stochastic_rounding, weight_ema=weight_ema is not None,
@@ -359,8 +460,8 @@ def finetune_lora_on_conditioning(dit: nn.Module, lora_modules, cond_latents: to
                               _joint_optimizer_step(opts, max_grad_norm), num_steps, lr, warmup_steps, early_stopper)
     ball = max_drift_hook([opt], max_drift, max_drift_scope, num_steps, _clones(params, max_drift))
     out = run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
-                         num_steps, lr, warmup_steps, early_stopper, grad_sync=_sp_sync(dit, opt), after_step=ball,
-                         grad_accum=grad_accum)
+                         num_steps, lr, warmup_steps, early_stopper, grad_sync=_sp_sync(dit, opt),
+                         sam=sam_hook([opt], sam_rho, sam_adaptive, sam_eta, num_steps), after_step=ball, grad_accum=grad_accum)
     return out if ball is None else ball.finish(out)
 
 
@@ -369,14 +470,16 @@ def finetune_lora_batch(dit: nn.Module, lora_modules, batch_data: List[Dict], nu
                         device: str = "cuda", dtype: torch.dtype = torch.bfloat16, lora_param_fn=None,
                         stochastic_rounding: bool = False, dora_magnitudes: Optional[Sequence[torch.Tensor]] = None,
                         max_drift: Optional[float] = None, max_drift_scope: str = "global",
+                        sam_rho: Optional[float] = None, sam_adaptive: bool = False, sam_eta: float = 0.01,
                         *, weight_ema: Optional[float] = None, ema_warmup: bool = False,
                         grad_accum: int = 1, moments_8bit: bool = False, master_weights: bool = False) -> Dict:
     """Shared adapters trained round-robin over the eval video and its neighbours; no early stopping (:558-634).  The feed
     receives the micro-step index, so `grad_accum` = number of videos puts every video behind each update.  `weight_ema`: the
     adapters end as their fp32 average over the steps.  `stochastic_rounding` and `dora_magnitudes`: as in
-    `finetune_lora_on_conditioning`; `max_drift` likewise."""
+    `finetune_lora_on_conditioning`; `max_drift` and `sam_rho` likewise."""
     params = _adapter_params(lora_modules, lora_param_fn)
     _refuse_max_drift_with_dora(max_drift, dora_magnitudes)
+    refuse_sam(dit, sam_rho, grad_accum, dora_magnitudes)
     refuse_stochastic_rounding_under_sp(dit, stochastic_rounding)
     dora_opt = _dora_optimizer(dit, dora_magnitudes, lr, master_weights=master_weights, moments_8bit=moments_8bit,
                                stochastic_rounding=stochastic_rounding, weight_ema=weight_ema is not None,
@@ -393,5 +496,6 @@ def finetune_lora_batch(dit: nn.Module, lora_modules, batch_data: List[Dict], nu
                               _joint_optimizer_step(opts, max_grad_norm), num_steps, lr, warmup_steps, None)
     ball = max_drift_hook([opt], max_drift, max_drift_scope, num_steps, _clones(params, max_drift))
     out = run_adaptation(dit, params, [opt], _fm_loss(dit, feed, device, dtype), _single_optimizer_step(opt, max_grad_norm),
-                         num_steps, lr, warmup_steps, None, grad_sync=_sp_sync(dit, opt), after_step=ball, grad_accum=grad_accum)
+                         num_steps, lr, warmup_steps, None, grad_sync=_sp_sync(dit, opt),
+                         sam=sam_hook([opt], sam_rho, sam_adaptive, sam_eta, num_steps), after_step=ball, grad_accum=grad_accum)
     return out if ball is None else ball.finish(out)

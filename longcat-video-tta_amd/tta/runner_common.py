@@ -50,6 +50,7 @@ def add_common_args(p):
 def add_shared_groups(p, clip_gate: bool = True):
     """The groups of the adapting runners (the baseline runner builds its own parser)."""
     C.add_max_drift_args(p)
+    C.add_sam_args(p)
     add_early_stopping_args(p)
     C.add_augmentation_args(p)
     C.add_tta_frame_args(p)
@@ -536,12 +537,12 @@ def run_delta_method(args, method: str, make_wrapper: Callable, optimize_fn: Cal
 
     def row_extra(opt, variants, blob):
         return {**({"aug_variants": [v["name"] for v in variants]} if variants is not None else {}), **result_extra(opt),
-                **C.max_drift_result(opt)}
+                **C.max_drift_result(opt), **C.sam_result(opt)}
 
     def summary_extra(merged, ok):
         return {**summary_head, **(clip_gate_summary(args) if hasattr(args, "clip_gate_enabled") else {}),
                 **C.step_cache_record(args), **C.solver_record(args), **C.cfg_reuse_record(args),
-                **C.apg_record(args), **C.max_drift_record(args)}
+                **C.apg_record(args), **C.max_drift_record(args), **C.sam_record(args)}
 
     run_tta_job(args, TTAMethod(name=method, file_suffix=file_suffix, prepare=freeze, adapt=adapt, row_extra=row_extra,
                                 summary_extra=summary_extra, make_model=make_wrapper, generating=_hooks_installed,
